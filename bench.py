@@ -7,11 +7,17 @@ each), rendered by the HIP megakernel into a float32 framebuffer in HBM, plus
 render interleaved rows of the same image (strong scaling); every rank splats
 into its own full-frame buffer, so the reduce is the path's one exchange step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Rank 0 prints one JSON line (metric, value = whole-job Msamples/s, roofline of
-the render kernel, cpu_baseline = the reference CPU path timed on this host).
+A plain run sets up, renders W warm-up and K timed steps and rank 0 prints one
+JSON line (metric, value = whole-job Msamples/s, ms_per_step). --dump-outputs DIR
+also writes the last timed step's framebuffer to DIR/framebuffer.npy (float32;
+the scene, camera and per-(pixel, sample) seeds are fixed, so two builds run with
+the same arguments render the same inputs). --full adds what takes runs of its
+own: the roofline of the render kernel (an untimed counting pass priced by the
+byte model, the build-stamped PMC summaries), cpu_baseline = the reference CPU
+path timed on this host, and the in-run parity check against its frame.
 """
 from __future__ import annotations
 
@@ -210,6 +216,24 @@ def issue_roofline(deep: dict, kernel_s: float) -> dict | None:
     return out
 
 
+DUMP_MAX_FLOATS = 15_000_000  # 60 MB of float32: --dump-outputs writes at most 64 MB in all
+
+
+def dump_outputs(dirname: str, fb, W: int, H: int) -> None:
+    """--dump-outputs: the framebuffer the timed path left after its last step (what a
+    caller of render_device receives; with N > 1 ranks, rank 0's reduced frame), as
+    DIR/framebuffer.npy, float32 (H, W, 3). A frame over the size limit is written as a
+    fixed, seeded sample of its pixels, (K, 3), in ascending pixel order."""
+    import numpy as np
+
+    a = fb.detach().cpu().numpy().astype(np.float32, copy=False).reshape(H, W, 3)
+    if a.size > DUMP_MAX_FLOATS:
+        pix = np.sort(np.random.default_rng(0).choice(H * W, DUMP_MAX_FLOATS // 3, replace=False))
+        a = a.reshape(-1, 3)[pix]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "framebuffer.npy"), a)
+
+
 def heartbeat(period: float = 30.0) -> None:
     """A line on stderr every `period` s while the process runs (a Russian-roulette
     frame is one kernel of a minute or more: without output it looks hung)."""
@@ -236,7 +260,12 @@ def main() -> None:
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--spp", type=int, default=256)
     ap.add_argument("--rr-depth", type=int, default=None)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's framebuffer to DIR/framebuffer.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the counting pass and roofline, the CPU "
+                         "baseline (unless --no-cpu) and the in-run parity check against it (unless --no-parity)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline (and the parity check)")
     ap.add_argument("--count-spp", type=int, default=None,
                     help="spp of the untimed counting pass (default min(spp, 16); 1 with --russian-roulette, where "
                          "a trapped subpath's chain runs at the lone lane's pace in that pass)")
@@ -396,6 +425,8 @@ def main() -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, fbs[(nstep[0] - 1) % nctx] if nctx > 1 else fb, W, H)
     samples_total = W * H * spp  # all ranks together, per step
     value = samples_total * args.steps / elapsed * 1e-6
     local_samples = integ.stats()["samples"]
@@ -430,75 +461,78 @@ def main() -> None:
                           "kernel_ms": round(avg_kernel_ms, 3)}}
         if ranks:
             out["ranks"] = ranks
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args.scene, W, H, spp, rr, integrator=args.integrator)
         print(json.dumps(out), flush=True)
     elif rank == 0:
-        # algorithmic bytes per sample from a counting pass (untimed, same seeds, smaller spp)
-        # (Russian roulette: 1 spp by default — the counting pass keeps every walk in the
-        # megakernel, so a trapped subpath's chain there runs at the lone lane's pace; at 1 spp
-        # every lane holds one sample, so its SIMD-efficiency counters measure a frame that is
-        # all drain: --count-spp 16 for scenes without trapped subpaths)
-        count_spp = args.count_spp or (1 if args.russian_roulette else min(spp, 16))
-        cnt_cfg = bdpt_amd.Config(camera=cfg.camera, width=W, height=H, spp=count_spp,
-                                  rr_depth=rr,
-                                  russian_roulette=rrm)
-        cnt = bdpt_amd.BDPTIntegrator(integ.scene, cnt_cfg, device=gpu if world > 1 else 0)
-        cbuf = torch.zeros(W * H * 3, dtype=torch.float32, device=dev)
-        cnt.render_device(cbuf.data_ptr(), stream, flags=bdpt_amd.FLAG_COUNT)
-        cst = cnt.stats()
-        cts = cst["counters"]
-        bps = algorithmic_bytes_per_sample(cts, cst["samples"], SURVEY_BYTES)
-        bps_layout = algorithmic_bytes_per_sample(cts, cst["samples"], LAYOUT_BYTES)
-        kernel_s = avg_kernel_ms * 1e-3
-        achieved = bps * local_samples / kernel_s / 1e9
         workload = f"{args.scene}_{W}x{H}_{spp}spp" + ("_rr" if args.russian_roulette else "")
-        build = bdpt_amd.kernel_build_hash()
-        # measured memory-side traffic and issue counters of THIS kernel build
-        # (rocprofv3 --pmc passes, tools/profile_round.sh / tools/pmc_deep.sh)
-        pm = stamped(os.path.join(args.profiles, f"pmc_{workload}.json"), build)
-        deep = stamped(os.path.join(args.profiles, f"pmc_deep_{workload}.json"), build)
-        traffic = pm["hbm_bytes_per_launch"] * local_samples / pm["samples_per_launch"] if pm else None
-        roof = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
-                "kernel": cst.get("kernel") or "bdpt_frame_kernel",
-                "kernel_build": build, "schedule": "megakernel", "kernel_ms": round(avg_kernel_ms, 3),
-                "samples_per_launch": local_samples,
-                "byte_model": "SURVEY.md 8(d): 64 B/node visit, 36 B/triangle test, 40 B/closest hit, "
-                              "64 B/light vertex written or read, 12 B/framebuffer add",
-                "bytes_per_sample": round(bps, 1),
-                "bytes_per_sample_layout_model": round(bps_layout, 1),
-                "achieved_layout_model": round(bps_layout * local_samples / kernel_s / 1e9, 2),
-                "counts_per_sample": {k: round(v / cst["samples"], 3) for k, v in cts.items()},
-                # the counting pass's schedule counters (bdpt_stats.sched; Counts::q), per sample
-                "sched_per_sample": {k: round(v / cst["samples"], 4) for k, v in cst["sched"].items()},
-                # the persistent grid's end tail (device clock: the frame's last 64-sample chunk
-                # claimed -> last wave done), what a 1/N row shard pays again per rank
-                "tail_ms": round(sum(tail_ms) / max(len(tail_ms), 1), 3)}
-        if traffic is not None:
-            roof["dram_achieved"] = round(traffic / kernel_s / 1e9, 2)
-            roof["dram_frac"] = round(traffic / kernel_s / 1e9 / HBM_PEAK_GBPS, 5)
-            roof["traffic_over_algorithmic"] = round(traffic / (bps * local_samples), 4)
-            roof["traffic_source"] = pm.get("source")
-            # FETCH_SIZE's x2 (MI355X_MICROARCH.md: 128-B requests tallied at 64 B) is calibrated on
-            # wide streaming reads only; this kernel's reads are 16-B gathers, so both readings are
-            # reported: `traffic` takes the doubled one (the upper bound)
-            scale = local_samples / pm["samples_per_launch"]
-            roof["traffic_bounds"] = {
-                "fetch_x1": round((pm["fetch_size_kib_raw"] * 1024 + pm["write_bytes"]) * scale),
-                "fetch_x2": round(traffic),
-                "write": round(pm["write_bytes"] * scale),
-                "write_over_algorithmic_writes": round(pm["write_bytes"] * scale / max(
-                    1.0, algorithmic_write_bytes(cts, cst["samples"]) * local_samples), 3)}
-        if deep is not None:
-            roof["limiter"] = deep.get("limiter")
-            for k in ("active_lane_frac", "valu_issue_frac", "wait_frac", "valu_insts_per_sample"):
-                roof[k] = deep.get(k)
-            roof["issue_source"] = deep.get("source")
-            issue = issue_roofline(deep, kernel_s * pm_scale(deep, local_samples))
-            if issue:
-                roof["issue"] = issue
-                roof["binding"] = issue["bound"]
+        # the persistent grid's end tail (device clock: the frame's last 64-sample chunk
+        # claimed -> last wave done), what a 1/N row shard pays again per rank
+        avg_tail_ms = round(sum(tail_ms) / max(len(tail_ms), 1), 3)
+        roof = cst = cts = None
+        if args.full:
+            # algorithmic bytes per sample from a counting pass (untimed, same seeds, smaller spp)
+            # (Russian roulette: 1 spp by default — the counting pass keeps every walk in the
+            # megakernel, so a trapped subpath's chain there runs at the lone lane's pace; at 1 spp
+            # every lane holds one sample, so its SIMD-efficiency counters measure a frame that is
+            # all drain: --count-spp 16 for scenes without trapped subpaths)
+            count_spp = args.count_spp or (1 if args.russian_roulette else min(spp, 16))
+            cnt_cfg = bdpt_amd.Config(camera=cfg.camera, width=W, height=H, spp=count_spp,
+                                      rr_depth=rr,
+                                      russian_roulette=rrm)
+            cnt = bdpt_amd.BDPTIntegrator(integ.scene, cnt_cfg, device=gpu if world > 1 else 0)
+            cbuf = torch.zeros(W * H * 3, dtype=torch.float32, device=dev)
+            cnt.render_device(cbuf.data_ptr(), stream, flags=bdpt_amd.FLAG_COUNT)
+            cst = cnt.stats()
+            cts = cst["counters"]
+            bps = algorithmic_bytes_per_sample(cts, cst["samples"], SURVEY_BYTES)
+            bps_layout = algorithmic_bytes_per_sample(cts, cst["samples"], LAYOUT_BYTES)
+            kernel_s = avg_kernel_ms * 1e-3
+            achieved = bps * local_samples / kernel_s / 1e9
+            build = bdpt_amd.kernel_build_hash()
+            # measured memory-side traffic and issue counters of THIS kernel build
+            # (rocprofv3 --pmc passes, tools/profile_round.sh / tools/pmc_deep.sh)
+            pm = stamped(os.path.join(args.profiles, f"pmc_{workload}.json"), build)
+            deep = stamped(os.path.join(args.profiles, f"pmc_deep_{workload}.json"), build)
+            traffic = pm["hbm_bytes_per_launch"] * local_samples / pm["samples_per_launch"] if pm else None
+            roof = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
+                    "kernel": cst.get("kernel") or "bdpt_frame_kernel",
+                    "kernel_build": build, "schedule": "megakernel", "kernel_ms": round(avg_kernel_ms, 3),
+                    "samples_per_launch": local_samples,
+                    "byte_model": "SURVEY.md 8(d): 64 B/node visit, 36 B/triangle test, 40 B/closest hit, "
+                                  "64 B/light vertex written or read, 12 B/framebuffer add",
+                    "bytes_per_sample": round(bps, 1),
+                    "bytes_per_sample_layout_model": round(bps_layout, 1),
+                    "achieved_layout_model": round(bps_layout * local_samples / kernel_s / 1e9, 2),
+                    "counts_per_sample": {k: round(v / cst["samples"], 3) for k, v in cts.items()},
+                    # the counting pass's schedule counters (bdpt_stats.sched; Counts::q), per sample
+                    "sched_per_sample": {k: round(v / cst["samples"], 4) for k, v in cst["sched"].items()},
+                    "tail_ms": avg_tail_ms}
+            if traffic is not None:
+                roof["dram_achieved"] = round(traffic / kernel_s / 1e9, 2)
+                roof["dram_frac"] = round(traffic / kernel_s / 1e9 / HBM_PEAK_GBPS, 5)
+                roof["traffic_over_algorithmic"] = round(traffic / (bps * local_samples), 4)
+                roof["traffic_source"] = pm.get("source")
+                # FETCH_SIZE's x2 (128-B requests are tallied at 64 B on this part) is calibrated on
+                # wide streaming reads only; this kernel's reads are 16-B gathers, so both readings are
+                # reported: `traffic` takes the doubled one (the upper bound)
+                scale = local_samples / pm["samples_per_launch"]
+                roof["traffic_bounds"] = {
+                    "fetch_x1": round((pm["fetch_size_kib_raw"] * 1024 + pm["write_bytes"]) * scale),
+                    "fetch_x2": round(traffic),
+                    "write": round(pm["write_bytes"] * scale),
+                    "write_over_algorithmic_writes": round(pm["write_bytes"] * scale / max(
+                        1.0, algorithmic_write_bytes(cts, cst["samples"]) * local_samples), 3)}
+            if deep is not None:
+                roof["limiter"] = deep.get("limiter")
+                for k in ("active_lane_frac", "valu_issue_frac", "wait_frac", "valu_insts_per_sample"):
+                    roof[k] = deep.get(k)
+                roof["issue_source"] = deep.get("source")
+                issue = issue_roofline(deep, kernel_s * pm_scale(deep, local_samples))
+                if issue:
+                    roof["issue"] = issue
+                    roof["binding"] = issue["bound"]
         default_workload = (args.scene, W, H, spp) == ("caustic", 512, 512, 256) and not args.russian_roulette
         out = {
             "metric": METRIC if default_workload else f"Msamples/sec (whole node), {SCENE_LABEL.get(args.scene, args.scene)} "
@@ -517,16 +551,18 @@ def main() -> None:
                      else "synthetic camera samples over a generated 1M-triangle scene"),
             "config": {"workload": workload, "scene": SCENE_LABEL.get(args.scene, args.scene),
                        "width": W, "height": H, "spp": spp, "rr_depth": rr, "samples_per_step": samples_total,
-                       "frames_in_flight": nctx,
+                       "frames_in_flight": nctx, "kernel_ms": round(avg_kernel_ms, 3),
                        "parallelism": (f"{world}-way row-interleaved shards + one framebuffer sum-reduce "
                                        f"({ranks['backend']})" if ranks else "one GPU, whole image (no reduce)")},
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         if args.russian_roulette:
             # Russian roulette: subpath depth is unbounded (bdpt.h:68, :188); the timed frames'
-            # samples that met the store / bounce bounds (must be 0) and the counting pass's maxima
+            # samples that met the store / bounce bounds (must be 0) and, with --full, the counting
+            # pass's maxima
             out["config"]["russian_roulette"] = "NO_RR = 0 (bdpt.h:18)"
-            out["russian_roulette"] = {"capped_samples_per_step": capped, "counting_pass_spp": cnt_cfg.spp,
+            out["russian_roulette"] = {"capped_samples_per_step": capped,
                                        "parked_walks_per_step": parked,
                                        # walks deeper than 512 bounces one wave held at once (max), and the
                                        # express-mode loop iterations of waves holding 1 / 2..4 / more of them
@@ -534,16 +570,20 @@ def main() -> None:
                                        "express_iters_1_2to4_more_per_step": express,
                                        "continuation": "walks past BDPT_PARK_DEPTH bounces finished by the chain kernel "
                                                        "(one wave per walk) and resume launches",
-                                       "max_light_depth": cst.get("max_light_depth"),
-                                       "max_eye_depth": cst.get("max_eye_depth"),
-                                       "max_queries_per_sample": cst.get("max_queries"),
-                                       # SIMD efficiency of the counting pass (lane iterations / 64 x wave iterations)
-                                       "trav_simd_eff": round(cts["trav_lane_iters"] / max(64 * cts["trav_wave_iters"], 1), 4),
-                                       "shade_simd_eff": round(cts["shade_lane_actions"] / max(64 * cts["shade_wave_actions"], 1), 4),
-                                       "tail_ms": roof["tail_ms"], "kernel": cst.get("kernel")}
+                                       "tail_ms": avg_tail_ms}
+            if cst is not None:
+                out["russian_roulette"].update({
+                    "counting_pass_spp": cnt_cfg.spp,
+                    "max_light_depth": cst.get("max_light_depth"),
+                    "max_eye_depth": cst.get("max_eye_depth"),
+                    "max_queries_per_sample": cst.get("max_queries"),
+                    # SIMD efficiency of the counting pass (lane iterations / 64 x wave iterations)
+                    "trav_simd_eff": round(cts["trav_lane_iters"] / max(64 * cts["trav_wave_iters"], 1), 4),
+                    "shade_simd_eff": round(cts["shade_lane_actions"] / max(64 * cts["shade_wave_actions"], 1), 4),
+                    "kernel": cst.get("kernel")})
         if ranks:
             out["ranks"] = ranks
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             ref_fb = None if args.no_parity else os.path.join("/tmp", f"bench_ref_fb_{os.getpid()}.f32")
             cb = cpu_baseline(args.scene, W, H, spp, rr, frame_out=ref_fb, russian_roulette=args.russian_roulette)
             out["cpu_baseline"] = {k: v for k, v in cb.items() if k != "row_stride"}

@@ -82,7 +82,7 @@ ab)
       [ "$name" != "$lib" ] && envs=${lib#*:}
       tag=$(echo "$lib" | tr ':=,' '_-_')
       out=gpurun_out/${LABEL}_${tag}_$rep.json
-      env ${envs//,/ } BDPT_AMD_LIB=$(lib_path $name) timeout -k 10 300 python3 bench.py --no-cpu --no-parity "$@" > $out 2> ${out%.json}.err
+      env ${envs//,/ } BDPT_AMD_LIB=$(lib_path $name) timeout -k 10 300 python3 bench.py --full --no-cpu --no-parity "$@" > $out 2> ${out%.json}.err
       rc=$?
       if [ $rc -ne 0 ]; then echo "$lib rep $rep rc=$rc" >> gpurun_out/$LABEL.txt; tail -5 ${out%.json}.err; exit $rc; fi
       summary ${tag}_$rep $out | tee -a gpurun_out/$LABEL.txt
@@ -96,7 +96,7 @@ final|final_a|final_b|final_c|final_tc|final_pc|final_ac)
   P=gpurun_out/prof_$LABEL
   kt() {  # name limit bench args...: the bench line under the kernel trace
     local name=$1 lim=$2; shift 2
-    echo "$lim ${LABEL}_bench_$name.json -- rocprofv3 --kernel-trace --stats -d $P/kt_$name -o kt --output-format csv -- python3 bench.py $*"
+    echo "$lim ${LABEL}_bench_$name.json -- rocprofv3 --kernel-trace --stats -d $P/kt_$name -o kt --output-format csv -- python3 bench.py --full $*"
   }
   A=( \
     "500 ${LABEL}_gpu_tests.log -- python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread" \

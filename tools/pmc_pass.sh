@@ -9,7 +9,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $CTRS -d $OUT/raw -o p --output-format csv -- \
-  python3 $R/bench.py --no-cpu --no-parity --steps 1 --warmup 0 "$@" > $OUT/run.log 2>&1 || exit $?
+  python3 $R/bench.py --full --no-cpu --no-parity --steps 1 --warmup 0 "$@" > $OUT/run.log 2>&1 || exit $?
 cd $R
 python3 tools/pmc_counters.py $OUT/raw "bdpt_frame_kernel<false, false, false>" $OUT/run.log > $OUT/summary.json
 cat $OUT/summary.json

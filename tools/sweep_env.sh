@@ -9,7 +9,8 @@ mkdir -p gpurun_out
 i=0
 for e in "${SETS[@]}"; do
   i=$((i + 1))
-  env $e timeout -k 10 200 python3 bench.py --no-cpu --no-parity --steps 3 --warmup 1 "$@" > gpurun_out/sweepenv_$i.json 2>gpurun_out/sweepenv_$i.err || { echo "$e FAILED" >> $OUT; exit 1; }
-  python3 -c "import json; d=json.loads(open('gpurun_out/sweepenv_$i.json').read().strip().splitlines()[-1]); print('$e', d['value'], d['roofline']['kernel_ms'])" >> $OUT
+  J=$(dirname "$OUT")/sweepenv_$i  # the run's JSON line and stderr, next to OUT.txt
+  env $e timeout -k 10 200 python3 bench.py --full --no-cpu --no-parity --steps 3 --warmup 1 "$@" > $J.json 2>$J.err || { echo "$e FAILED" >> $OUT; exit 1; }
+  python3 -c "import json; d=json.loads(open('$J.json').read().strip().splitlines()[-1]); print('$e', d['value'], d['roofline']['kernel_ms'])" >> $OUT
   tail -1 $OUT
 done

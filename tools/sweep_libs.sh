@@ -11,7 +11,8 @@ mkdir -p gpurun_out
 for n in "${NAMES[@]}"; do
   if [ "$n" == "default" ]; then LIB=$PWD/bidirectional-path-tracing_amd/lib/libbdpt_amd.so
   else LIB=$PWD/bidirectional-path-tracing_amd/lib/libbdpt_amd_$n.so; fi
-  BDPT_AMD_LIB=$LIB timeout -k 10 150 python3 bench.py --no-cpu --no-parity --steps 3 --warmup 1 "$@" > gpurun_out/sweep_$n.json 2>gpurun_out/sweep_$n.err || { echo "$n FAILED" >> $OUT; exit 1; }
-  python3 -c "import json,sys; d=json.loads(open('gpurun_out/sweep_$n.json').read().strip().splitlines()[-1]); print('$n', d['value'], d['roofline']['kernel_ms'])" >> $OUT
+  J=$(dirname "$OUT")/sweep_$n  # the run's JSON line and stderr, next to OUT.txt
+  BDPT_AMD_LIB=$LIB timeout -k 10 150 python3 bench.py --full --no-cpu --no-parity --steps 3 --warmup 1 "$@" > $J.json 2>$J.err || { echo "$n FAILED" >> $OUT; exit 1; }
+  python3 -c "import json,sys; d=json.loads(open('$J.json').read().strip().splitlines()[-1]); print('$n', d['value'], d['roofline']['kernel_ms'])" >> $OUT
   cat $OUT | tail -1
 done
