@@ -678,14 +678,12 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     c->sc.gdepth = static_cast<uint32_t>(std::max(1, depth - lds_entries));  // per slot (DevScene::gdepth)
     const size_t spill_mega = static_cast<size_t>(c->sc.gdepth) * c->nslots;
     HIP_TRY(hipMalloc(&c->gstack, sizeof(uint2) * std::max<size_t>(1, spill_mega)));
-    // shadow-ray task rings, one per wave of the persistent grid (4096 waves x 256 x 48 B = 50 MB on
-    // 256 CUs); only builds with BDPT_HELP read them
+    // shadow-ray task rings: their capacity here, their memory in ensure_tasks
     c->task_cap = kTaskCap;
     if (const char* e = std::getenv("BDPT_TASK_CAP")) {  // (sweeps) a power of two in [64, 4096]
         const int v = std::atoi(e);
         if (v >= 64 && v <= 4096 && (v & (v - 1)) == 0) c->task_cap = static_cast<uint32_t>(v);
     }
-    HIP_TRY(hipMalloc(&c->tasks, sizeof(float4) * 3 * c->task_cap * (c->nslots / 64)));
     *out = c.release();
     return BDPT_OK;
 }
@@ -744,6 +742,15 @@ static int ensure_lv(bdpt_ctx* c, int lv_max, uint32_t nslots) {
     return BDPT_OK;
 }
 
+// Shadow-ray task rings, one per wave of the persistent grid (4096 waves x 256 x 40 B = 42 MB
+// on 256 CUs). Only the frame kernels without Russian roulette (BDPT_HELP builds) use them,
+// so the first render that launches one allocates them; the context's destruction frees them.
+static int ensure_tasks(bdpt_ctx* c) {
+    if (!c->tasks)
+        HIP_TRY(hipMalloc(&c->tasks, static_cast<size_t>(dev::kTaskBytes) * c->task_cap * (c->nslots / 64)));
+    return BDPT_OK;
+}
+
 // Interior boxes of the triangle traversal tree are padded by kTriBoxPad x the
 // scene diagonal (wide_bvh.hpp), so a ray that hits a triangle passes through
 // every box above it over a t-interval of at least 2 pad; slab_fast's rounding
@@ -793,6 +800,7 @@ int bdpt_render(bdpt_ctx* c, const bdpt_frame_params* p, float* fb, void* hip_st
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     dev::DevFrame fr = make_frame(p);
     fr.capped = c->capped;
+    if (!fr.rr_mode && fr.total_samples > 0 && (rc = ensure_tasks(c))) return rc;
     fr.tasks = c->tasks;
     fr.task_cap = c->task_cap;
     if (c->row_order_n) {

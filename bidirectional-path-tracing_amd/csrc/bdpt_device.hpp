@@ -40,6 +40,19 @@ __device__ __forceinline__ void gst1(float* p, float x) { *(__attribute__((addre
 __device__ __forceinline__ void gst4(float4* p, float4 x) {
     *(__attribute__((address_space(1))) v4f_t*)(p) = v4f_t{x.x, x.y, x.z, x.w};
 }
+typedef float v2f_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float2 gld2(const float2* p) {
+    const v2f_t v = *(const __attribute__((address_space(1))) v2f_t*)(p);
+    return make_float2(v.x, v.y);
+}
+__device__ __forceinline__ void gst2(float2* p, float2 x) { *(__attribute__((address_space(1))) v2f_t*)(p) = v2f_t{x.x, x.y}; }
+
+// Bytes of a shadow-ray task record in the waves' rings (bdpt_path.hpp task_push;
+// the host sizes DevFrame::tasks by it).
+#ifndef BDPT_HELP_SOA
+#define BDPT_HELP_SOA 1  // the ring as planes of 16- and 8-byte vectors (consecutive slots' pushes and claims coalesce)
+#endif
+constexpr uint32_t kTaskBytes = BDPT_HELP_SOA ? 40 : 48;  // 0: whole records of 3 float4 (the last half unused)
 
 struct DevScene {
     const float4* __restrict__ tri;
@@ -190,7 +203,8 @@ struct DevFrame {
     int32_t express_depth;
     uint32_t sched_flags;
     // Shadow-ray task rings of the BDPT_HELP build (bdpt_path.hpp task_push): per
-    // wave task_cap records of 48 bytes (3 float4), wave w's at tasks + 3 * task_cap * w
+    // wave task_cap records of kTaskBytes, wave w's at tasks + kTaskBytes / 16 * task_cap * w
+    // (allocated by the first bdpt_render that launches such a build)
     float4* tasks;
     uint32_t task_cap;
     // the shard's row claim order (bdpt_set_row_order; null: top to bottom) and, in a

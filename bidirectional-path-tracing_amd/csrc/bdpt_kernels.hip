@@ -404,6 +404,9 @@ struct KParams {
 #ifndef BDPT_HELP_DEFER
 #define BDPT_HELP_DEFER 0  // BDPT_HELP: a claimed task's walk begins one walk iteration after its record loads (305.8 vs 323.5: not kept)
 #endif
+#ifndef BDPT_HELP_LAZY_TAIL
+#define BDPT_HELP_LAZY_TAIL 0  // BDPT_HELP: a claim loads the record's plane C only once plane A shows no splat (a second exposed load latency per round for 8 bytes fewer per splat)
+#endif
 #ifndef BDPT_HELP_MIN
 #define BDPT_HELP_MIN 16  // BDPT_HELP: fewest waiting lanes that start a claim round (unless the ring holds fewer tasks; 1 / 8 / 12 / 16 / 20 / 24: 264.9 / 322.7 / 323.3 / 323.4 / 319.8 / 266.4)
 #endif
@@ -1029,29 +1032,41 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                         const uint32_t slot = (head + rank) & (P->fr.task_cap - 1);
                         float4* const ring = task_ring(P->fr);
                         const uint32_t cap = P->fr.task_cap;
-                        const float4 a = gld4(task_vec(ring, cap, slot, 0)), b = gld4(task_vec(ring, cap, slot, 1)),
-                                     c = gld4(task_vec(ring, cap, slot, 2));
+                        // the record (bdpt_path.hpp task_push): (P, meta) (end, c.x | c, -) (c.y, c.z)
+                        const float4 a = gld4(task_vec(ring, cap, slot, 0)), b = gld4(task_vec(ring, cap, slot, 1));
+                        const uint32_t meta = __float_as_uint(a.w);
+#if BDPT_HELP_LAZY_TAIL
+                        const float2 cyz = meta & kTaskSplat ? make_float2(b.y, b.z) : gld2(task_tail(ring, cap, slot));
+#else
+                        const float2 ctl2 = gld2(task_tail(ring, cap, slot));
+                        const float2 cyz = meta & kTaskSplat ? make_float2(b.y, b.z) : ctl2;
+#endif
+                        const f3 c = meta & kTaskSplat ? mk(b.x, cyz.x, cyz.y) : mk(b.w, cyz.x, cyz.y);
+                        const f3 rs = meta & kTaskSplat ? mk(P->fr.cam_o[0], P->fr.cam_o[1], P->fr.cam_o[2]) : xyz(a);
+                        const f3 re = meta & kTaskSplat ? xyz(a) : xyz(b);
+                        const float near = meta & kTaskNoCull ? kNoCullNear : kCullNear;
 #if BDPT_HELP_HOIST
                         // the record's loads are in flight while the lane's own hit is shaded
                         // (one exposed latency per claim round instead of two)
                         if (has_res) help_compact(L, res, rt, ru, rv, P->sc);  // frees L.ray
 #endif
                         if (COUNT) cnt.q[3]++;  // (counting pass: claims)
-                        L.ray = Ray{xyz(a), xyz(b), kEpsilon, a.w};
+                        // visibilityQuery's ray of the two points, by the pusher's own code (the same bits)
+                        L.ray = shadow_ray(rs, re);
                         helping = true;
 #if BDPT_HELP_DEFER
                         // the walk begins next iteration (the loads land meanwhile): the near
                         // cull, contribution and pixel wait in the lane's idle walk registers
-                        ri.near = b.w;
+                        ri.near = near;
                         ts.best_t = c.x, ts.best_u = c.y, ts.best_v = c.z;
-                        ts.link = __float_as_uint(c.w);
+                        ts.link = meta & ~kTaskNoCull;
                         hwait = true;
 #else
-                        // the contribution and pixel into the lane's (free) pending-connection
-                        // fields: the slot may be pushed over once claimed
-                        L.c.pend = xyz(c);
-                        L.c.pend_px = __float_as_int(c.w);
-                        help_begin(b.w);
+                        // the contribution and pixel | splat bit into the lane's (free) pending-
+                        // connection fields: the slot may be pushed over once claimed
+                        L.c.pend = c;
+                        L.c.pend_px = static_cast<int>(meta & ~kTaskNoCull);
+                        help_begin(near);
 #endif
                     }
                 }

@@ -346,6 +346,7 @@ __device__ __forceinline__ void eye_slot_reset(float* __restrict__ fb, int k, in
 #endif
 #if BDPT_HELP && !BDPT_SAMPLER_STATE
 constexpr uint32_t kTaskSplat = 0x40000000u;   // meta bit: a camera splat (framebuffer add, bdpt.h:363-370)
+constexpr uint32_t kTaskNoCull = 0x80000000u;  // meta bit: no near cull (kNoCullNear; clear: kCullNear)
 constexpr uint32_t kTaskPixel = 0x3fffffffu;
 constexpr int kResShaded = -2;  // an own closest-hit result already applied to the lane (walk loop, help_compact)
 // The wave's ring positions live in LDS, in the Russian-roulette field of its
@@ -360,20 +361,42 @@ __device__ __forceinline__ TaskCtl task_ctl(const LaneCold& mine) {
     constexpr uint32_t kRrWord = offsetof(LaneCold, rr) / 4, kStride = sizeof(LaneCold) / 4;
     return TaskCtl{w + kRrWord, w + kStride + kRrWord};
 }
+// A task is its shadow ray's two end points (visibilityQuery is a pure function of
+// them: the taker forms the ray with the pusher's shadow_ray code, the same bits),
+// its contribution and a meta word: pixel | kTaskSplat | kTaskNoCull. A camera
+// splat's start is the camera origin, a frame constant, so its record holds the end
+// only. Three SoA planes per wave, so a round's pushes and claims coalesce:
+//   A float4 (P, meta)     P: the ray's start (eye-side task) or its end (splat)
+//   B float4 (end, c.x)    splat: (c, -)
+//   C float2 (c.y, c.z)    eye-side tasks only
+// 40 bytes stored and loaded for an eye-side task, 28 stored for a splat.
+#if BDPT_HELP_SOA
 __device__ __forceinline__ float4* task_ring(const DevFrame& fr) {
     const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x * 4 + (threadIdx.x >> 6))));
-    return fr.tasks + static_cast<size_t>(wave) * fr.task_cap * 3;
+    return fr.tasks + static_cast<size_t>(wave) * (fr.task_cap / 2) * (kTaskBytes / 8);  // (task_cap is even: a power of two >= 64)
 }
+__device__ __forceinline__ float4* task_vec(float4* ring, uint32_t cap, uint32_t slot, int k) {  // plane A (k = 0) or B (1)
+    return ring + static_cast<size_t>(k) * cap + slot;
+}
+__device__ __forceinline__ float2* task_tail(float4* ring, uint32_t cap, uint32_t slot) {  // plane C
+    return reinterpret_cast<float2*>(ring + 2 * static_cast<size_t>(cap)) + slot;
+}
+#else  // records of 3 float4 (plane C's float2 in the third), slot after slot
+__device__ __forceinline__ float4* task_ring(const DevFrame& fr) {
+    const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x * 4 + (threadIdx.x >> 6))));
+    return fr.tasks + static_cast<size_t>(wave) * fr.task_cap * (kTaskBytes / 16);
+}
+__device__ __forceinline__ float4* task_vec(float4* ring, uint32_t, uint32_t slot, int k) {
+    return ring + 3 * static_cast<size_t>(slot) + k;
+}
+__device__ __forceinline__ float2* task_tail(float4* ring, uint32_t, uint32_t slot) {
+    return reinterpret_cast<float2*>(ring + 3 * static_cast<size_t>(slot) + 2);
+}
+#endif
 // Called by the lanes that push (their exec mask is the set): true if this lane's
 // task went into the ring (false: the ring is full; the caller traces it itself).
-#ifndef BDPT_HELP_SOA
-#define BDPT_HELP_SOA 1  // the ring as three planes of 16-byte vectors (consecutive slots' pushes and claims coalesce)
-#endif
-// float4 k (0..2) of ring slot `slot`
-__device__ __forceinline__ float4* task_vec(float4* ring, uint32_t cap, uint32_t slot, int k) {
-    return BDPT_HELP_SOA ? ring + static_cast<size_t>(k) * cap + slot : ring + 3 * static_cast<size_t>(slot) + k;
-}
-__device__ __forceinline__ bool task_push(const LaneCold& mine, const DevFrame& fr, const Ray& r, bool nocull, f3 c,
+// start, end: the arguments of the task's shadow_ray (a splat's start is the camera).
+__device__ __forceinline__ bool task_push(const LaneCold& mine, const DevFrame& fr, f3 start, f3 end, bool nocull, f3 c,
                                           int pixel, bool splat, Counts& cnt) {
     const TaskCtl ctl = task_ctl(mine);
     const uint64_t m = __ballot(true);
@@ -386,16 +409,21 @@ __device__ __forceinline__ bool task_push(const LaneCold& mine, const DevFrame& 
     if (rank >= k) return false;
     float4* const ring = task_ring(fr);
     const uint32_t slot = (tail + rank) & (fr.task_cap - 1);
-    // (o, max_t) (d, near cull) (contribution, pixel | splat bit)
-    gst4(task_vec(ring, fr.task_cap, slot, 0), make_float4(r.o.x, r.o.y, r.o.z, r.max_t));
-    gst4(task_vec(ring, fr.task_cap, slot, 1), make_float4(r.d.x, r.d.y, r.d.z, nocull ? kNoCullNear : kCullNear));
-    gst4(task_vec(ring, fr.task_cap, slot, 2),
-         make_float4(c.x, c.y, c.z, __uint_as_float(static_cast<uint32_t>(pixel) | (splat ? kTaskSplat : 0u))));
+    const float meta =
+        __uint_as_float(static_cast<uint32_t>(pixel) | (splat ? kTaskSplat : 0u) | (nocull ? kTaskNoCull : 0u));
+    if (splat) {
+        gst4(task_vec(ring, fr.task_cap, slot, 0), make_float4(end.x, end.y, end.z, meta));
+        gst4(task_vec(ring, fr.task_cap, slot, 1), make_float4(c.x, c.y, c.z, 0.f));
+    } else {
+        gst4(task_vec(ring, fr.task_cap, slot, 0), make_float4(start.x, start.y, start.z, meta));
+        gst4(task_vec(ring, fr.task_cap, slot, 1), make_float4(end.x, end.y, end.z, c.x));
+        gst2(task_tail(ring, fr.task_cap, slot), make_float2(c.y, c.z));
+    }
     return true;
 }
 #else
 constexpr int kResShaded = -2;
-__device__ __forceinline__ bool task_push(const LaneCold&, const DevFrame&, const Ray&, bool, f3, int, bool, Counts&) {
+__device__ __forceinline__ bool task_push(const LaneCold&, const DevFrame&, f3, f3, bool, f3, int, bool, Counts&) {
     return false;
 }
 #endif
@@ -556,11 +584,11 @@ __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
         const float mis = rcp_w(lightWeight + 1.f + 0.f); \
         const f3 pend_ = (fr.strategy == 0) ? rad * mis : rad; \
         const int px_ = yp * fr.W + xp; \
-        const Ray sr_ = shadow_ray(cam_o, L.h.p); \
-        if (kTasks && task_push(L.c, fr, sr_, false, pend_, px_, true, cnt)) break;  /* a helper walks it (act: A_LIGHT_CONTINUE) */ \
+        /* a helper walks it and forms its ray from the camera and L.h.p (act: A_LIGHT_CONTINUE) */ \
+        if (kTasks && task_push(L.c, fr, cam_o, L.h.p, false, pend_, px_, true, cnt)) break; \
         L.c.pend = pend_; \
         L.c.pend_px = px_; \
-        L.ray = sr_; \
+        L.ray = shadow_ray(cam_o, L.h.p); \
         L.state = ST_SPLAT; \
         act = A_ISSUED; \
     } BDPT_END;
@@ -767,7 +795,7 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
         const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
         const f3 pend = (fr.strategy == 0) ? Li * mis : Li;
         const Ray sr = shadow_ray(L.h.p, e_p);
-        if (kTasks && task_push(L.c, fr, sr, vertex_nocull(L, sr.d), pend * fr.inv_spp, L.c.pixel, false, cnt))
+        if (kTasks && task_push(L.c, fr, L.h.p, e_p, vertex_nocull(L, sr.d), pend * fr.inv_spp, L.c.pixel, false, cnt))
             break;  // a helper walks it (act: A_CONN)
         L.c.pend = pend;
         L.ray = sr;
@@ -824,7 +852,7 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
             const float eyeWeight = eyePathRev_a * (L.c.vcm + eyePrevRev * L.c.vc);
             const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
             const Ray sr = shadow_ray(L.h.p, V.p);
-            if (kTasks && task_push(L.c, fr, sr, vertex_nocull(L, sr.d), (Li * mis) * fr.inv_spp, L.c.pixel, false, cnt)) {
+            if (kTasks && task_push(L.c, fr, L.h.p, V.p, vertex_nocull(L, sr.d), (Li * mis) * fr.inv_spp, L.c.pixel, false, cnt)) {
                 L.c.ci++;  // a helper walks it; the next light vertex now
                 continue;
             }
@@ -946,7 +974,7 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
 #if BDPT_GRAZE_IN_DIST
 #error "conn_batch: BDPT_GRAZE_IN_DIST keeps the threshold in Hit::dist"
 #endif
-        task_push(L.c, fr, sr, graze_exempt(sr.d, hn, hshape), (Li * mis) * fr.inv_spp, oc.pixel, false, cnt);
+        task_push(L.c, fr, hp, V.p, graze_exempt(sr.d, hn, hshape), (Li * mis) * fr.inv_spp, oc.pixel, false, cnt);
     }
     if (k > 0) L.c.ci = L.c.nl;
 }
