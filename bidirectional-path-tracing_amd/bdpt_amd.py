@@ -46,7 +46,10 @@ COUNTER_NAMES = ["closest_rays", "shadow_rays", "interior_visits", "tri_tests", 
 
 
 class BdptError(RuntimeError):
-    pass
+    code = 0  # the BDPT_ERR_* status (set by _check)
+
+
+ERR_INVALID, ERR_IO, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4, -5
 
 
 class _Camera(ctypes.Structure):
@@ -137,6 +140,17 @@ class _SceneDesc(ctypes.Structure):  # bdpt_scene_desc
                 ("bvh", ctypes.c_void_p), ("bvh_order", ctypes.c_void_p)]
 
 
+class _TextureDesc(ctypes.Structure):  # bdpt_texture_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("rgb", ctypes.c_void_p)]
+
+
+class _SceneTextures(ctypes.Structure):  # bdpt_scene_textures
+    _fields_ = [("ntextures", ctypes.c_int32), ("texture", ctypes.c_void_p), ("diffuse_tex", ctypes.c_void_p),
+                ("specular_tex", ctypes.c_void_p), ("texcoords", ctypes.c_void_p)]
+
+
+TEXTURE_ARRAYS = ("tex_tab", "tri_st", "mat_tex", "tex_dims")  # bdpt_scene_export_textures ids 0..3
+
 # BsdfKind (bdpt_types.h) -> the MTL illum that selects it (renderer.cpp:258-271)
 KIND_ILLUM = {0: 5, 1: 7, 2: 3, 3: 6, 4: 8, 5: 2}
 LAYOUT_ARRAYS = ("tri", "shade", "nodes", "wnodes", "wtri", "lbox", "bsdfs", "emitters", "emit_tri", "emit_cdf",
@@ -159,6 +173,11 @@ class SceneDesc:
     emitters: list          # dicts: shape area radiance cdf
     bvh: np.ndarray         # structured (bmin f4[3], bmax f4[3], start u4, nprims u4, right_offset u4)
     bvh_order: np.ndarray   # int32 (n,)
+    # bitmap textures (bdpt_scene_textures; all None = an untextured scene, bdpt_scene_create)
+    textures: list | None = None         # float32 (h, w, 3) arrays: Tex::cs, expanded and flipped
+    diffuse_tex: np.ndarray | None = None   # int32 (materials,): texture of the diffuse map, -1 none
+    specular_tex: np.ndarray | None = None  # int32 (materials,)
+    texcoords: np.ndarray | None = None     # float32 (n, 6): st0 st1 st2 per triangle
 
 
 BVH_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("start", "<u4"), ("nprims", "<u4"),
@@ -178,7 +197,7 @@ class _Stats(ctypes.Structure):
 # Sources that make up the frame kernels' code objects: their hash stamps the
 # profiles (PMC passes) so bench.py only reuses a measurement of the same kernel.
 KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
-                  "csrc/bdpt_types.h", "Makefile")
+                  "csrc/powf_restated.inc", "csrc/bdpt_types.h", "Makefile")
 
 
 def kernel_build_hash() -> str:
@@ -223,6 +242,9 @@ def lib():
         L.bdpt_intersect_from.argtypes = [vp, ctypes.c_int64, vp, vp, vp, i32, vp]
         L.bdpt_scene_create.argtypes = [ctypes.POINTER(_SceneDesc), ctypes.POINTER(vp)]
         L.bdpt_scene_export_layout.argtypes = [vp, i32, vp, ctypes.POINTER(ctypes.c_int64)]
+        L.bdpt_scene_create_textured.argtypes = [ctypes.POINTER(_SceneDesc), ctypes.POINTER(_SceneTextures),
+                                                 ctypes.POINTER(vp)]
+        L.bdpt_scene_export_textures.argtypes = [vp, i32, vp, ctypes.POINTER(ctypes.c_int64), vp]
         L.bdpt_camera_constants.argtypes = [ctypes.POINTER(_Camera), i32, i32, f32p]
         L.bdpt_device_count.argtypes = [ctypes.POINTER(i32)]
         L.bdpt_ctx_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
@@ -273,7 +295,9 @@ def lib():
 
 def _check(rc: int) -> None:
     if rc != 0:
-        raise BdptError(f"bdpt error {rc}: {lib().bdpt_last_error().decode()}")
+        e = BdptError(f"bdpt error {rc}: {lib().bdpt_last_error().decode()}")
+        e.code = rc
+        raise e
 
 
 def device_count() -> int:
@@ -506,7 +530,19 @@ class Scene:
         c.bvh_nodes, c.bvh = int(bvh.size), bvh.ctypes.data
         c.bvh_order = arr(d.bvh_order, np.int32)
         h = ctypes.c_void_p()
-        _check(lib().bdpt_scene_create(ctypes.byref(c), ctypes.byref(h)))
+        if d.textures is not None:  # bdpt_scene_create_textured
+            texs = (_TextureDesc * max(len(d.textures), 1))()
+            for k, t in enumerate(d.textures):
+                t = np.asarray(t, np.float32)
+                texs[k].height, texs[k].width = int(t.shape[0]), int(t.shape[1])
+                texs[k].rgb = arr(t, np.float32)
+            tx = _SceneTextures()
+            tx.ntextures, tx.texture = len(d.textures), ctypes.addressof(texs)
+            tx.diffuse_tex, tx.specular_tex = arr(d.diffuse_tex, np.int32), arr(d.specular_tex, np.int32)
+            tx.texcoords = arr(d.texcoords, np.float32) if d.texcoords is not None else None
+            _check(lib().bdpt_scene_create_textured(ctypes.byref(c), ctypes.byref(tx), ctypes.byref(h)))
+        else:
+            _check(lib().bdpt_scene_create(ctypes.byref(c), ctypes.byref(h)))
         self = cls.__new__(cls)
         self._h, self.path = h, None
         return self
@@ -519,6 +555,27 @@ class Scene:
         buf = ctypes.create_string_buffer(max(n.value, 1))
         _check(lib().bdpt_scene_export_layout(self._h, i, buf, ctypes.byref(n)))
         return buf.raw[:n.value]
+
+    def export_textures(self, array) -> bytes:
+        """bdpt_scene_export_textures: one of the texture arrays (TEXTURE_ARRAYS) as bytes."""
+        i = TEXTURE_ARRAYS.index(array) if isinstance(array, str) else int(array)
+        n = ctypes.c_int64(0)
+        _check(lib().bdpt_scene_export_textures(self._h, i, None, ctypes.byref(n), None))
+        buf = ctypes.create_string_buffer(max(n.value, 1))
+        _check(lib().bdpt_scene_export_textures(self._h, i, buf, ctypes.byref(n), None))
+        return buf.raw[:n.value]
+
+    def texture_info(self) -> dict:
+        """Bitmap textures of the scene: their count, texels and HBM bytes."""
+        n, info = ctypes.c_int64(0), (ctypes.c_int64 * 3)()
+        _check(lib().bdpt_scene_export_textures(self._h, 0, None, ctypes.byref(n), info))
+        return dict(textures=info[0], texels=info[1], device_bytes=info[2])
+
+    def textures(self) -> list:
+        """The maps as float32 (h, w, 3) arrays (Tex::cs: gamma-expanded, flipped)."""
+        dims = np.frombuffer(self.export_textures("tex_dims"), np.int32).reshape(-1, 3)
+        tab = np.frombuffer(self.export_textures("tex_tab"), np.float32).reshape(-1, 4)
+        return [tab[at:at + w * h, :3].reshape(h, w, 3).copy() for w, h, at in dims]
 
     def to_desc(self) -> SceneDesc:
         """The descriptor of this scene, rebuilt from its exports (BVH leaf order back
@@ -539,9 +596,17 @@ class Scene:
         bvh = np.zeros(nf.shape[0], BVH_NODE_DTYPE)
         bvh["bmin"], bvh["bmax"] = nf[:, :3], nf[:, 3:]
         bvh["start"], bvh["nprims"], bvh["right_offset"] = nu[:, 0], nu[:, 1], nu[:, 2]
-        return SceneDesc(positions=tf[perm, :9], normals=tf[perm, 9:], tri_shape=ti[perm, 0], tri_prim=ti[perm, 1],
-                         tri_mat=ti[perm, 2], shapes=inf["shapes"], materials=mats, emitters=ems, bvh=bvh,
-                         bvh_order=order.astype(np.int32))
+        d = SceneDesc(positions=tf[perm, :9], normals=tf[perm, 9:], tri_shape=ti[perm, 0], tri_prim=ti[perm, 1],
+                      tri_mat=ti[perm, 2], shapes=inf["shapes"], materials=mats, emitters=ems, bvh=bvh,
+                      bvh_order=order.astype(np.int32))
+        if self.texture_info()["textures"]:
+            mt = np.frombuffer(self.export_textures("mat_tex"), np.int32).reshape(-1, 2)
+            for m, (kd, ks) in zip(mats, mt):
+                m["has_texture"] = int(kd >= 0 or ks >= 0)
+            d.textures = self.textures()
+            d.diffuse_tex, d.specular_tex = mt[:, 0].copy(), mt[:, 1].copy()
+            d.texcoords = np.frombuffer(self.export_textures("tri_st"), np.float32).reshape(-1, 6)[perm]
+        return d
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:

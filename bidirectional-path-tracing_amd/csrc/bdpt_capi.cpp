@@ -72,6 +72,15 @@ hipError_t launch_frame_split(const dev::DevScene& sc, const dev::DevFrame& fr, 
                               uint2* gstack, uint32_t nslots, unsigned long long* work, unsigned long long* counters,
                               int grid, hipStream_t stream, void* dparams);
 int frame_kernel_blocks_per_cu_split(size_t dyn_lds);
+// bdpt_kernels_tex.hip / sample_state_tex.hip: the megakernel and the single-sample kernel for
+// scenes with bitmap textures (BDPT_TEXTURED: texel lookup at every closest hit, 80-byte light vertices)
+hipError_t launch_frame_tex(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf, uint2* gstack,
+                            uint32_t nslots, unsigned long long* work, unsigned long long* counters, int grid,
+                            hipStream_t stream, void* dparams);
+int frame_kernel_blocks_per_cu_tex(size_t dyn_lds);
+int light_vertex_fields_tex();
+hipError_t launch_sample_tex(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf,
+                             uint2* gstack, const dev::Ray& ray, float* out, hipStream_t stream);
 size_t pt_params_bytes();
 int pt_blocks_per_cu(size_t dyn_lds);
 hipError_t launch_pt(const dev::DevScene& sc, const dev::DevFrame& fr, const int32_t settings[8], float* fb,
@@ -226,6 +235,8 @@ struct bdpt_ctx {
     uint32_t* park = nullptr;     // Russian roulette: continuation records + parked-slot list (DevFrame::park)
     float4* tasks = nullptr;      // per-wave shadow-ray task rings (DevFrame::tasks; read by BDPT_HELP builds)
     uint32_t task_cap = 0;        // their capacity (tasks per wave, a power of two)
+    bool textured = false;        // the scene has bitmap textures: bdpt_render runs bdpt_kernels_tex.hip
+    std::vector<uint8_t> mat_textured;  // per material: it reads a map (bdpt_bsdf_* carry no hit to look one up)
     bool has_glass = false;       // a GlassBSDF material: Russian-roulette renders run bdpt_kernels_rrc.hip
     int32_t* row_order = nullptr;  // bdpt_set_row_order (device copy; DevFrame::row_order)
     int32_t row_order_n = 0;       // its row count (0: top to bottom)
@@ -274,12 +285,15 @@ static int end_use(bdpt_ctx* c, hipStream_t st) {
 // holds) with (u.x - 0) / (1 - 0) == u.x. The kernels run it as diffuse, so a
 // wave whose lanes shade both kinds runs one branch instead of two.
 // BDPT_KEEP_MIXTURE=1 keeps the record as loaded (the A/B of DESIGN.md).
-static std::vector<BsdfRecord> device_bsdfs(const std::vector<BsdfRecord>& in) {
+// A material with a specular map keeps its kind: its Ks is the texel's, not the record's.
+static std::vector<BsdfRecord> device_bsdfs(const std::vector<BsdfRecord>& in, const std::vector<int32_t>& mat_tex) {
     std::vector<BsdfRecord> out = in;
     const char* keep = std::getenv("BDPT_KEEP_MIXTURE");
     if (keep && *keep == '1') return out;
-    for (BsdfRecord& b : out) {
-        const bool ks0 = b.ks[0] == 0.f && b.ks[1] == 0.f && b.ks[2] == 0.f;
+    for (size_t m = 0; m < out.size(); m++) {
+        BsdfRecord& b = out[m];
+        const bool ks_map = 2 * m + 1 < mat_tex.size() && mat_tex[2 * m + 1] >= 0;
+        const bool ks0 = b.ks[0] == 0.f && b.ks[1] == 0.f && b.ks[2] == 0.f && !ks_map;
         if (b.kind == BSDF_MIXTURE && ks0 && b.scale == 1.f && b.specw == 0.f && std::isfinite(b.exponent) &&
             b.exponent >= 0.f)
             b.kind = BSDF_DIFFUSE;  // type keeps the reference's flags (only its delta bits are read)
@@ -331,6 +345,11 @@ static std::vector<float4_t> device_shade(const DeviceLayout& L) {
     for (size_t i = 0; i < ntri; i++) {
         for (int q = 0; q < 5; q++) out[kShadeStride * i + q] = L.shade[5 * i + q];
         if (kShadeStride > kShadeV0) out[kShadeStride * i + kShadeV0] = L.tri[3 * i];
+        if (L.textured() && kShadeStride >= kShadeSt + 2) {  // the corners' texture coordinates, in the same line
+            const float* st = &L.tri_st[6 * i];
+            out[kShadeStride * i + kShadeSt] = {st[0], st[1], st[2], st[3]};
+            out[kShadeStride * i + kShadeSt + 1] = {st[4], st[5], 0.f, 0.f};
+        }
         const float4_t* s = &L.shade[5 * i];
         const float v0[3] = {L.tri[3 * i].x, L.tri[3 * i].y, L.tri[3 * i].z};
         const float v1[3] = {s[3].x, s[3].y, s[3].z}, v2[3] = {s[4].x, s[4].y, s[4].z};
@@ -367,19 +386,49 @@ int bdpt_scene_load_obj(const char* obj_path, bdpt_scene** out) {
     if (!obj_path || !out) return fail(BDPT_ERR_INVALID, "null argument");
     auto s = std::make_unique<bdpt_scene>();
     std::string err;
-    if (!load_obj_scene(obj_path, s->host, err)) return fail(BDPT_ERR_IO, err);
+    int code = BDPT_ERR_IO;
+    if (!load_obj_scene(obj_path, s->host, err, &code)) return fail(code, err);
+    if (!build_device_layout(s->host, s->layout, err)) return fail(BDPT_ERR_INVALID, err);
+    *out = s.release();
+    return BDPT_OK;
+}
+
+int bdpt_scene_create_textured(const bdpt_scene_desc* desc, const bdpt_scene_textures* textures, bdpt_scene** out) {
+    if (!desc || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    auto s = std::make_unique<bdpt_scene>();
+    std::string err;
+    if (!load_desc_scene(*desc, textures, s->host, err)) return fail(BDPT_ERR_INVALID, err);
     if (!build_device_layout(s->host, s->layout, err)) return fail(BDPT_ERR_INVALID, err);
     *out = s.release();
     return BDPT_OK;
 }
 
 int bdpt_scene_create(const bdpt_scene_desc* desc, bdpt_scene** out) {
-    if (!desc || !out) return fail(BDPT_ERR_INVALID, "null argument");
-    auto s = std::make_unique<bdpt_scene>();
-    std::string err;
-    if (!load_desc_scene(*desc, s->host, err)) return fail(BDPT_ERR_INVALID, err);
-    if (!build_device_layout(s->host, s->layout, err)) return fail(BDPT_ERR_INVALID, err);
-    *out = s.release();
+    return bdpt_scene_create_textured(desc, nullptr, out);
+}
+
+int bdpt_scene_export_textures(const bdpt_scene* s, int32_t array, void* dst, int64_t* bytes, int64_t info[3]) {
+    if (!s || !bytes) return fail(BDPT_ERR_INVALID, "null argument");
+    const DeviceLayout& L = s->layout;
+    const void* src = nullptr;
+    size_t n = 0;
+    switch (array) {
+        case 0: src = L.tex_tab.data(), n = L.tex_tab.size() * 16; break;
+        case 1: src = L.tri_st.data(), n = L.tri_st.size() * 4; break;
+        case 2: src = L.mat_tex.data(), n = L.mat_tex.size() * 4; break;
+        case 3: src = L.tex_dims.data(), n = L.tex_dims.size() * 4; break;
+        default: return fail(BDPT_ERR_INVALID, "unknown texture array");
+    }
+    if (dst) {
+        if (*bytes < static_cast<int64_t>(n)) return fail(BDPT_ERR_INVALID, "destination too small");
+        if (n) std::memcpy(dst, src, n);
+    }
+    *bytes = static_cast<int64_t>(n);
+    if (info) {
+        info[0] = static_cast<int64_t>(L.tex_dims.size() / 3);
+        info[1] = L.textured() ? static_cast<int64_t>(L.tex_tab.size() - 2 * L.bsdfs.size()) : 0;
+        info[2] = static_cast<int64_t>(L.tex_tab.size() * 16 + L.tri_st.size() * 4);
+    }
     return BDPT_OK;
 }
 
@@ -399,7 +448,7 @@ int bdpt_scene_export_layout(const bdpt_scene* s, int32_t array, void* dst, int6
         case 3: src = L.wnodes.data(), n = L.wnodes.size() * 16; break;
         case 4: src = L.wtri.data(), n = L.wtri.size() * 16; break;
         case 5: src = L.lbox.data(), n = L.lbox.size() * 16; break;
-        case 6: tmpb = device_bsdfs(L.bsdfs), src = tmpb.data(), n = tmpb.size() * sizeof(BsdfRecord); break;
+        case 6: tmpb = device_bsdfs(L.bsdfs, L.mat_tex), src = tmpb.data(), n = tmpb.size() * sizeof(BsdfRecord); break;
         case 7: src = L.emitters.data(), n = L.emitters.size() * sizeof(EmitterRecord); break;
         case 8: tmp4 = device_emit_tri(L), src = tmp4.data(), n = tmp4.size() * 16; break;
         case 9: src = L.emit_cdf.data(), n = L.emit_cdf.size() * 4; break;
@@ -577,7 +626,7 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     if ((rc = upload(c.get(), L.lbox.data(), L.lbox.size() * 16, &p))) return rc;
     c->sc.lbox = static_cast<const float4*>(p);
     {
-        const std::vector<BsdfRecord> dev_bsdfs = device_bsdfs(L.bsdfs);
+        const std::vector<BsdfRecord> dev_bsdfs = device_bsdfs(L.bsdfs, L.mat_tex);
         if ((rc = upload(c.get(), dev_bsdfs.data(), dev_bsdfs.size() * sizeof(BsdfRecord), &p))) return rc;
         for (const BsdfRecord& b : dev_bsdfs) c->has_glass = c->has_glass || b.kind == BSDF_GLASS;
     }
@@ -593,6 +642,15 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     c->sc.emit_cdf = static_cast<const float*>(p);
     if ((rc = upload(c.get(), L.shape_emitter.data(), L.shape_emitter.size() * 4, &p))) return rc;
     c->sc.shape_emitter = static_cast<const int32_t*>(p);
+    c->sc.tex_tab = nullptr;
+    if (L.textured()) {  // map records + texel pool; the texture coordinates ride in the shade records
+        if (kShadeStride < kShadeSt + 2)
+            return fail(BDPT_ERR_UNSUPPORTED, "bitmap textures need the wide shade records (BDPT_SHADE_WIDE)");
+        if ((rc = upload(c.get(), L.tex_tab.data(), L.tex_tab.size() * 16, &p))) return rc;
+        c->sc.tex_tab = static_cast<const float4*>(p);
+        c->textured = true;
+        for (size_t m = 0; m < L.bsdfs.size(); m++) c->mat_textured.push_back(L.mat_tex[2 * m] >= 0 || L.mat_tex[2 * m + 1] >= 0);
+    }
     c->sc.root_link = L.root_link;
     c->sc.node_slack = 1u;  // per render: node_slack_needed
     c->tri_tree = L.tri_tree;
@@ -732,7 +790,8 @@ static dev::DevFrame make_frame(const bdpt_frame_params* p) {
 }
 
 static int ensure_lv(bdpt_ctx* c, int lv_max, uint32_t nslots) {
-    const size_t need = static_cast<size_t>(std::max(lv_max, 1)) * light_vertex_fields() * nslots;
+    const int fields = c->textured ? light_vertex_fields_tex() : light_vertex_fields();
+    const size_t need = static_cast<size_t>(std::max(lv_max, 1)) * fields * nslots;
     if (need > c->lv_floats) {
         if (c->lv) HIP_TRY(hipFree(c->lv));
         c->lv = nullptr;
@@ -748,6 +807,21 @@ static int ensure_lv(bdpt_ctx* c, int lv_max, uint32_t nslots) {
 static int ensure_tasks(bdpt_ctx* c) {
     if (!c->tasks)
         HIP_TRY(hipMalloc(&c->tasks, static_cast<size_t>(dev::kTaskBytes) * c->task_cap * (c->nslots / 64)));
+    return BDPT_OK;
+}
+
+// What a scene with bitmap textures does not run: never a wrong image.
+static int textured_unsupported(const bdpt_ctx* c, const char* what) {
+    if (!c->textured) return BDPT_OK;
+    return fail(BDPT_ERR_UNSUPPORTED, std::string("a scene with bitmap textures (map_Kd / map_Ks) does not run ") + what);
+}
+static int textured_frame_check(const bdpt_ctx* c, const bdpt_frame_params* p) {
+    if (!c->textured) return BDPT_OK;
+    if (p->russian_roulette != BDPT_RR_NONE)
+        return textured_unsupported(c, "with russian_roulette = BDPT_RR_LUMINANCE (texture + Russian roulette)");
+    if (p->rr_depth > kLazyRrDepth) return textured_unsupported(c, "with rr_depth > 28 (texture + deep rr_depth)");
+    if (c->sc.lds_bsdf_off == dev::kNoLds)
+        return textured_unsupported(c, "with the BSDF records in HBM (texture + too many materials for the LDS table)");
     return BDPT_OK;
 }
 
@@ -796,6 +870,7 @@ int bdpt_render(bdpt_ctx* c, const bdpt_frame_params* p, float* fb, void* hip_st
     if (!c || !fb) return fail(BDPT_ERR_INVALID, "null argument");
     int rc = check_params(p);
     if (rc) return rc;
+    if ((rc = textured_frame_check(c, p))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     dev::DevFrame fr = make_frame(p);
@@ -865,7 +940,13 @@ int bdpt_render(bdpt_ctx* c, const bdpt_frame_params* p, float* fb, void* hip_st
     HIP_TRY(hipEventRecord(c->ev0, st));
     int64_t launches = 0;
     if (fr.total_samples > 0) {
-        if (rr) {  // never more resident blocks than the slots allocated
+        if (c->textured) {  // (no Russian roulette, rr_depth <= 28, LDS records: textured_frame_check)
+            const int grid = std::min(c->grid, c->cus * frame_kernel_blocks_per_cu_tex(
+                                                           4 * static_cast<size_t>(c->sc.lds_words)));
+            HIP_TRY(launch_frame_tex(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, grid, st,
+                                     c->dparams));
+            c->last_kernel = "bdpt_frame_kernel_tex";
+        } else if (rr) {  // never more resident blocks than the slots allocated
             // scenes with a dielectric can trap a subpath in a chain of delta bounces: the
             // build that runs a lone chain inline (bdpt_kernels_rrc.hip); BDPT_RR_CHAIN=0/1 forces
             const char* ce = std::getenv("BDPT_RR_CHAIN");
@@ -983,6 +1064,7 @@ static dev::DevScene pt_scene(const bdpt_ctx* c, const bdpt_frame_params* p) {
 int bdpt_render_path(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_params* path, float* fb,
                      void* hip_stream) {
     if (!c || !fb || !path) return fail(BDPT_ERR_INVALID, "null argument");
+    if (int trc = textured_unsupported(c, "the path integrator (texture + bdpt_render_path)")) return trc;
     if (!p) return fail(BDPT_ERR_INVALID, "null params");
     if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(BDPT_ERR_INVALID, "width/height/spp must be > 0");
     if (static_cast<int64_t>(p->width) * p->height >= (1ll << 31))
@@ -1040,6 +1122,7 @@ int bdpt_render_path_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_pa
 int bdpt_render_direct(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_direct_params* d, float* fb,
                        void* hip_stream) {
     if (!c || !fb || !d) return fail(BDPT_ERR_INVALID, "null argument");
+    if (int trc = textured_unsupported(c, "the direct integrator (texture + bdpt_render_direct)")) return trc;
     if (!p) return fail(BDPT_ERR_INVALID, "null params");
     if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(BDPT_ERR_INVALID, "width/height/spp must be > 0");
     if (static_cast<int64_t>(p->width) * p->height >= (1ll << 31))
@@ -1109,6 +1192,8 @@ static int render_pt_sample(bdpt_ctx* c, const bdpt_frame_params* p, const int32
                             const float ray[8], uint32_t* state, float Li[3], uint32_t* taken = nullptr) {
     if (!c || !p || !ray || !Li) return fail(BDPT_ERR_INVALID, "null argument");
     int rc;
+    if ((rc = textured_unsupported(c, "the path / direct integrators (texture + bdpt_render_path / _direct sample)")))
+        return rc;
     if ((rc = check_mt_state(state))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = ensure_pt(c, levels))) return rc;
@@ -1352,6 +1437,7 @@ static int render_bdpt_sample(bdpt_ctx* c, const bdpt_frame_params* p, const flo
     int rc = check_params(p);
     if (rc) return rc;
     if ((rc = check_mt_state(state))) return rc;
+    if ((rc = textured_frame_check(c, p))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     // the sample kernel's one lane uses lane slot 0 of the light-vertex store
     if ((rc = ensure_lv(c, make_frame(p).lv_max, 1))) return rc;
@@ -1376,7 +1462,8 @@ static int render_bdpt_sample(bdpt_ctx* c, const bdpt_frame_params* p, const flo
                                c->stream));
         HIP_TRY(hipMemcpyAsync(c->splat_list, hdr, sizeof(hdr), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemsetAsync(c->capped, 0, sizeof(uint32_t), c->stream));
-        HIP_TRY(launch_sample(sc, fr, c->splat_list, c->lv, c->gstack, r, c->sample_out, c->stream));
+        HIP_TRY((c->textured ? launch_sample_tex : launch_sample)(sc, fr, c->splat_list, c->lv, c->gstack, r,
+                                                                  c->sample_out, c->stream));
         list.assign(4 * (static_cast<size_t>(c->splat_cap) + 1), 0.f);
         HIP_TRY(hipMemcpyAsync(out, c->sample_out, sizeof(out), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(list.data(), c->splat_list, list.size() * sizeof(float), hipMemcpyDeviceToHost,
@@ -1470,6 +1557,11 @@ static int bsdf_kat(bdpt_ctx* c, int mode, int64_t n, const int32_t* mat, const 
     if (!c || n < 0 || (n > 0 && (!mat || !wo || !x || !out))) return fail(BDPT_ERR_INVALID, "bad argument");
     for (int64_t i = 0; i < n; i++)
         if (mat[i] < 0 || mat[i] >= c->sc.nbsdf) return fail(BDPT_ERR_INVALID, "material index out of range");
+    for (int64_t i = 0; c->textured && i < n; i++)
+        if (c->mat_textured[mat[i]])
+            return fail(BDPT_ERR_UNSUPPORTED, "bdpt_bsdf_eval / pdf / sample of material " + std::to_string(mat[i]) +
+                                                  ": it reads a bitmap texture and these calls carry no hit (texture + "
+                                                  "bdpt_bsdf_*)");
     if (n == 0) return BDPT_OK;
     HIP_TRY(hipSetDevice(c->device));
     int rc;

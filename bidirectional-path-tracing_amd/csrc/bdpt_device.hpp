@@ -97,6 +97,10 @@ struct DevScene {
     float near_lo[3], near_hi[3];
     uint32_t q_ok;  // qnodes present: the BDPT_QNODES kernels walk the 4-wide tree (else the binary one)
     uint32_t gdepth;  // traversal-stack overflow entries per lane slot (beyond the LDS ones)
+    // Bitmap textures (null without; read by the BDPT_TEXTURED builds only): per material two
+    // int4 records — diffuse, specular map: (first texel's index in this table, w, h, 0), index
+    // -1 = none — then the pool of float4 texels (rgb, 0) of every map
+    const float4* __restrict__ tex_tab;
 };
 constexpr uint32_t kNoLds = 0xffffffffu;
 constexpr uint32_t kLdsHdr = 4;  // LDS header words: mt_ring (2 words), mt_ring_stride, the block's first lane slot
@@ -221,11 +225,19 @@ struct Ray {
 };
 
 // Hit record = the parts of SurfaceInteraction (core.h:173-180) the path reads.
+#ifndef BDPT_TEXTURED
+#define BDPT_TEXTURED 0  // 1: the builds for scenes with bitmap textures (bdpt_kernels_tex.hip)
+#endif
 struct Hit {
     f3 p, wo;
     f3 n;  // frameNs.n; s and t are recomputed from it (Frame(n) is a pure function of n)
     float dist;
     int mat, shape;
+#if BDPT_TEXTURED
+    // BitmapTexture3f::eval's texel (core.h:569-587) of the material's diffuse / specular map
+    // at this hit, as an index into DevScene::tex_tab; -1: the material record's constant
+    int tkd, tks;
+#endif
 };
 
 // ------------------------------------------------------------------ sampler
@@ -1885,6 +1897,15 @@ __device__ __forceinline__ bool coop_closest_groups(const TravScene& sc, const R
     return ok;
 }
 
+#if BDPT_TEXTURED
+// w * y + x of core.h:582-584 (int(float) as x86's cvttss2si, clamp to [0, size - 1]).
+__device__ __forceinline__ int texel_of(float sx, float sy, int tw, int th) {
+    int x = x86_trunc_i32(sx * static_cast<float>(tw)), y = x86_trunc_i32(sy * static_cast<float>(th));
+    x = x < 0 ? 0 : (x > tw - 1 ? tw - 1 : x);
+    y = y < 0 ? 0 : (y > th - 1 ? th - 1 : y);
+    return tw * y + x;
+}
+#endif
 // AcceleratorBVH::intersect's shading of a closest hit (accel.h:133-166).
 __device__ __forceinline__ void shade_hit(const DevScene& sc, int i, float u, float v, float t, f3 dir, Hit& h) {
     const float4* sh = sc.shade + kShadeStride * static_cast<size_t>(i);
@@ -1900,6 +1921,23 @@ __device__ __forceinline__ void shade_hit(const DevScene& sc, int i, float u, fl
     h.dist = t;
     h.mat = __float_as_int(s0.w);
     h.shape = __float_as_int(s1.w);
+#if BDPT_TEXTURED
+    // BitmapTexture3f::eval (core.h:569-587): st = barycentric(st0, st1, st2, u, v) + 1
+    // (math.h:20-22), st -= floor(st), x = clamp(int(st.x * w), 0, w - 1), likewise y,
+    // texel w * y + x; the hit's u, v and 1 - u - v are the ones the hit point uses.
+    h.tkd = h.tks = -1;
+    const float4 mk_ = gld4(sc.tex_tab + 2 * static_cast<size_t>(h.mat)), ms_ = gld4(sc.tex_tab + 2 * static_cast<size_t>(h.mat) + 1);
+    const int kd0 = __float_as_int(mk_.x), ks0 = __float_as_int(ms_.x);
+    if (kd0 >= 0 || ks0 >= 0) {
+        const float4 t0 = gld4(sh + kShadeSt), t1 = gld4(sh + kShadeSt + 1);
+        float sx = (t0.x * w + t0.z * u) + t1.x * v;
+        float sy = (t0.y * w + t0.w * u) + t1.y * v;
+        sx = sx + 1.f, sy = sy + 1.f;
+        sx = sx - __builtin_floorf(sx), sy = sy - __builtin_floorf(sy);
+        if (kd0 >= 0) h.tkd = kd0 + texel_of(sx, sy, __float_as_int(mk_.y), __float_as_int(mk_.z));
+        if (ks0 >= 0) h.tks = ks0 + texel_of(sx, sy, __float_as_int(ms_.y), __float_as_int(ms_.z));
+    }
+#endif
 }
 
 // The shadow ray of visibilityQuery (bdpt.h:498-505).
@@ -2161,6 +2199,28 @@ __device__ __forceinline__ f3 bsdf_sample(const BsdfRecord& b, f3 wo, F2 u, f3& 
 }
 
 __device__ __forceinline__ bool is_delta(const BsdfRecord& b) { return (b.type & kTypeDelta) != 0; }
+
+// The BSDF of a path vertex. Textured builds: a copy of the material's record with Kd / Ks
+// replaced by the vertex's texels (diffuse.h:40, mixture.h:66-70, phong.h:66-70 evaluate the
+// Texture<v3f> at the hit), fetched here, where eval / sample need them; a vertex carries
+// the two texel indices, not the reflectances.
+#if BDPT_TEXTURED
+__device__ __forceinline__ BsdfRecord bsdf_tex(const DevScene& sc, int mat, int tkd, int tks) {
+    BsdfRecord b = bsdf_of(sc, mat);
+    if (tkd >= 0) {
+        const float4 t = gld4(sc.tex_tab + tkd);
+        b.kd[0] = t.x, b.kd[1] = t.y, b.kd[2] = t.z;
+    }
+    if (tks >= 0) {
+        const float4 t = gld4(sc.tex_tab + tks);
+        b.ks[0] = t.x, b.ks[1] = t.y, b.ks[2] = t.z;
+    }
+    return b;
+}
+#define BDPT_VERTEX_BSDF(NAME, SC, MAT, TKD, TKS) const BsdfRecord NAME = bsdf_tex(SC, MAT, TKD, TKS)
+#else
+#define BDPT_VERTEX_BSDF(NAME, SC, MAT, TKD, TKS) const BsdfRecord& NAME = bsdf_of(SC, MAT)
+#endif
 
 // The direction v in the shading frame of normal n, for evaluating BSDF b:
 // DiffuseBSDF's eval and pdf read only the z component, dot(v, n) (to_local),

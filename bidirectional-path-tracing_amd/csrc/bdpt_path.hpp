@@ -15,7 +15,11 @@ namespace bdpt {
 namespace dev {
 
 
-constexpr int kLvFields = 16;  // p vcm n vc wo rr tp mat
+// Floats of a stored light vertex: p vcm n vc wo rr tp mat (64 B), and in the textured
+// builds a fifth float4 (tkd, tks, 0, 0): connectVertices evaluates the stored vertex's
+// BSDF again (bdpt.h:434-483), so its texels travel with it (80 B).
+constexpr int kLvQuads = BDPT_TEXTURED ? 5 : 4;
+constexpr int kLvFields = 4 * kLvQuads;
 constexpr uint32_t kFlagNoEyeAccum = 0x100u;  // single-sample API: Li is returned, not added
 // Safety bound on the queries of one sample: a legal sample issues at most D
 // light-walk rays, D camera splats, D eye-walk rays and, per eye vertex, one
@@ -62,11 +66,11 @@ struct LightStore {
     bool tid_rel = false;  // slot is the block's first; the lane adds threadIdx.x at each access (opaque_tid)
     __device__ __forceinline__ float4* at(int v) const {
         const uint32_t s = tid_rel ? slot + opaque_tid() : slot;
-        return base + (static_cast<size_t>(s) * maxv + static_cast<uint32_t>(v)) * 4;
+        return base + (static_cast<size_t>(s) * maxv + static_cast<uint32_t>(v)) * kLvQuads;
     }
     // vertex v of the lane threadIdx.x == tid (tid_rel stores only)
     __device__ __forceinline__ float4* at_tid(int v, uint32_t tid) const {
-        return base + (static_cast<size_t>(slot + tid) * maxv + static_cast<uint32_t>(v)) * 4;
+        return base + (static_cast<size_t>(slot + tid) * maxv + static_cast<uint32_t>(v)) * kLvQuads;
     }
 };
 __device__ __forceinline__ LightStore light_store(float* lv, int lv_max, uint32_t slot) {
@@ -77,6 +81,9 @@ struct Vertex {  // PathVertex (bdpt.h:24-35); its Frame is rebuilt from n where
     f3 p, n, wo, tp;
     float vcm, vc, rr;
     int mat;
+#if BDPT_TEXTURED
+    int tkd, tks;  // Hit::tkd, tks of the vertex
+#endif
 };
 
 #ifndef BDPT_LV_NT
@@ -108,6 +115,9 @@ __device__ __forceinline__ void store_vertex(const LightStore& ls, int v, const 
     lv_st(q + 1, make_float4(h.n.x, h.n.y, h.n.z, vc));
     lv_st(q + 2, make_float4(h.wo.x, h.wo.y, h.wo.z, rr));
     lv_st(q + 3, make_float4(tp.x, tp.y, tp.z, __int_as_float(h.mat)));
+#if BDPT_TEXTURED
+    lv_st(q + 4, make_float4(__int_as_float(h.tkd), __int_as_float(h.tks), 0.f, 0.f));
+#endif
 }
 
 __device__ __forceinline__ Vertex load_vertex_at(const float4* q) {
@@ -117,6 +127,10 @@ __device__ __forceinline__ Vertex load_vertex_at(const float4* q) {
     x.n = xyz(b), x.vc = b.w;
     x.wo = xyz(c), x.rr = c.w;
     x.tp = xyz(d), x.mat = __float_as_int(d.w);
+#if BDPT_TEXTURED
+    const float4 e = lv_ld(q + 4);
+    x.tkd = __float_as_int(e.x), x.tks = __float_as_int(e.y);
+#endif
     return x;
 }
 __device__ __forceinline__ Vertex load_vertex(const LightStore& ls, int v) {
@@ -127,6 +141,10 @@ __device__ __forceinline__ Vertex load_vertex(const LightStore& ls, int v) {
     x.n = xyz(b), x.vc = b.w;
     x.wo = xyz(c), x.rr = c.w;  // rr: always 1 under NO_RR (bdpt.h:18), where x * rr == x is not formed
     x.tp = xyz(d), x.mat = __float_as_int(d.w);
+#if BDPT_TEXTURED
+    const float4 e = lv_ld(q + 4);
+    x.tkd = __float_as_int(e.x), x.tks = __float_as_int(e.y);
+#endif
     return x;
 }
 
@@ -551,7 +569,7 @@ __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
         L.c.vc *= rcp_w(absCosIn); \
         act = A_LIGHT_CONTINUE; \
         if (rr_on(fr)) L.c.rr = rr_probability(fr, L.c.depth, L.c.tp);  /* bdpt.h:201-204 */ \
-        const BsdfRecord& b = bsdf_of(sc, L.h.mat); \
+        BDPT_VERTEX_BSDF(b, sc, L.h.mat, L.h.tkd, L.h.tks); \
         if (is_delta(b)) break; \
         if (COUNT) cnt.t_step++;  /* a camera-connection task (Counts::q) */ \
         /* connectToCamera (bdpt.h:295-371): everything but the visibility test. */ \
@@ -596,7 +614,7 @@ __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
     /* ContinuePathRandomWalk of either subpath (light: bdpt.h:211-215, eye: bdpt.h:152). */ \
     BDPT_ACTION(28, COND_) { \
         const bool light = act == A_LIGHT_CONTINUE; \
-        const BsdfRecord& b = bsdf_of(sc, L.h.mat); \
+        BDPT_VERTEX_BSDF(b, sc, L.h.mat, L.h.tkd, L.h.tks); \
         const bool delta = is_delta(b); \
         const float rrp = rr_on(fr) ? L.c.rr : 1.f; \
         /* the store is full: the vertex would be pushed only if the walk continues (bdpt.h:211-215) */ \
@@ -767,7 +785,7 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
     BDPT_ACTION(25, act == A_NEE) {  // connectToLight (bdpt.h:374-430): everything but the visibility test
         act = A_CONN;
         if (COUNT) cnt.t_step += 1u + (fr.strategy == 0 ? static_cast<uint32_t>(L.c.nl) : 0u);  // (Counts::q)
-        const BsdfRecord& b = bsdf_of(sc, L.h.mat);
+        BDPT_VERTEX_BSDF(b, sc, L.h.mat, L.h.tkd, L.h.tks);
         const EmitterRecord& e = emitter_of(sc, e_id);
         f3 dir = L.h.p - e_p;
         const float d2 = dot(dir, dir);
@@ -810,7 +828,7 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
     BDPT_ACTION(27, act == A_CONN) {  // connectVertices (bdpt.h:434-483) with light vertex ci
         act = A_EYE_CONTINUE;
         if (fr.strategy != 0) break;  // LIGHT/PATH_TRACING builds skip connections (bdpt.h:145)
-        const BsdfRecord& be = bsdf_of(sc, L.h.mat);
+        BDPT_VERTEX_BSDF(be, sc, L.h.mat, L.h.tkd, L.h.tks);
         while (L.c.ci < L.c.nl) {
             const Vertex V = load_vertex(ls, L.c.ci);
             if (COUNT) cnt.c[5]++;
@@ -825,7 +843,7 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
                 L.c.ci++;
                 continue;
             }
-            const BsdfRecord& bl = bsdf_of(sc, V.mat);
+            BDPT_VERTEX_BSDF(bl, sc, V.mat, V.tkd, V.tks);
             const f3 wiL = local_for(bl, V.n, dir);  // Frame(n) is a pure function of n
             const f3 wiE = local_for(be, L.h.n, -dir);
 #else
@@ -836,7 +854,7 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
                 L.c.ci++;
                 continue;
             }
-            const BsdfRecord& bl = bsdf_of(sc, V.mat);
+            BDPT_VERTEX_BSDF(bl, sc, V.mat, V.tkd, V.tks);
 #endif
             const EvalPdfs eL = bsdf_eval_pdfs(bl, wiL, V.wo), eE = bsdf_eval_pdfs(be, wiE, L.h.wo);
             f3 Li = eL.f * eE.f;
@@ -945,6 +963,9 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
         const f3 hn = mk(__shfl(L.h.n.x, src), __shfl(L.h.n.y, src), __shfl(L.h.n.z, src));
         const f3 hwo = mk(__shfl(L.h.wo.x, src), __shfl(L.h.wo.y, src), __shfl(L.h.wo.z, src));
         const int hmat = __shfl(L.h.mat, src), hshape = __shfl(L.h.shape, src);
+#if BDPT_TEXTURED
+        const int htkd = __shfl(L.h.tkd, src), htks = __shfl(L.h.tks, src);
+#endif
         if (o < 0) continue;
         const LaneCold& oc = wave_cold[o];
         const Vertex V = load_vertex_at(ls.at_tid(oc.ci + j, (opaque_tid() & ~63u) + static_cast<uint32_t>(o)));
@@ -954,8 +975,8 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
         dir = dir * sqrt_w(invD2);
         const float cosL = dot(dir, V.n), cosE = dot(-dir, hn);
         if (cosL <= 0.f || cosE <= 0.f) continue;
-        const BsdfRecord& be = bsdf_of(sc, hmat);
-        const BsdfRecord& bl = bsdf_of(sc, V.mat);
+        BDPT_VERTEX_BSDF(be, sc, hmat, htkd, htks);
+        BDPT_VERTEX_BSDF(bl, sc, V.mat, V.tkd, V.tks);
         const f3 wiL = local_for(bl, V.n, dir);
         const f3 wiE = local_for(be, hn, -dir);
         const EvalPdfs eL = bsdf_eval_pdfs(bl, wiL, V.wo), eE = bsdf_eval_pdfs(be, wiE, hwo);

@@ -74,6 +74,9 @@ struct CameraConstants {
 #endif
 constexpr int kShadeStride = BDPT_SHADE_WIDE ? 8 : 5;
 constexpr int kShadeV0 = 5;  // slot of (v0, 0) in a wide record
+// Scenes with bitmap textures: slots 6, 7 of a wide record hold the corners' texture
+// coordinates (s0 t0 s1 t1) (s2 t2 0 0), zero otherwise (as before).
+constexpr int kShadeSt = 6;
 
 constexpr uint32_t kLeafBit = 0x80000000u;
 // Words per lane slot of the BDPT megakernel's MT19937 ring (DevScene::mt_ring):

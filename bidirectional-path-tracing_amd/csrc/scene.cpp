@@ -159,6 +159,41 @@ struct MaterialTable {
     }
 };
 
+// ParseTextureNameAndOption (tiny_obj_loader.h:861-961): options (each followed by a
+// fixed number of blank-separated values) are skipped, the first other token starts
+// the name, which runs to the end of the line (blanks included); the name is kept
+// only if one was found.
+void parse_texname(const char* t, std::string& name) {
+    static const struct {
+        const char* key;
+        int values;
+    } kOptions[] = {{"-blendu", 1}, {"-blendv", 1}, {"-clamp", 1}, {"-boost", 1}, {"-bm", 1},     {"-o", 3},
+                    {"-s", 3},      {"-t", 3},      {"-type", 1},  {"-imfchan", 1}, {"-mm", 2}};
+    bool found = false;
+    std::string got;
+    while (!is_newline(*t)) {
+        t += std::strspn(t, " \t");
+        bool option = false;
+        for (const auto& o : kOptions) {
+            const size_t n = std::strlen(o.key);
+            if (std::strncmp(t, o.key, n) == 0 && is_space(t[n])) {
+                t += n;
+                for (int k = 0; k < o.values; k++) {
+                    t += std::strspn(t, " \t");
+                    t += std::strcspn(t, " \t\r");
+                }
+                option = true;
+                break;
+            }
+        }
+        if (option) continue;
+        got = t;
+        t += got.size();
+        found = true;
+    }
+    if (found) name = got;
+}
+
 // LoadMtl (tiny_obj_loader.h:1273-1657), keys the BDPT path reads.
 void parse_mtl(const std::string& text, MaterialTable& tab) {
     Material m;
@@ -195,8 +230,10 @@ void parse_mtl(const std::string& text, MaterialTable& tab) {
         } else if (std::strncmp(t, "illum", 5) == 0 && is_space(t[5])) {
             t += 6;
             m.illum = next_int(t);
-        } else if ((std::strncmp(t, "map_Kd", 6) == 0 || std::strncmp(t, "map_Ks", 6) == 0) && is_space(t[6])) {
-            m.has_texture = true;
+        } else if (std::strncmp(t, "map_Kd", 6) == 0 && is_space(t[6])) {
+            parse_texname(t + 7, m.map_kd);
+        } else if (std::strncmp(t, "map_Ks", 6) == 0 && is_space(t[6])) {
+            parse_texname(t + 7, m.map_ks);
         }
     });
     tab.flush(m);  // the last material is always flushed
@@ -218,8 +255,7 @@ bool point_in_triangle(const float* vx, const float* vy, float tx, float ty) {
 }
 
 struct ObjBuilder {
-    std::vector<float> v, vn;
-    int nvt = 0;
+    std::vector<float> v, vn, vt;  // vt: two floats per `vt` line (tiny_obj_loader.h:1754-1762)
     std::vector<Face> group;
     struct Tri {
         Corner c[3];
@@ -342,14 +378,16 @@ bool parse_obj(const std::string& path, ObjBuilder& ob, MaterialTable& mats, std
             t += 3;
             for (int k = 0; k < 3; k++) ob.vn.push_back(next_real(t, 0.0));
         } else if (t[0] == 'v' && t[1] == 't' && is_space(t[2])) {
-            ob.nvt++;
+            t += 3;
+            for (int k = 0; k < 2; k++) ob.vt.push_back(next_real(t, 0.0));
         } else if (t[0] == 'f' && is_space(t[1])) {
             t += 2;
             t += std::strspn(t, " \t");
             Face f;
             while (!is_newline(*t)) {
                 Corner c;
-                if (!next_corner(t, static_cast<int>(ob.v.size() / 3), static_cast<int>(ob.vn.size() / 3), ob.nvt, &c)) {
+                if (!next_corner(t, static_cast<int>(ob.v.size() / 3), static_cast<int>(ob.vn.size() / 3),
+                                 static_cast<int>(ob.vt.size() / 2), &c)) {
                     err = "Failed parse `f' line (e.g. zero value for face index) in " + path;
                     ok = false;
                     return;
@@ -521,11 +559,141 @@ bool check_shape_bsdfs(const HostScene& s, std::string& err) {
     return true;
 }
 
+// ---------------------------------------------------------------- textures
+// glibc's powf restated (powf_restated.inc, the source the kernels' glibc_powf is
+// built from), so a texel does not depend on the libm of the machine that loads
+// the scene.
+namespace hostmath {
+inline uint32_t f2u(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    return u;
+}
+inline float pf_u2f(uint32_t u) {
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+inline double d_from_u(uint64_t u) {
+    double d;
+    std::memcpy(&d, &u, 8);
+    return d;
+}
+inline uint64_t u_from_d(double d) {
+    uint64_t u;
+    std::memcpy(&u, &d, 8);
+    return u;
+}
+#define BDPT_PF_TABLE static const
+#define BDPT_PF_INLINE inline
+#define BDPT_PF_NOINLINE inline
+#define BDPT_PF_ENTRY inline
+#include "powf_restated.inc"
+#undef BDPT_PF_TABLE
+#undef BDPT_PF_INLINE
+#undef BDPT_PF_NOINLINE
+#undef BDPT_PF_ENTRY
+}  // namespace hostmath
+
+// BitmapTexture3f's path rule (core.h:528-542) and Tex::load's (core.h:494-500): a
+// relative name resolves against the OBJ's directory, the extension becomes .ppm.
+std::string texture_path(const std::string& obj_dir, const std::string& name) {
+    std::string p = (!name.empty() && name[0] == '/') ? name : obj_dir + name;
+    const size_t slash = p.find_last_of('/');
+    const size_t first = slash == std::string::npos ? 0 : slash + 1;
+    const size_t dot = p.find_last_of('.');
+    const std::string fname = p.substr(first);
+    if (dot != std::string::npos && dot > first && fname != "..") p.resize(dot);  // path::replace_extension
+    return p + ".ppm";
+}
+
+// Tex::loadpxm<uint8_t> (core.h:455-486) with pf / fl (core.h:430-442): header
+// "%*s %d %d %d%*c" (no comments), w * h * 3 bytes, each channel
+// powf(float(byte) / float(maxval), 2.2f), rows flipped. Unlike the reference (a 1 x 1
+// pink texture) an unreadable file is an error, and so is an inconsistent one.
+bool load_ppm_texture(const std::string& path, TextureImage& out, std::string& err, int* code) {
+    std::string buf;
+    if (!read_whole_file(path, buf)) {
+        err = "cannot open texture " + path;
+        if (code) *code = BDPT_ERR_IO;
+        return false;
+    }
+    if (code) *code = BDPT_ERR_INVALID;
+    int w = 0, h = 0, e = 0, used = -1;
+    const int got = std::sscanf(buf.c_str(), "%*s %d %d %d%*c%n", &w, &h, &e, &used);
+    if (got != 3 || w <= 0 || h <= 0 || e < 1 || e > 255) {
+        err = "texture " + path + ": bad PPM header (needs width, height > 0 and maxval in 1..255, no comments)";
+        return false;
+    }
+    const uint64_t sz = static_cast<uint64_t>(w) * static_cast<uint64_t>(h) * 3u;
+    if (sz > (1ull << 31) - 1) {
+        err = "texture " + path + ": w * h * 3 does not fit the reference's int";
+        return false;
+    }
+    if (used < 0 || buf.size() - static_cast<size_t>(used) < sz) {
+        err = "texture " + path + ": file shorter than width * height * 3 bytes";
+        return false;
+    }
+    const unsigned char* ct = reinterpret_cast<const unsigned char*>(buf.data()) + used;
+    out.w = w, out.h = h;
+    out.cs.resize(sz);
+    const float ef = static_cast<float>(e);
+    float lut[256];
+    for (int b = 0; b < 256; b++) lut[b] = hostmath::glibc_powf(static_cast<float>(b) / ef, 2.2f);
+    for (uint64_t i = 0; i < sz; i++) {
+        const uint64_t j = i / 3, x = j % w, y = j / w;
+        out.cs[i] = lut[ct[3 * ((h - y - 1) * w + x) + i % 3]];
+    }
+    return true;
+}
+
+// Texture<v3f>::getMax / getAverage of a material's reflectance (core.h:509-511, :544-567).
+F3 reflectance_max(const TextureImage* t, const float* constant) {
+    if (!t) return load3(constant);
+    const float lo = -1.17549435e-38f;  // -numeric_limits<float>::min()
+    F3 s{lo, lo, lo};
+    for (size_t i = 0; i < t->cs.size() / 3; i++)
+        s = {gmax(s.x, t->cs[3 * i]), gmax(s.y, t->cs[3 * i + 1]), gmax(s.z, t->cs[3 * i + 2])};
+    return s;
+}
+F3 reflectance_average(const TextureImage* t, const float* constant) {
+    if (!t) return load3(constant);
+    F3 s{0.f, 0.f, 0.f};
+    for (size_t i = 0; i < t->cs.size() / 3; i++) s = s + F3{t->cs[3 * i], t->cs[3 * i + 1], t->cs[3 * i + 2]};
+    const float scale = 1.0 / (t->cs.size() / 3.0);  // (a double division, rounded to float: core.h:549)
+    return s * scale;
+}
+
+// mixture.h:39-46 / phong.h:40-47: energy-conserving scale and specular sampling weight.
+void glossy_constants(BsdfRecord& b, const TextureImage* kd_tex, const TextureImage* ks_tex) {
+    F3 mx = reflectance_max(ks_tex, b.ks) + reflectance_max(kd_tex, b.kd);
+    float actualMax = std::max(std::max(mx.x, mx.y), mx.z);
+    b.scale = actualMax > 1.0f ? 0.99f * (1.0f / actualMax) : 1.0f;
+    const F3 lum{0.212671f, 0.715160f, 0.072169f};
+    float dAvg = dot(reflectance_average(kd_tex, b.kd) * b.scale, lum);
+    float sAvg = dot(reflectance_average(ks_tex, b.ks) * b.scale, lum);
+    b.specw = sAvg / (dAvg + sAvg);
+}
+
+// A face of a textured material must carry texture coordinates: the reference reads
+// texcoords[2 * -1] there (core.h:572-577).
+bool check_textured_faces(const HostScene& s, const std::vector<uint8_t>& has_st, std::string& err) {
+    for (size_t i = 0; i < s.num_triangles(); i++) {
+        const Material& m = s.materials[s.tri_mat[i]];
+        if ((m.kd_tex >= 0 || m.ks_tex >= 0) && !has_st[i]) {
+            err = "triangle " + std::to_string(i) + " of textured material '" + m.name + "' has no texture coordinates";
+            return false;
+        }
+    }
+    return true;
+}
+
 }  // namespace
 
-bool load_obj_scene(const std::string& obj_path, HostScene& s, std::string& err) {
+bool load_obj_scene(const std::string& obj_path, HostScene& s, std::string& err, int* code) {
     ObjBuilder ob;
     MaterialTable mats;
+    if (code) *code = BDPT_ERR_IO;  // (every failure that is not a texture's keeps the historical code)
     if (!parse_obj(obj_path, ob, mats, err)) return false;
     const size_t n = ob.tris.size();
     s = HostScene();
@@ -534,8 +702,21 @@ bool load_obj_scene(const std::string& obj_path, HostScene& s, std::string& err)
     s.tri_shape.resize(n);
     s.tri_prim.resize(n);
     s.tri_mat.resize(n);
+    bool any_map = false;
+    for (const Material& m : mats.list) any_map = any_map || !m.map_kd.empty() || !m.map_ks.empty();
+    std::vector<uint8_t> has_st(n, 0);
+    if (any_map) s.st.assign(6 * n, 0.f);
     for (size_t i = 0; i < n; i++) {
         const ObjBuilder::Tri& t = ob.tris[i];
+        if (any_map) {  // the corners' texcoord_index into attrib.texcoords (core.h:572-577)
+            bool all = true;
+            for (int c = 0; c < 3; c++) all = all && t.c[c].vt >= 0 && 2 * static_cast<size_t>(t.c[c].vt) + 1 < ob.vt.size();
+            has_st[i] = all;
+            for (int c = 0; all && c < 3; c++) {
+                s.st[6 * i + 2 * c] = ob.vt[2 * t.c[c].vt];
+                s.st[6 * i + 2 * c + 1] = ob.vt[2 * t.c[c].vt + 1];
+            }
+        }
         for (int c = 0; c < 3; c++) {
             if (t.c[c].v < 0 || 3 * static_cast<size_t>(t.c[c].v) + 2 >= ob.v.size()) {
                 err = "face vertex index out of range";
@@ -567,24 +748,37 @@ bool load_obj_scene(const std::string& obj_path, HostScene& s, std::string& err)
     for (size_t i = 0; i < n; i++) s.shape_count[s.tri_shape[i]]++;
 
     // BSDFs by illum (renderer.cpp:258-271) with the constructors' constants.
-    for (const Material& m : s.materials) {
-        if (m.has_texture) {
-            err = "material '" + m.name + "' uses a bitmap texture (not supported)";
-            return false;
+    std::string obj_dir = obj_path.substr(0, obj_path.find_last_of('/') + 1);
+    std::unordered_map<std::string, int> loaded;  // resolved path -> index in s.textures
+    auto texture_of = [&](const std::string& name, int& index) {
+        const std::string path = texture_path(obj_dir, name);
+        auto it = loaded.find(path);
+        if (it == loaded.end()) {
+            TextureImage img;
+            if (!load_ppm_texture(path, img, err, code)) return false;
+            it = loaded.emplace(path, static_cast<int>(s.textures.size())).first;
+            s.textures.push_back(std::move(img));
         }
+        index = it->second;
+        return true;
+    };
+    for (Material& m : s.materials) {
         BsdfRecord b = bsdf_record(m);
-        if (b.kind == BSDF_MIXTURE || b.kind == BSDF_PHONG) {
-            // mixture.h:39-46 / phong.h:40-47: energy-conserving scale and specular sampling weight.
-            F3 mx = load3(b.ks) + load3(b.kd);
-            float actualMax = std::max(std::max(mx.x, mx.y), mx.z);
-            b.scale = actualMax > 1.0f ? 0.99f * (1.0f / actualMax) : 1.0f;
-            const F3 lum{0.212671f, 0.715160f, 0.072169f};
-            float dAvg = dot(load3(b.kd) * b.scale, lum);
-            float sAvg = dot(load3(b.ks) * b.scale, lum);
-            b.specw = sAvg / (dAvg + sAvg);
-        }
+        // The BSDFs that read a Texture<v3f> (diffuse.h:23-26, mixture.h:27-35, phong.h:28-36);
+        // mirror, glass and the null BSDF never look at the map names.
+        const bool glossy = b.kind == BSDF_MIXTURE || b.kind == BSDF_PHONG;
+        if ((glossy || b.kind == BSDF_DIFFUSE) && !m.map_kd.empty() && !texture_of(m.map_kd, m.kd_tex)) return false;
+        if (glossy && !m.map_ks.empty() && !texture_of(m.map_ks, m.ks_tex)) return false;
+        m.has_texture = m.kd_tex >= 0 || m.ks_tex >= 0;
+        if (glossy)
+            glossy_constants(b, m.kd_tex >= 0 ? &s.textures[m.kd_tex] : nullptr,
+                             m.ks_tex >= 0 ? &s.textures[m.ks_tex] : nullptr);
         s.bsdfs.push_back(b);
     }
+    if (s.textures.empty()) s.st.clear();
+    if (code) *code = BDPT_ERR_INVALID;
+    if (!s.textures.empty() && !check_textured_faces(s, has_st, err)) return false;
+    if (code) *code = BDPT_ERR_IO;
     if (!check_shape_bsdfs(s, err)) return false;
     // Emitters: shapes whose first face's BSDF emits (renderer.cpp:279-305).
     for (int sh = 0; sh < nshapes; sh++) {
@@ -611,7 +805,7 @@ bool load_obj_scene(const std::string& obj_path, HostScene& s, std::string& err)
 }
 
 // ------------------------------------------------------ caller's Scene (desc)
-bool load_desc_scene(const bdpt_scene_desc& d, HostScene& s, std::string& err) {
+bool load_desc_scene(const bdpt_scene_desc& d, const bdpt_scene_textures* tx, HostScene& s, std::string& err) {
     s = HostScene();
     if (d.triangles <= 0 || !d.positions || !d.normals || !d.tri_shape || !d.tri_prim || !d.tri_mat) {
         err = "scene descriptor: no triangles or a null triangle array";
@@ -657,8 +851,9 @@ bool load_desc_scene(const bdpt_scene_desc& d, HostScene& s, std::string& err) {
     }
     for (int32_t m = 0; m < d.materials; m++) {
         const bdpt_material_desc& md = d.material[m];
-        if (md.has_texture) {
-            err = "material " + std::to_string(m) + " uses a bitmap texture (not supported)";
+        if (md.has_texture && !tx) {
+            err = "material " + std::to_string(m) + " uses a bitmap texture: hand the scene over with "
+                  "bdpt_scene_create_textured";
             return false;
         }
         Material mt;
@@ -674,6 +869,51 @@ bool load_desc_scene(const bdpt_scene_desc& d, HostScene& s, std::string& err) {
             b.specw = md.spec_weight;
         }
         s.bsdfs.push_back(b);
+    }
+    if (tx) {  // the caller's BitmapTexture3f objects: Tex::cs as loaded, checked, nothing recomputed
+        if (tx->ntextures < 0 || (tx->ntextures > 0 && !tx->texture) || !tx->diffuse_tex || !tx->specular_tex) {
+            err = "texture descriptor: null table";
+            return false;
+        }
+        for (int32_t k = 0; k < tx->ntextures; k++) {
+            const bdpt_texture_desc& td = tx->texture[k];
+            if (td.width <= 0 || td.height <= 0 || !td.rgb ||
+                static_cast<uint64_t>(td.width) * static_cast<uint64_t>(td.height) * 3u > (1ull << 31) - 1) {
+                err = "texture descriptor: texture " + std::to_string(k) + " has a bad size or no texels";
+                return false;
+            }
+            TextureImage img;
+            img.w = td.width, img.h = td.height;
+            img.cs.assign(td.rgb, td.rgb + static_cast<size_t>(td.width) * td.height * 3);
+            s.textures.push_back(std::move(img));
+        }
+        for (int32_t m = 0; m < d.materials; m++) {
+            const int32_t kd = tx->diffuse_tex[m], ks = tx->specular_tex[m];
+            if (kd < -1 || kd >= tx->ntextures || ks < -1 || ks >= tx->ntextures) {
+                err = "texture descriptor: material " + std::to_string(m) + " names a texture out of range";
+                return false;
+            }
+            const int kind = s.bsdfs[m].kind;
+            const bool glossy = kind == BSDF_MIXTURE || kind == BSDF_PHONG;
+            if ((kd >= 0 && !glossy && kind != BSDF_DIFFUSE) || (ks >= 0 && !glossy)) {
+                err = "texture descriptor: material " + std::to_string(m) + " has a map its BSDF does not read";
+                return false;
+            }
+            s.materials[m].kd_tex = kd, s.materials[m].ks_tex = ks;
+            s.materials[m].has_texture = kd >= 0 || ks >= 0;
+        }
+        if (!s.textures.empty()) {
+            if (!tx->texcoords) {
+                err = "texture descriptor: textures without texcoords";
+                return false;
+            }
+            s.st.assign(tx->texcoords, tx->texcoords + 6 * n);
+            for (float v : s.st)
+                if (!std::isfinite(v)) {
+                    err = "texture descriptor: a texture coordinate is not finite";
+                    return false;
+                }
+        }
     }
     if (!check_shape_bsdfs(s, err)) return false;
     for (int32_t k = 0; k < d.emitters; k++) {
@@ -918,6 +1158,33 @@ bool build_device_layout(const HostScene& s, DeviceLayout& out, std::string& err
         return false;
     }
     out.shape_emitter = s.shape_emitter;
+    if (!s.textures.empty()) {
+        const size_t nm = s.materials.size();
+        size_t texels = 0;
+        for (const TextureImage& t : s.textures) texels += t.cs.size() / 3;
+        if (2 * nm + texels >= (size_t(1) << 31)) {
+            err = "more than 2^31 texels";
+            return false;
+        }
+        out.tex_tab.assign(2 * nm + texels, float4_t{0.f, 0.f, 0.f, 0.f});
+        size_t at = 2 * nm;
+        for (const TextureImage& t : s.textures) {
+            out.tex_dims.insert(out.tex_dims.end(), {t.w, t.h, static_cast<int32_t>(at)});
+            for (size_t i = 0; i < t.cs.size() / 3; i++) out.tex_tab[at++] = {t.cs[3 * i], t.cs[3 * i + 1], t.cs[3 * i + 2], 0.f};
+        }
+        for (size_t m = 0; m < nm; m++) {
+            const int ids[2] = {s.materials[m].kd_tex, s.materials[m].ks_tex};
+            for (int k = 0; k < 2; k++) {
+                out.mat_tex.push_back(ids[k]);
+                float4_t r = {bits(-1), bits(0), bits(0), bits(0)};
+                if (ids[k] >= 0) r = {bits(out.tex_dims[3 * ids[k] + 2]), bits(s.textures[ids[k]].w), bits(s.textures[ids[k]].h), bits(0)};
+                out.tex_tab[2 * m + k] = r;
+            }
+        }
+        out.tri_st.resize(6 * n);
+        for (size_t i = 0; i < n; i++)
+            std::memcpy(&out.tri_st[6 * i], &s.st[6 * static_cast<size_t>(s.order[i])], 6 * sizeof(float));
+    }
     return true;
 }
 

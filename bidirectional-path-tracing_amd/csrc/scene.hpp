@@ -26,6 +26,17 @@ struct Material {
     float Kd[3] = {0, 0, 0}, Ks[3] = {0, 0, 0}, Ke[3] = {0, 0, 0}, Tf[3] = {0, 0, 0};
     float Ns = 1.f, Ni = 1.f;  // tinyobj InitMaterial defaults (tiny_obj_loader.h:964-999)
     bool has_texture = false;
+    // map_Kd / map_Ks as tinyobj's diffuse_texname / specular_texname hold them, and the
+    // index of the loaded map in HostScene::textures (-1: the constant Kd / Ks)
+    std::string map_kd, map_ks;
+    int kd_tex = -1, ks_tex = -1;
+};
+
+// Tex (core.h:417-501) of a BitmapTexture3f: the PPM's texels gamma-expanded and
+// flipped vertically, cs[3 * (w * y + x) + c].
+struct TextureImage {
+    int w = 0, h = 0;
+    std::vector<float> cs;
 };
 
 struct Emitter {
@@ -53,18 +64,24 @@ struct HostScene {
     std::vector<int32_t> order;
     std::vector<FlatNode> nodes;
     int max_depth = 0;
+    // Bitmap textures (empty for a scene without map_Kd / map_Ks): the distinct maps and
+    // the corners' texture coordinates, [ntri][6] = st0 st1 st2 (0 where a face has none).
+    std::vector<TextureImage> textures;
+    std::vector<float> st;
 
     size_t num_triangles() const { return tri_shape.size(); }
 };
 
 // Returns false and sets `err` on failure (missing file, bad face index, face
-// without normal or material, bitmap textures, null BSDF on an emitter test).
-bool load_obj_scene(const std::string& obj_path, HostScene& out, std::string& err);
+// without normal or material, null BSDF on an emitter test); *code (if given)
+// tells an unreadable file (BDPT_ERR_IO) from inconsistent content (BDPT_ERR_INVALID).
+bool load_obj_scene(const std::string& obj_path, HostScene& out, std::string& err, int* code = nullptr);
 
 // The same HostScene from the caller's in-memory Scene (core.h:352-358) handed
 // over as a bdpt_scene_desc: triangles, materials with their constructed
 // constants, emitters with their CDFs and the flattened Fast-BVH, validated.
-bool load_desc_scene(const bdpt_scene_desc& desc, HostScene& out, std::string& err);
+// `tex` (may be null): the caller's bitmap textures (bdpt_scene_create_textured).
+bool load_desc_scene(const bdpt_scene_desc& desc, const bdpt_scene_textures* tex, HostScene& out, std::string& err);
 
 // Flattened arrays uploaded to HBM (layouts documented in bdpt_types.h).
 struct DeviceLayout {
@@ -86,6 +103,15 @@ struct DeviceLayout {
     std::vector<float4_t> emit_tri; // 5 per emitter face, shape face order
     std::vector<float> emit_cdf;
     std::vector<int32_t> shape_emitter;
+    // Bitmap textures (all empty for an untextured scene): one flat pool of float4 texels
+    // (rgb, 0) preceded by two int4 records per material — the diffuse and the specular map
+    // as (first texel's index in tex_tab, w, h, 0), index -1 for none — and the triangles'
+    // texture coordinates in BVH leaf order, [ntri][6].
+    std::vector<float4_t> tex_tab;
+    std::vector<float> tri_st;
+    std::vector<int32_t> mat_tex;   // [materials][2]: index into `textures` of Kd / Ks map, -1 none
+    std::vector<int32_t> tex_dims;  // [textures][3]: w, h, first texel's index in tex_tab
+    bool textured() const { return !tex_tab.empty(); }
 };
 
 bool build_device_layout(const HostScene& s, DeviceLayout& out, std::string& err);

@@ -194,7 +194,8 @@ typedef struct {
     float ns, ni;              /* shininess, ior */
     float scale, spec_weight;  /* MixtureBSDF / PhongBSDF::scale, ::specularSamplingWeight as constructed
                                   (mixture.h:39-46, phong.h:40-47); unused by the other kinds */
-    int32_t has_texture;       /* non-zero: a bitmap texture (diffuse_/specular_texname) — rejected */
+    int32_t has_texture;       /* non-zero: a bitmap texture (diffuse_/specular_texname) — rejected by
+                                  bdpt_scene_create; hand such a scene over with bdpt_scene_create_textured */
 } bdpt_material_desc;
 typedef struct {
     int32_t shape;             /* Emitter::shapeID */
@@ -229,6 +230,36 @@ typedef struct {
  * copies it; the caller's arrays may be freed afterwards. BDPT_ERR_INVALID with a
  * message when it is inconsistent. */
 int bdpt_scene_create(const bdpt_scene_desc* desc, bdpt_scene** out);
+/* ---- bitmap textures (map_Kd / map_Ks: BitmapTexture3f, core.h:525-588) ----
+ * bdpt_scene_load_obj reads them itself (<name>.ppm next to the OBJ; an unreadable file
+ * is BDPT_ERR_IO, not the reference's pink texel). A caller that hands its Scene over
+ * passes, next to the unchanged bdpt_scene_desc, what its BitmapTexture3f objects hold. */
+typedef struct {
+    int32_t width, height;     /* Tex::w, Tex::h */
+    const float* rgb;          /* Tex::cs: [height][width][3], gamma-expanded and flipped as loaded */
+} bdpt_texture_desc;
+typedef struct {
+    int32_t ntextures;
+    const bdpt_texture_desc* texture;
+    const int32_t* diffuse_tex;  /* [desc->materials]: the texture behind diffuseReflectance / albedo, -1 = constant */
+    const int32_t* specular_tex; /* [desc->materials]: the texture behind specularReflectance, -1 = constant */
+    const float* texcoords;      /* [desc->triangles][6]: attrib.texcoords of the corners' texcoord_index, st0 st1 st2 */
+} bdpt_scene_textures;
+/* bdpt_scene_create with the textures of materials whose has_texture is set. Ranges are
+ * checked; nothing the caller supplies is recomputed (scale / spec_weight come from
+ * bdpt_material_desc as the constructors left them). textures may be NULL (= bdpt_scene_create). */
+int bdpt_scene_create_textured(const bdpt_scene_desc* desc, const bdpt_scene_textures* textures, bdpt_scene** out);
+/* The scene's texture arrays as uploaded, for checking that two ingest paths agree:
+ * 0 the table the kernels read (per material two int32[4] records — diffuse, specular map:
+ *   first texel's index in this table, w, h, 0; index -1 = none — then the pool of float[4]
+ *   texels rgb0), 1 the triangles' texture coordinates float[triangles][6] in BVH leaf order
+ *   (bdpt_scene_export's order), 2 int32[materials][2] texture index of the diffuse / specular
+ *   map (-1 none), 3 int32[textures][3] = w, h, first texel's index in array 0.
+ * Same size protocol as bdpt_scene_export_layout; every array is empty for a scene
+ * without bitmap textures. info (may be NULL): [0] textures, [1] texels, [2] HBM bytes
+ * of arrays 0 and 1. */
+#define BDPT_TEXTURE_ARRAYS 4
+int bdpt_scene_export_textures(const bdpt_scene* scene, int32_t array, void* dst, int64_t* bytes, int64_t info[3]);
 /* The scene's device arrays as uploaded by bdpt_ctx_create (the
  * same transforms: shade records widened with v0 and the triangle's near-cull
  * graze code in the shape word's top byte, mixture records with Ks = 0 as
