@@ -8,6 +8,8 @@ Mirrors the reference's plugin surface for the BDPT path
     .init()                            Integrator::init     src/core/integrator.cpp:16-20 (allocates rgb)
     .render(ray, sampler) -> Li        Integrator::render   bdpt.h:219-241 (one camera sample)
     .render_frame(...)                 Renderer::render offline loop renderer.cpp:130-214
+    .render_frame(window=SampleWindow(first, stride, count)) / .render_progressive(batch)
+                                       a part of that loop's samples per pixel (bdpt_render_window)
     .rgb                               Integrator::rgb      (W x H x 3 float32, accumulated)
   Sampler(seed)                        Sampler              src/core/math.h:63-76 (seed + draw count)
   Ray(o, d, min_t, max_t)              Ray                  src/core/core.h:117-122
@@ -73,6 +75,10 @@ class _SceneInfo(ctypes.Structure):
 class _PathParams(ctypes.Structure):  # bdpt_path_params
     _fields_ = [("is_explicit", ctypes.c_int32), ("max_depth", ctypes.c_int32), ("rr_depth", ctypes.c_int32),
                 ("rr_prob", ctypes.c_float), ("emitter_samples", ctypes.c_int32), ("bsdf_samples", ctypes.c_int32)]
+
+
+class _SampleWindow(ctypes.Structure):  # bdpt_sample_window
+    _fields_ = [("first", ctypes.c_int32), ("stride", ctypes.c_int32), ("count", ctypes.c_int32)]
 
 
 class _DirectParams(ctypes.Structure):  # bdpt_direct_params
@@ -275,6 +281,11 @@ def lib():
         L.bdpt_multi_render_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_PathParams),
                                              ctypes.POINTER(_DirectParams), vp]
         L.bdpt_multi_get_stats.argtypes = [vp, ctypes.POINTER(_MultiStats)]
+        L.bdpt_multi_set_sharding.argtypes = [vp, i32]
+        L.bdpt_render_window.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow),
+                                         ctypes.POINTER(_PathParams), ctypes.POINTER(_DirectParams), vp, vp]
+        L.bdpt_render_window_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow),
+                                              ctypes.POINTER(_PathParams), ctypes.POINTER(_DirectParams), vp]
         L.bdpt_synchronize.argtypes = [vp]
         L.bdpt_config_load_toml.argtypes = [ctypes.c_char_p, ctypes.POINTER(_Config)]
         L.bdpt_render_path.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_PathParams), vp, vp]
@@ -318,6 +329,43 @@ class Camera:
         c.eye[:], c.at[:], c.up[:] = list(map(float, self.eye)), list(map(float, self.at)), list(map(float, self.up))
         c.fov = float(self.fov)
         return c
+
+
+@dataclass(frozen=True)
+class SampleWindow:
+    """bdpt_sample_window: of each pixel's spp samples, k = first + i * stride for
+    0 <= i < count. Samples keep the seed and the 1 / spp weight of the frame's full
+    spp, so windows that partition range(spp) sum to the unwindowed frame."""
+    first: int = 0
+    stride: int = 1
+    count: int = 0
+
+    def samples(self) -> range:
+        return range(self.first, self.first + self.count * self.stride, self.stride)
+
+    def c(self) -> _SampleWindow:
+        return _SampleWindow(self.first, self.stride, self.count)
+
+    @staticmethod
+    def parse(text: str, spp: int | None = None) -> "SampleWindow":
+        """"F:S:C" (the command line's --sample-window); ValueError when malformed or,
+        with spp given, invalid for that spp (the C-ABI's rule)."""
+        parts = text.split(":")
+        if len(parts) != 3:
+            raise ValueError(f"sample window {text!r}: expected first:stride:count")
+        try:
+            w = SampleWindow(*(int(x) for x in parts))
+        except ValueError:
+            raise ValueError(f"sample window {text!r}: first, stride and count must be integers") from None
+        if w.first < 0:
+            raise ValueError(f"sample window {text!r}: first must be >= 0")
+        if w.stride < 1:
+            raise ValueError(f"sample window {text!r}: stride must be >= 1")
+        if w.count < 0:
+            raise ValueError(f"sample window {text!r}: count must be >= 0")
+        if spp is not None and w.count > 0 and w.first + (w.count - 1) * w.stride >= spp:
+            raise ValueError(f"sample window {text!r}: count reaches past spp = {spp}")
+        return w
 
 
 @dataclass
@@ -770,19 +818,61 @@ class BDPTIntegrator:
         _check(lib().bdpt_splat_to_image_plane(self._h, ctypes.byref(p), q.shape[0], q.ctypes.data, out.ctypes.data))
         return out
 
-    def render_frame(self, row_offset: int = 0, row_stride: int = 1, flags: int = 0) -> np.ndarray:
-        """All pixels x spp of the (sharded) image into self.rgb (host copy)."""
+    def _integrator_params(self):
+        """(bdpt_path_params, bdpt_direct_params) of bdpt_render_window: None, None = BDPT."""
+        return None, None
+
+    def _window_host(self, p: _FrameParams, window: SampleWindow) -> None:
+        pp, dp = self._integrator_params()
+        w = window.c()
+        _check(lib().bdpt_render_window_host(self._h, ctypes.byref(p), ctypes.byref(w), pp and ctypes.byref(pp),
+                                             dp and ctypes.byref(dp), self.rgb.ctypes.data))
+
+    def _window_device(self, p: _FrameParams, window: SampleWindow, fb_ptr: int, stream_ptr: int) -> None:
+        pp, dp = self._integrator_params()
+        w = window.c()
+        _check(lib().bdpt_render_window(self._h, ctypes.byref(p), ctypes.byref(w), pp and ctypes.byref(pp),
+                                        dp and ctypes.byref(dp), ctypes.c_void_p(fb_ptr),
+                                        ctypes.c_void_p(stream_ptr)))
+
+    def render_frame(self, row_offset: int = 0, row_stride: int = 1, flags: int = 0,
+                     window: SampleWindow | None = None) -> np.ndarray:
+        """All pixels x spp of the (sharded) image into self.rgb (host copy); with a
+        window only its samples of every pixel (bdpt_render_window_host)."""
         if self.rgb is None:
             self.init()
         p = self.params(row_offset, row_stride, flags)
+        if window is not None:
+            self._window_host(p, window)
+            return self.rgb
         _check(lib().bdpt_render_host(self._h, ctypes.byref(p), self.rgb.ctypes.data))
         return self.rgb
 
     def render_device(self, fb_ptr: int, stream_ptr: int = 0, row_offset: int = 0, row_stride: int = 1,
-                      flags: int = 0) -> None:
+                      flags: int = 0, window: SampleWindow | None = None) -> None:
         """Asynchronous render into a device framebuffer (e.g. a torch tensor's data_ptr())."""
         p = self.params(row_offset, row_stride, flags)
+        if window is not None:
+            return self._window_device(p, window, fb_ptr, stream_ptr)
         _check(lib().bdpt_render(self._h, ctypes.byref(p), ctypes.c_void_p(fb_ptr), ctypes.c_void_p(stream_ptr)))
+
+    def render_progressive(self, batch: int):
+        """Generator: renders the contiguous sample windows [0, batch), [batch, 2 batch), ...
+        into self.rgb (zeroed first) and yields (done_spp, preview) after each, with preview =
+        self.rgb * (spp / done_spp). Every contribution of a sample, light-path splats
+        included, carries 1 / spp, so the preview is the unbiased estimate from the samples
+        so far; the last item has done_spp == spp and the full frame (the same samples as
+        render_frame())."""
+        if batch < 1:
+            raise ValueError("render_progressive: batch must be >= 1")
+        spp = self.config.spp
+        self.init()
+        done = 0
+        while done < spp:
+            n = min(batch, spp - done)
+            self.render_frame(window=SampleWindow(done, 1, n))
+            done += n
+            yield done, (self.rgb if done == spp else self.rgb * np.float32(spp / done))
 
     def stats(self) -> dict:
         s = _Stats()
@@ -841,19 +931,28 @@ class PathTracerIntegrator(BDPTIntegrator):
         sampler.state = st
         return np.array(Li[:], np.float32)
 
-    def render_frame(self, row_offset: int = 0, row_stride: int = 1, flags: int = 0) -> np.ndarray:
+    def _integrator_params(self):
+        return self.path.c(), None
+
+    def render_frame(self, row_offset: int = 0, row_stride: int = 1, flags: int = 0,
+                     window: SampleWindow | None = None) -> np.ndarray:
         if self.rgb is None:
             self.init()
         p, pp = self.params(row_offset, row_stride, flags), self.path.c()
+        if window is not None:
+            self._window_host(p, window)
+            return self.rgb
         _check(lib().bdpt_render_path_host(self._h, ctypes.byref(p), ctypes.byref(pp), self.rgb.ctypes.data))
         return self.rgb
 
     def render_device(self, fb_ptr: int, stream_ptr: int = 0, row_offset: int = 0, row_stride: int = 1,
-                      flags: int = 0) -> None:
+                      flags: int = 0, window: SampleWindow | None = None) -> None:
         """Asynchronous; call check_levels() after the stream is synchronised: a
         sample that outgrew the 512-level recursion stack makes the frame differ
         from the reference's (render_frame checks this itself)."""
         p, pp = self.params(row_offset, row_stride, flags), self.path.c()
+        if window is not None:
+            return self._window_device(p, window, fb_ptr, stream_ptr)
         _check(lib().bdpt_render_path(self._h, ctypes.byref(p), ctypes.byref(pp), ctypes.c_void_p(fb_ptr),
                                       ctypes.c_void_p(stream_ptr)))
 
@@ -886,16 +985,25 @@ class DirectIntegrator(BDPTIntegrator):
         sampler.state = st
         return np.array(Li[:], np.float32)
 
-    def render_frame(self, row_offset: int = 0, row_stride: int = 1, flags: int = 0) -> np.ndarray:
+    def _integrator_params(self):
+        return None, self.direct.c()
+
+    def render_frame(self, row_offset: int = 0, row_stride: int = 1, flags: int = 0,
+                     window: SampleWindow | None = None) -> np.ndarray:
         if self.rgb is None:
             self.init()
         p, d = self.params(row_offset, row_stride, flags), self.direct.c()
+        if window is not None:
+            self._window_host(p, window)
+            return self.rgb
         _check(lib().bdpt_render_direct_host(self._h, ctypes.byref(p), ctypes.byref(d), self.rgb.ctypes.data))
         return self.rgb
 
     def render_device(self, fb_ptr: int, stream_ptr: int = 0, row_offset: int = 0, row_stride: int = 1,
-                      flags: int = 0) -> None:
+                      flags: int = 0, window: SampleWindow | None = None) -> None:
         p, d = self.params(row_offset, row_stride, flags), self.direct.c()
+        if window is not None:
+            return self._window_device(p, window, fb_ptr, stream_ptr)
         _check(lib().bdpt_render_direct(self._h, ctypes.byref(p), ctypes.byref(d), ctypes.c_void_p(fb_ptr),
                                         ctypes.c_void_p(stream_ptr)))
 
@@ -905,16 +1013,23 @@ class MultiDeviceRenderer:
     over host threads (parallelfor.h:25-65) as one context and stream per device,
     interleaved row shards, and one RCCL sum-reduce of the frames to devices[0].
     A repeated device (e.g. [0, 0]) rehearses the decomposition on one GPU with a
-    local sum instead of RCCL."""
+    local sum instead of RCCL. sharding="samples" splits by samples instead of rows:
+    device i renders samples i, i + N, ... of every pixel of the whole image
+    (bdpt_multi_set_sharding), equal work per device whatever the rows cost."""
+
+    SHARDING = {"rows": 0, "samples": 1}  # BDPT_SHARD_*
 
     def __init__(self, scene: Scene, config: Config, devices=(0,), path: PathSettings | None = None,
-                 direct: DirectSettings | None = None):
+                 direct: DirectSettings | None = None, sharding: str = "rows"):
+        if sharding not in self.SHARDING:
+            raise ValueError(f"sharding must be 'rows' or 'samples', not {sharding!r}")
         self.scene, self.config, self.devices = scene, config, list(devices)
-        self.path, self.direct = path, direct
+        self.path, self.direct, self.sharding = path, direct, sharding
         dev = (ctypes.c_int32 * len(self.devices))(*self.devices)
         h = ctypes.c_void_p()
         _check(lib().bdpt_multi_create(scene._h, len(self.devices), dev, ctypes.byref(h)))
         self._h = h
+        _check(lib().bdpt_multi_set_sharding(self._h, self.SHARDING[sharding]))
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:

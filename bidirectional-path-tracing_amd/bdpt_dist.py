@@ -24,6 +24,19 @@ def shard_rows(rank: int, world: int, height: int) -> list[int]:
     return list(range(off, height, stride))
 
 
+def sample_shard(rank: int, world: int, spp: int):
+    """The bdpt_amd.SampleWindow of `rank` when the frame is split by samples instead
+    of rows: samples rank, rank + world, ... of every pixel of the whole image (count
+    0 when spp <= rank). Rows differ in cost, the samples of a pixel do not, so these
+    shards are balanced without a cost model; the buffers and the reduce are those
+    of the row shards. The windows of all ranks partition range(spp)."""
+    from bdpt_amd import SampleWindow
+
+    if world < 1 or not (0 <= rank < world) or spp < 1:
+        raise ValueError(f"bad sample shard {rank}/{world} of spp {spp}")
+    return SampleWindow(rank, world, max(0, (spp - rank + world - 1) // world))
+
+
 def reduce_framebuffer(fb, dst: int = 0) -> None:
     """Sums every rank's full-frame buffer into `fb` on rank `dst` (in place)."""
     import torch.distributed as dist

@@ -728,6 +728,13 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     c->grid = c->cus * (c->sc.lds_bsdf_off == dev::kNoLds ? frame_kernel_blocks_per_cu_hbm(dyn)
                                                           : frame_kernel_blocks_per_cu(dyn));
     c->nslots = static_cast<uint32_t>(c->grid * frame_kernel_block());
+    // BDPT_GRID_BLOCKS=n (debugging knob): at most n blocks per frame-kernel launch; the slots
+    // stay allocated for the whole grid. With few blocks a small frame gives each wave many
+    // chunks, which is what reuses its eye slots (tests/test_gpu_sample_window.py).
+    if (const char* gb = debug_knob("BDPT_GRID_BLOCKS")) {
+        const int n = std::atoi(gb);
+        if (n >= 1) c->grid = std::min(c->grid, n);
+    }
     // Traversal stack: worst case of either tree (binary: depth + 1 pending
     // right children; 4-wide: the host-computed bound), the part beyond the
     // kernel's LDS entries in HBM.
@@ -762,8 +769,21 @@ static int check_params(const bdpt_frame_params* p) {
     return BDPT_OK;
 }
 
+// A sample window (bdpt_render_window) of a frame whose spp the entry has accepted
+// (> 0); null = the whole range.
+static int check_window(const bdpt_frame_params* p, const bdpt_sample_window* w) {
+    if (!w) return BDPT_OK;
+    if (w->first < 0) return fail(BDPT_ERR_INVALID, "sample window: first must be >= 0");
+    if (w->stride < 1) return fail(BDPT_ERR_INVALID, "sample window: stride must be >= 1");
+    if (w->count < 0) return fail(BDPT_ERR_INVALID, "sample window: count must be >= 0");
+    if (w->count > 0 && static_cast<int64_t>(w->first) + static_cast<int64_t>(w->count - 1) * w->stride >= p->spp)
+        return fail(BDPT_ERR_INVALID, "sample window: count reaches past spp (first + (count - 1) * stride must be < spp = " +
+                                          std::to_string(p->spp) + ")");
+    return BDPT_OK;
+}
+
 constexpr int kExpressDepth = 512;  // Russian roulette: express mode past this many bounces
-static dev::DevFrame make_frame(const bdpt_frame_params* p) {
+static dev::DevFrame make_frame(const bdpt_frame_params* p, const bdpt_sample_window* w = nullptr) {
     dev::DevFrame fr{};
     camera_constants(p->camera.eye, p->camera.at, p->camera.up, p->camera.fov, p->width, p->height, fr.cam);
     for (int i = 0; i < 3; i++) fr.cam_o[i] = p->camera.eye[i];
@@ -772,7 +792,8 @@ static dev::DevFrame make_frame(const bdpt_frame_params* p) {
     fr.row_offset = p->row_offset, fr.row_stride = p->row_stride;
     fr.nrows = p->row_offset >= p->height ? 0 : (p->height - p->row_offset + p->row_stride - 1) / p->row_stride;
     fr.flags = p->flags;
-    fr.total_samples = static_cast<uint64_t>(fr.nrows) * static_cast<uint64_t>(p->width) * p->spp;
+    fr.win_first = w ? w->first : 0, fr.win_stride = w ? w->stride : 1, fr.win_count = w ? w->count : p->spp;
+    fr.total_samples = static_cast<uint64_t>(fr.nrows) * static_cast<uint64_t>(p->width) * fr.win_count;
     fr.rr_mode = p->russian_roulette == BDPT_RR_LUMINANCE ? 1 : 0;
     fr.depth_cap = fr.rr_mode ? kRrDepthGuard : p->rr_depth;
     fr.lv_max = fr.rr_mode ? std::max(kRrLightVerts, p->rr_depth - 1) : std::max(p->rr_depth - 1, 1);
@@ -866,14 +887,17 @@ static uint32_t node_slack_needed(const bdpt_ctx* c, const float* const* origins
     return 0u;
 }
 
-int bdpt_render(bdpt_ctx* c, const bdpt_frame_params* p, float* fb, void* hip_stream) {
+// bdpt_render and the BDPT form of bdpt_render_window (w null: every sample).
+static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* fb,
+                       void* hip_stream) {
     if (!c || !fb) return fail(BDPT_ERR_INVALID, "null argument");
     int rc = check_params(p);
     if (rc) return rc;
+    if ((rc = check_window(p, w))) return rc;
     if ((rc = textured_frame_check(c, p))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    dev::DevFrame fr = make_frame(p);
+    dev::DevFrame fr = make_frame(p, w);
     fr.capped = c->capped;
     if (!fr.rr_mode && fr.total_samples > 0 && (rc = ensure_tasks(c))) return rc;
     fr.tasks = c->tasks;
@@ -1011,6 +1035,10 @@ int bdpt_render(bdpt_ctx* c, const bdpt_frame_params* p, float* fb, void* hip_st
     return BDPT_OK;
 }
 
+int bdpt_render(bdpt_ctx* c, const bdpt_frame_params* p, float* fb, void* hip_stream) {
+    return render_bdpt(c, p, nullptr, fb, hip_stream);
+}
+
 static int ensure_tmp_fb(bdpt_ctx* c, size_t floats);
 
 // PathTracerIntegrator (path.h) on the same substrate: pt_kernels.hip.
@@ -1061,8 +1089,8 @@ static dev::DevScene pt_scene(const bdpt_ctx* c, const bdpt_frame_params* p) {
     return sc;
 }
 
-int bdpt_render_path(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_params* path, float* fb,
-                     void* hip_stream) {
+static int render_path(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                       const bdpt_path_params* path, float* fb, void* hip_stream) {
     if (!c || !fb || !path) return fail(BDPT_ERR_INVALID, "null argument");
     if (int trc = textured_unsupported(c, "the path integrator (texture + bdpt_render_path)")) return trc;
     if (!p) return fail(BDPT_ERR_INVALID, "null params");
@@ -1071,6 +1099,7 @@ int bdpt_render_path(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_pa
         return fail(BDPT_ERR_INVALID, "image too large (W*H must fit int32, as in the reference)");
     if (p->row_stride < 1 || p->row_offset < 0) return fail(BDPT_ERR_INVALID, "bad row shard");
     if (path->emitter_samples < 0 || path->bsdf_samples < 0) return fail(BDPT_ERR_INVALID, "negative sample counts");
+    if (int wrc = check_window(p, w)) return wrc;
     // the recursion depth the settings allow: maxDepth levels, or Russian roulette
     const bool rr = path->is_explicit && path->max_depth == -1;
     const int levels = rr ? kPtMaxLevels : std::max(path->max_depth, 0) + 2;
@@ -1079,7 +1108,7 @@ int bdpt_render_path(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_pa
     int rc;
     if ((rc = pt_frame_tables(c)) || (rc = ensure_pt(c, levels))) return rc;
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    const dev::DevFrame fr = make_frame(p);
+    const dev::DevFrame fr = make_frame(p, w);
     int32_t settings[8] = {path->is_explicit ? 1 : 0, path->max_depth, path->rr_depth, 0, path->emitter_samples,
                            path->bsdf_samples, levels, 0};
     std::memcpy(&settings[3], &path->rr_prob, 4);
@@ -1100,7 +1129,13 @@ int bdpt_render_path(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_pa
     return BDPT_OK;
 }
 
-int bdpt_render_path_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_params* path, float* fb_host) {
+int bdpt_render_path(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_params* path, float* fb,
+                     void* hip_stream) {
+    return render_path(c, p, nullptr, path, fb, hip_stream);
+}
+
+static int render_path_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                            const bdpt_path_params* path, float* fb_host) {
     if (!c || !fb_host || !p) return fail(BDPT_ERR_INVALID, "null argument");
     if (p->width <= 0 || p->height <= 0) return fail(BDPT_ERR_INVALID, "width/height must be > 0");
     HIP_TRY(hipSetDevice(c->device));
@@ -1108,7 +1143,7 @@ int bdpt_render_path_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_pa
     int rc;
     if ((rc = ensure_tmp_fb(c, n))) return rc;
     HIP_TRY(hipMemcpyAsync(c->tmp_fb, fb_host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if ((rc = bdpt_render_path(c, p, path, c->tmp_fb, c->stream))) return rc;
+    if ((rc = render_path(c, p, w, path, c->tmp_fb, c->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(fb_host, c->tmp_fb, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     bdpt_stats st;
@@ -1118,9 +1153,13 @@ int bdpt_render_path_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_pa
     return BDPT_OK;
 }
 
+int bdpt_render_path_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_params* path, float* fb_host) {
+    return render_path_host(c, p, nullptr, path, fb_host);
+}
+
 // DirectIntegrator (direct.h) on the path tracer's kernel: one level, no recursion.
-int bdpt_render_direct(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_direct_params* d, float* fb,
-                       void* hip_stream) {
+static int render_direct(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                         const bdpt_direct_params* d, float* fb, void* hip_stream) {
     if (!c || !fb || !d) return fail(BDPT_ERR_INVALID, "null argument");
     if (int trc = textured_unsupported(c, "the direct integrator (texture + bdpt_render_direct)")) return trc;
     if (!p) return fail(BDPT_ERR_INVALID, "null params");
@@ -1131,11 +1170,12 @@ int bdpt_render_direct(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_direc
     if (d->sampling_strategy < BDPT_DIRECT_AREA || d->sampling_strategy > BDPT_DIRECT_MIS)
         return fail(BDPT_ERR_INVALID, "Error: wrong strategy");  // direct.h:460
     if (d->emitter_samples < 0 || d->bsdf_samples < 0) return fail(BDPT_ERR_INVALID, "negative sample counts");
+    if (int wrc = check_window(p, w)) return wrc;
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = pt_frame_tables(c)) || (rc = ensure_pt(c, 1))) return rc;
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    const dev::DevFrame fr = make_frame(p);
+    const dev::DevFrame fr = make_frame(p, w);
     const int32_t settings[8] = {1, -1, 0, 0, d->emitter_samples, d->bsdf_samples, 1, d->sampling_strategy};
     if ((rc = begin_use(c, st))) return rc;
     HIP_TRY(hipMemsetAsync(c->work, 0, sizeof(unsigned long long), st));
@@ -1154,7 +1194,13 @@ int bdpt_render_direct(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_direc
     return BDPT_OK;
 }
 
-int bdpt_render_direct_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_direct_params* d, float* fb_host) {
+int bdpt_render_direct(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_direct_params* d, float* fb,
+                       void* hip_stream) {
+    return render_direct(c, p, nullptr, d, fb, hip_stream);
+}
+
+static int render_direct_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                              const bdpt_direct_params* d, float* fb_host) {
     if (!c || !fb_host || !p) return fail(BDPT_ERR_INVALID, "null argument");
     if (p->width <= 0 || p->height <= 0) return fail(BDPT_ERR_INVALID, "width/height must be > 0");
     HIP_TRY(hipSetDevice(c->device));
@@ -1162,10 +1208,14 @@ int bdpt_render_direct_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_
     int rc;
     if ((rc = ensure_tmp_fb(c, n))) return rc;
     HIP_TRY(hipMemcpyAsync(c->tmp_fb, fb_host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if ((rc = bdpt_render_direct(c, p, d, c->tmp_fb, c->stream))) return rc;
+    if ((rc = render_direct(c, p, w, d, c->tmp_fb, c->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(fb_host, c->tmp_fb, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BDPT_OK;
+}
+
+int bdpt_render_direct_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_direct_params* d, float* fb_host) {
+    return render_direct_host(c, p, nullptr, d, fb_host);
 }
 
 static int ensure_sample_buffers(bdpt_ctx* c, int32_t splat_cap) {
@@ -1404,15 +1454,16 @@ static int ensure_tmp_fb(bdpt_ctx* c, size_t floats) {
     return BDPT_OK;
 }
 
-int bdpt_render_host(bdpt_ctx* c, const bdpt_frame_params* p, float* fb_host) {
+static int render_bdpt_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* fb_host) {
     if (!c || !fb_host) return fail(BDPT_ERR_INVALID, "null argument");
     int rc = check_params(p);
     if (rc) return rc;
+    if ((rc = check_window(p, w))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = static_cast<size_t>(p->width) * p->height * 3;
     if ((rc = ensure_tmp_fb(c, n))) return rc;
     HIP_TRY(hipMemcpyAsync(c->tmp_fb, fb_host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if ((rc = bdpt_render(c, p, c->tmp_fb, c->stream))) return rc;
+    if ((rc = render_bdpt(c, p, w, c->tmp_fb, c->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(fb_host, c->tmp_fb, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     {
@@ -1428,6 +1479,31 @@ int bdpt_render_host(bdpt_ctx* c, const bdpt_frame_params* p, float* fb_host) {
                                                   "bounce guard); the image is not the reference's");
     }
     return BDPT_OK;
+}
+
+int bdpt_render_host(bdpt_ctx* c, const bdpt_frame_params* p, float* fb_host) {
+    return render_bdpt_host(c, p, nullptr, fb_host);
+}
+
+// Sample windows: the three integrators' frame entries with a window (null: the whole
+// range, then exactly the unwindowed entry).
+static int window_integrator(const bdpt_path_params* path, const bdpt_direct_params* direct) {
+    if (path && direct) return fail(BDPT_ERR_INVALID, "bdpt_render_window: path and direct are both set (at most one)");
+    return BDPT_OK;
+}
+int bdpt_render_window(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                       const bdpt_path_params* path, const bdpt_direct_params* direct, float* fb, void* hip_stream) {
+    if (int rc = window_integrator(path, direct)) return rc;
+    if (path) return render_path(c, p, w, path, fb, hip_stream);
+    if (direct) return render_direct(c, p, w, direct, fb, hip_stream);
+    return render_bdpt(c, p, w, fb, hip_stream);
+}
+int bdpt_render_window_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                            const bdpt_path_params* path, const bdpt_direct_params* direct, float* fb_host) {
+    if (int rc = window_integrator(path, direct)) return rc;
+    if (path) return render_path_host(c, p, w, path, fb_host);
+    if (direct) return render_direct_host(c, p, w, direct, fb_host);
+    return render_bdpt_host(c, p, w, fb_host);
 }
 
 static int render_bdpt_sample(bdpt_ctx* c, const bdpt_frame_params* p, const float ray[8], uint32_t* state,

@@ -177,7 +177,7 @@ struct DevFrame {
     uint32_t seed_base;
     int32_t row_offset, row_stride, nrows;
     uint32_t flags;
-    uint64_t total_samples;  // nrows * W * spp
+    uint64_t total_samples;  // nrows * W * win_count
     int32_t rr_mode;    // 1: NO_RR = 0 (Russian roulette past rr_depth; the bdpt_kernels_rr.hip build)
     int32_t depth_cap;  // subpath depth bound: rr_depth under NO_RR; with RR a guard (2^25 bounces)
     int32_t lv_max;     // light vertices a lane slot stores: rr_depth - 1 under NO_RR, more with RR
@@ -215,6 +215,10 @@ struct DevFrame {
     // counting pass, the queries issued per local row (null otherwise)
     const int32_t* row_order;
     unsigned long long* row_cost;
+    // sample window (bdpt_render_window): of each pixel's spp samples only k = win_first +
+    // i * win_stride, 0 <= i < win_count, are rendered (the whole frame: 0, 1, spp); seeds,
+    // inv_spp and camera_dir's spp == 1 rule keep the frame's full spp
+    int32_t win_first, win_stride, win_count;
 };
 enum : uint32_t { kParkOn = 1u, kParkResume = 2u };
 enum : uint32_t { kSchedNoCoopGroups = 1u };

@@ -619,10 +619,11 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                 int px;
                 chunk_x397 = mt_x397(sample_seed(base + (opaque_tid() & 63), P->fr, px));
 #if BDPT_EYE_SLOTS
-                // the chunk's pixel when all 64 samples share one (spp a multiple of 64)
+                // the chunk's pixel when all 64 samples share one (the rendered samples per
+                // pixel, the window's count, a multiple of 64; spp alone does not say so)
                 const int cpx = lane_val(px, 0);
                 if (lane0())
-                    eye_slot_reset(P->fb, static_cast<int>(chunk_seq % BDPT_EYE_SLOTS), P->fr.spp % 64 == 0 ? cpx : -1);
+                    eye_slot_reset(P->fb, static_cast<int>(chunk_seq % BDPT_EYE_SLOTS), P->fr.win_count % 64 == 0 ? cpx : -1);
                 chunk_seq++;
 #endif
             }

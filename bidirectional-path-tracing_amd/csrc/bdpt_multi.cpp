@@ -8,6 +8,11 @@
 // ncclCommInitAll) is the path's only exchange. The launches are asynchronous,
 // so all devices render concurrently from a single host thread.
 //
+// bdpt_multi_set_sharding(BDPT_SHARD_SAMPLES) splits the frame by samples instead:
+// device i renders the whole image's samples k = i, i + N, ... of every pixel (a
+// sample window, bdpt_render_window), so every device does statistically the same
+// work whatever the rows cost; the buffers and the reduce are the same.
+//
 // RCCL is resolved at first use with dlopen (librccl.so.1 of the ROCm image):
 // processes that never render on several devices do not load it. A device list
 // that names one device more than once (a single-GPU rehearsal of the
@@ -100,6 +105,7 @@ struct bdpt_multi {
     size_t fb_floats = 0;
     hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;  // root device: render start, renders done, reduce done
     bdpt_multi_stats stats{};
+    int32_t sharding = BDPT_SHARD_ROWS;  // bdpt_multi_set_sharding
 };
 
 static int multi_buffers(bdpt_multi* m, size_t n) {
@@ -221,13 +227,20 @@ int bdpt_multi_render_host(bdpt_multi* m, const bdpt_frame_params* params, const
         MHIP(hipSetDevice(m->devices[i]));
         MHIP(hipMemsetAsync(m->fb[i], 0, n * sizeof(float), m->stream[i]));
     }
-    for (int i = 0; i < N; i++) {  // bdpt::dist.row_shard: device i renders rows i, i + N, ...
+    for (int i = 0; i < N; i++) {
         bdpt_frame_params p = *params;
-        p.row_offset = i;
-        p.row_stride = N;
-        if (path) rc = bdpt_render_path(m->ctx[i], &p, path, m->fb[i], m->stream[i]);
-        else if (direct) rc = bdpt_render_direct(m->ctx[i], &p, direct, m->fb[i], m->stream[i]);
-        else rc = bdpt_render(m->ctx[i], &p, m->fb[i], m->stream[i]);
+        if (m->sharding == BDPT_SHARD_SAMPLES) {
+            // bdpt_dist.sample_shard: device i renders samples i, i + N, ... of every pixel
+            // (none when spp <= i: nothing is launched, its zeroed frame joins the reduce)
+            const bdpt_sample_window w = {i, N, params->spp > i ? (params->spp - i + N - 1) / N : 0};
+            rc = bdpt_render_window(m->ctx[i], &p, &w, path, direct, m->fb[i], m->stream[i]);
+        } else {  // bdpt_dist.row_shard: device i renders rows i, i + N, ...
+            p.row_offset = i;
+            p.row_stride = N;
+            if (path) rc = bdpt_render_path(m->ctx[i], &p, path, m->fb[i], m->stream[i]);
+            else if (direct) rc = bdpt_render_direct(m->ctx[i], &p, direct, m->fb[i], m->stream[i]);
+            else rc = bdpt_render(m->ctx[i], &p, m->fb[i], m->stream[i]);
+        }
         if (rc) return rc;
     }
     // renders done on every device: the root's t1 waits for the others' streams
@@ -298,6 +311,14 @@ int bdpt_multi_render_host(bdpt_multi* m, const bdpt_frame_params* params, const
         return bdpt::set_error(BDPT_ERR_UNSUPPORTED, std::to_string(m->stats.capped_samples) +
                                                          " samples met the Russian-roulette bounds (light-vertex store / "
                                                          "bounce guard); the image is not the reference's");
+    return BDPT_OK;
+}
+
+int bdpt_multi_set_sharding(bdpt_multi* m, int32_t mode) {
+    if (!m) return bdpt::set_error(BDPT_ERR_INVALID, "null argument");
+    if (mode != BDPT_SHARD_ROWS && mode != BDPT_SHARD_SAMPLES)
+        return bdpt::set_error(BDPT_ERR_INVALID, "bdpt_multi_set_sharding: mode must be BDPT_SHARD_ROWS or BDPT_SHARD_SAMPLES");
+    m->sharding = mode;
     return BDPT_OK;
 }
 

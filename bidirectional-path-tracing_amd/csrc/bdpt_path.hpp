@@ -311,7 +311,8 @@ __device__ __forceinline__ void splat_add(float* __restrict__ fb, int pixel, f3 
 #endif
 }
 
-// Eye-estimate sums per wave (frame kernels). With spp a multiple of 64 the
+// Eye-estimate sums per wave (frame kernels). With the samples rendered per pixel
+// (spp; of a sample window its count, DevFrame::win_count) a multiple of 64 the
 // megakernel's 64-sample refill chunks each cover ONE pixel, and the samples a
 // wave runs at a time come from its few most recent chunks. Each wave keeps a
 // sum (x, y, z, pixel bits in w) for each of its last BDPT_EYE_SLOTS chunks in
@@ -1002,13 +1003,16 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
 #endif
 
 // Pixel and Sampler seed of sample `s` of the shard: seed_base + p * spp + k
-// (the per-(pixel, sample) convention of SURVEY §8c on renderer.cpp:155).
+// (the per-(pixel, sample) convention of SURVEY §8c on renderer.cpp:155). The shard's
+// work index runs over W * win_count samples per row; the i-th of a pixel is the frame's
+// sample k = win_first + i * win_stride (the whole frame: k = i), seeded with the full spp.
 __device__ __forceinline__ uint32_t sample_seed(uint64_t s, const DevFrame& fr, int& pixel) {
-    const uint64_t per_row = static_cast<uint64_t>(fr.W) * fr.spp;
+    const uint64_t per_row = static_cast<uint64_t>(fr.W) * fr.win_count;
     uint64_t lr = s / per_row;
     const uint64_t q = s % per_row;
     if (fr.row_order) lr = static_cast<uint64_t>(((const gbl_i32*)fr.row_order)[lr]);  // bdpt_set_row_order
-    const int j = static_cast<int>(q / fr.spp), k = static_cast<int>(q % fr.spp);
+    const int j = static_cast<int>(q / fr.win_count);
+    const int k = fr.win_first + static_cast<int>(q % fr.win_count) * fr.win_stride;
     const int row = fr.row_offset + static_cast<int>(lr) * fr.row_stride;
     pixel = row * fr.W + j;
     return fr.seed_base + static_cast<uint32_t>(pixel) * static_cast<uint32_t>(fr.spp) + static_cast<uint32_t>(k);

@@ -10,8 +10,14 @@
 // integrators and the realtime render passes are rejected with an error.
 // Optional overrides (not in the reference): --width W --height H --spp N
 // --rr D --device K --out FILE.exr --seed S, and --gpus N / --devices a,b,...
-// to render on several devices (row shards + one RCCL sum-reduce, bdpt_multi_*).
+// to render on several devices (row shards + one RCCL sum-reduce, bdpt_multi_*);
+// --shard samples|rows picks how those devices split the frame
+// (bdpt_multi_set_sharding), and --sample-window F:S:C renders only the samples
+// F, F + S, ... (C of them) of every pixel and writes that partial image
+// (bdpt_render_window_host; partial images of windows that partition the spp sum
+// to the frame). A malformed or out-of-range window is refused before any device is used.
 #include <chrono>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -37,12 +43,28 @@ std::string exr_path_of(const std::string& toml) {
     return toml.substr(0, dot) + ".exr";
 }
 
+// "F:S:C", three integers and nothing else.
+bool parse_window(const char* text, bdpt_sample_window* w) {
+    int32_t* const field[3] = {&w->first, &w->stride, &w->count};
+    const char* q = text;
+    for (int k = 0; k < 3; k++) {
+        char* end = nullptr;
+        const long v = std::strtol(q, &end, 10);
+        if (end == q || v < INT32_MIN || v > INT32_MAX) return false;
+        if (*end != (k < 2 ? ':' : '\0')) return false;
+        *field[k] = static_cast<int32_t>(v);
+        q = end + 1;
+    }
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Syntax: %s <scene.toml> [nogui] [--width W --height H --spp N --rr D --device K "
-                             "--out FILE.exr --seed S --gpus N --devices a,b,...]\n", argv[0]);
+                             "--out FILE.exr --seed S --gpus N --devices a,b,... --shard samples|rows "
+                             "--sample-window F:S:C]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string toml = argv[1];
@@ -50,6 +72,9 @@ int main(int argc, char** argv) {
     long long seed = -1;
     std::string out;
     std::vector<int32_t> devices;  // non-empty: the multi-device render
+    int32_t sharding = BDPT_SHARD_ROWS;
+    bool shard_given = false, windowed = false;
+    bdpt_sample_window window = {0, 1, 0};
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -67,7 +92,28 @@ int main(int argc, char** argv) {
         else if (a == "--device") device = std::atoi(next("--device"));
         else if (a == "--seed") seed = std::atoll(next("--seed"));
         else if (a == "--out") out = next("--out");
-        else if (a == "--gpus") {
+        else if (a == "--shard") {
+            const std::string v = next("--shard");
+            if (v != "samples" && v != "rows") {
+                std::fprintf(stderr, "--shard must be samples or rows, not %s\n", v.c_str());
+                return EXIT_FAILURE;
+            }
+            sharding = v == "samples" ? BDPT_SHARD_SAMPLES : BDPT_SHARD_ROWS;
+            shard_given = true;
+        } else if (a == "--sample-window") {
+            const char* v = next("--sample-window");
+            if (!parse_window(v, &window)) {
+                std::fprintf(stderr, "--sample-window %s: expected first:stride:count (three integers)\n", v);
+                return EXIT_FAILURE;
+            }
+            if (window.first < 0 || window.stride < 1 || window.count < 0) {
+                std::fprintf(stderr, "--sample-window %s: %s\n", v,
+                             window.first < 0 ? "first must be >= 0"
+                                              : window.stride < 1 ? "stride must be >= 1" : "count must be >= 0");
+                return EXIT_FAILURE;
+            }
+            windowed = true;
+        } else if (a == "--gpus") {
             const int n = std::atoi(next("--gpus"));
             devices.clear();
             for (int k = 0; k < n; k++) devices.push_back(k);
@@ -83,6 +129,14 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
             return EXIT_FAILURE;
         }
+    }
+    if (windowed && !devices.empty()) {
+        std::fprintf(stderr, "--sample-window renders on one device (--gpus / --devices split the frame themselves)\n");
+        return EXIT_FAILURE;
+    }
+    if (shard_given && devices.empty()) {
+        std::fprintf(stderr, "--shard applies to a multi-device render (--gpus N / --devices a,b,...)\n");
+        return EXIT_FAILURE;
     }
 
     bdpt_config cfg;
@@ -105,6 +159,12 @@ int main(int argc, char** argv) {
     if (H > 0) cfg.height = H;
     if (spp > 0) cfg.spp = spp;
     if (rr > 0) cfg.rr_depth = rr;
+    if (windowed && window.count > 0 &&
+        static_cast<long long>(window.first) + static_cast<long long>(window.count - 1) * window.stride >= cfg.spp) {
+        std::fprintf(stderr, "--sample-window %d:%d:%d: count reaches past spp = %d\n", window.first, window.stride,
+                     window.count, cfg.spp);
+        return EXIT_FAILURE;
+    }
 
     bdpt_scene* scene = nullptr;
     if (bdpt_scene_load_obj(cfg.obj_file, &scene) != BDPT_OK) return die("Scene::load");
@@ -113,6 +173,7 @@ int main(int argc, char** argv) {
     if (!devices.empty()) {
         if (bdpt_multi_create(scene, static_cast<int32_t>(devices.size()), devices.data(), &multi) != BDPT_OK)
             return die("bdpt_multi_create");
+        if (bdpt_multi_set_sharding(multi, sharding) != BDPT_OK) return die("bdpt_multi_set_sharding");
     } else if (bdpt_ctx_create(scene, device, &ctx) != BDPT_OK) {
         return die("bdpt_ctx_create");
     }
@@ -130,17 +191,18 @@ int main(int argc, char** argv) {
     p.row_stride = 1;
     std::vector<float> rgb(static_cast<size_t>(cfg.width) * cfg.height * 3, 0.f);  // Integrator::init: rgb->clear()
 
+    const bdpt_sample_window* const win = windowed ? &window : nullptr;  // null: every sample
     const auto t0 = std::chrono::high_resolution_clock::now();
     if (path) {
         if (rr > 0) cfg.path.rr_depth = rr;
         p.rr_depth = 1;  // unused by the path tracer
         const int rc = multi ? bdpt_multi_render_host(multi, &p, &cfg.path, nullptr, rgb.data())
-                             : bdpt_render_path_host(ctx, &p, &cfg.path, rgb.data());
+                             : bdpt_render_window_host(ctx, &p, win, &cfg.path, nullptr, rgb.data());
         if (rc != BDPT_OK) return die("render (path)");
     } else if (direct) {
         p.rr_depth = 1;  // unused by the direct integrator
         const int rc = multi ? bdpt_multi_render_host(multi, &p, nullptr, &cfg.direct, rgb.data())
-                             : bdpt_render_direct_host(ctx, &p, &cfg.direct, rgb.data());
+                             : bdpt_render_window_host(ctx, &p, win, nullptr, &cfg.direct, rgb.data());
         if (rc != BDPT_OK) {
             if (cfg.direct.sampling_strategy == 0) {  // direct.h:460-461
                 std::printf("Error: wrong strategy\n");
@@ -149,7 +211,7 @@ int main(int argc, char** argv) {
             return die("render (direct)");
         }
     } else if ((multi ? bdpt_multi_render_host(multi, &p, nullptr, nullptr, rgb.data())
-                      : bdpt_render_host(ctx, &p, rgb.data())) != BDPT_OK) {
+                      : bdpt_render_window_host(ctx, &p, win, nullptr, nullptr, rgb.data())) != BDPT_OK) {
         return die("render (bdpt)");
     }
     const auto t1 = std::chrono::high_resolution_clock::now();

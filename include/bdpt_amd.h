@@ -36,6 +36,9 @@
  *                            integrator, TOML type = "path"), on the same GPU substrate
  *   bdpt_render_direct       DirectIntegrator::render         src/integrators/direct.h:449-462 (TOML
  *                            type = "direct": area / solidAngle / cosineHemisphere / bsdf / mis)
+ *   bdpt_render_window       a part of the offline loop's inner sample loop (renderer.cpp:160, the
+ *                            samples k = first + i * stride of every pixel) for any of the three
+ *                            integrators: progressive, resumable and sample-sharded frames
  *
  * Conventions: plain C types only; status 0 = OK, < 0 = error (message from
  * bdpt_last_error(), thread-local). A context is bound to one HIP device and is
@@ -342,6 +345,20 @@ int bdpt_set_row_order(bdpt_ctx* ctx, const int32_t* order, int32_t n);
  * n differs from that shard's row count. Synchronous. */
 int bdpt_get_row_costs(bdpt_ctx* ctx, int64_t* costs, int32_t n);
 
+/* ---- sample windows: progressive, resumable, sample-sharded frames ---- */
+/* Of each pixel's spp samples, the samples k = first + i * stride, 0 <= i < count. Valid iff
+ * first >= 0, stride >= 1, count >= 0 and (count == 0 or first + (count - 1) * stride < spp);
+ * anything else is BDPT_ERR_INVALID with a message naming the field. A window changes which
+ * samples run and nothing about a sample: sample k of pixel p keeps its seed seed_base +
+ * p * spp + k and its weight 1 / spp of the frame's FULL spp (and the spp == 1 no-jitter rule
+ * looks at the full spp). So windows that partition [0, spp) - contiguous batches, or the
+ * residues modulo N - add up to the frame the unwindowed entry renders, up to the order of the
+ * float additions, exactly as row shards do; they combine with row shards, bdpt_set_row_order
+ * (the row count is unchanged) and BDPT_FLAG_COUNT. */
+typedef struct {
+    int32_t first, stride, count;
+} bdpt_sample_window;
+
 /* ---- the reference's path tracer on the same substrate (src/integrators/path.h) ---- */
 typedef struct {
     int32_t is_explicit;     /* [renderer] isExplicit (default true): renderExplicit / renderImplicit */
@@ -402,6 +419,19 @@ int bdpt_render_direct_sample(bdpt_ctx* ctx, const bdpt_frame_params* params, co
 /* samplingStrategy string -> BDPT_DIRECT_* (0 when unknown). */
 int32_t bdpt_direct_strategy(const char* name);
 
+/* (new) The window's samples of every pixel of the shard, ADDED to the framebuffer as the
+ * unwindowed entries add theirs. path / direct as in bdpt_multi_render_host: NULL / NULL is
+ * bdpt_render's integrator, else at most one is set (bdpt_render_path / bdpt_render_direct).
+ * window NULL = the whole range (exactly the unwindowed entry); count == 0 renders nothing and
+ * returns BDPT_OK. Every refusal of the unwindowed entries stands (textures + Russian roulette,
+ * HBM records + Russian roulette, ...), the device form is asynchronous and the host form
+ * synchronous like theirs, and bdpt_stats.samples is the window's sample count. */
+int bdpt_render_window(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                       const bdpt_path_params* path, const bdpt_direct_params* direct, float* fb_device,
+                       void* hip_stream);
+int bdpt_render_window_host(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                            const bdpt_path_params* path, const bdpt_direct_params* direct, float* fb_host);
+
 /* ---- several HIP devices in one process ---- */
 /* The reference fans the offline loop out over host threads (parallel_for,
  * src/core/parallelfor.h:25-65, renderer.cpp:157); here every device gets one
@@ -435,6 +465,16 @@ int bdpt_multi_destroy(bdpt_multi* multi);
 int bdpt_multi_render_host(bdpt_multi* multi, const bdpt_frame_params* params, const bdpt_path_params* path,
                            const bdpt_direct_params* direct, float* fb_host);
 int bdpt_multi_get_stats(bdpt_multi* multi, bdpt_multi_stats* out);
+/* (new) How bdpt_multi_render_host splits the frame over the N devices. BDPT_SHARD_ROWS (the
+ * default): device i renders rows i, i + N, ... BDPT_SHARD_SAMPLES: device i renders the whole
+ * image with the sample window (i, N, ceil((spp - i) / N)) (count 0 when spp <= i: nothing is
+ * launched there and its zero frame still joins the reduce). Rows differ in cost, samples of one
+ * pixel do not, so sample shards are balanced without a cost model; every device holds a
+ * full-frame buffer either way (camera splats land anywhere), so memory and the reduce are the
+ * same. Stats and the capped_samples / schedule_errors sums work alike in both modes. */
+#define BDPT_SHARD_ROWS 0
+#define BDPT_SHARD_SAMPLES 1
+int bdpt_multi_set_sharding(bdpt_multi* multi, int32_t mode);
 
 /* ---- the BSDF plugin contract and the path's building blocks, batched on the device ---- */
 /* All arrays are host arrays of n elements; directions are in the local shading
