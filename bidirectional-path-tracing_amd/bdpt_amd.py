@@ -11,6 +11,8 @@ Mirrors the reference's plugin surface for the BDPT path
     .render_frame(window=SampleWindow(first, stride, count)) / .render_progressive(batch)
                                        a part of that loop's samples per pixel (bdpt_render_window)
     .rgb                               Integrator::rgb      (W x H x 3 float32, accumulated)
+    .render_aov(...) / .aov            first-hit albedo, normal, depth, coverage (bdpt_render_aov; no counterpart)
+    .denoise(samples_done=...)         edge-avoiding a-trous filter of a low-spp frame (bdpt_denoise; no counterpart)
   Sampler(seed)                        Sampler              src/core/math.h:63-76 (seed + draw count)
   Ray(o, d, min_t, max_t)              Ray                  src/core/core.h:117-122
   load_toml(path) -> SceneConfig       loadTOML             src/main.cpp:22-116
@@ -79,6 +81,11 @@ class _PathParams(ctypes.Structure):  # bdpt_path_params
 
 class _SampleWindow(ctypes.Structure):  # bdpt_sample_window
     _fields_ = [("first", ctypes.c_int32), ("stride", ctypes.c_int32), ("count", ctypes.c_int32)]
+
+
+class _DenoiseParams(ctypes.Structure):  # bdpt_denoise_params
+    _fields_ = [("iterations", ctypes.c_int32), ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_depth", ctypes.c_float), ("demodulate", ctypes.c_int32), ("norm", ctypes.c_float)]
 
 
 class _DirectParams(ctypes.Structure):  # bdpt_direct_params
@@ -202,7 +209,7 @@ class _Stats(ctypes.Structure):
 
 # Sources that make up the frame kernels' code objects: their hash stamps the
 # profiles (PMC passes) so bench.py only reuses a measurement of the same kernel.
-KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
+KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
                   "csrc/powf_restated.inc", "csrc/bdpt_types.h", "Makefile")
 
 
@@ -286,6 +293,10 @@ def lib():
                                          ctypes.POINTER(_PathParams), ctypes.POINTER(_DirectParams), vp, vp]
         L.bdpt_render_window_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow),
                                               ctypes.POINTER(_PathParams), ctypes.POINTER(_DirectParams), vp]
+        L.bdpt_render_aov.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), vp, vp]
+        L.bdpt_render_aov_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), vp]
+        L.bdpt_denoise.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.POINTER(_DenoiseParams), vp]
+        L.bdpt_denoise_host.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.POINTER(_DenoiseParams)]
         L.bdpt_synchronize.argtypes = [vp]
         L.bdpt_config_load_toml.argtypes = [ctypes.c_char_p, ctypes.POINTER(_Config)]
         L.bdpt_render_path.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_PathParams), vp, vp]
@@ -366,6 +377,21 @@ class SampleWindow:
         if spp is not None and w.count > 0 and w.first + (w.count - 1) * w.stride >= spp:
             raise ValueError(f"sample window {text!r}: count reaches past spp = {spp}")
         return w
+
+
+@dataclass
+class DenoiseSettings:
+    """bdpt_denoise_params with the header's defaults (BDPT_DENOISE_*); norm is set per call
+    from the samples rendered so far."""
+    iterations: int = 5
+    sigma_color: float = 2.0
+    sigma_normal: float = 0.3
+    sigma_depth: float = 0.02
+    demodulate: bool = True
+
+    def c(self, norm: float = 1.0) -> _DenoiseParams:
+        return _DenoiseParams(int(self.iterations), float(self.sigma_color), float(self.sigma_normal),
+                              float(self.sigma_depth), int(self.demodulate), float(norm))
 
 
 @dataclass
@@ -714,6 +740,7 @@ class BDPTIntegrator:
         _check(lib().bdpt_ctx_create(scene._h, device, ctypes.byref(h)))
         self._h = h
         self.rgb = None
+        self.aov = None
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -725,6 +752,7 @@ class BDPTIntegrator:
 
     def init(self) -> bool:
         self.rgb = np.zeros((self.config.height, self.config.width, 3), np.float32)
+        self.aov = np.zeros((self.config.height, self.config.width, 8), np.float32)
         return True
 
     def params(self, row_offset: int = 0, row_stride: int = 1, flags: int = 0) -> _FrameParams:
@@ -862,7 +890,17 @@ class BDPTIntegrator:
         self.rgb * (spp / done_spp). Every contribution of a sample, light-path splats
         included, carries 1 / spp, so the preview is the unbiased estimate from the samples
         so far; the last item has done_spp == spp and the full frame (the same samples as
-        render_frame())."""
+        render_frame()).
+
+        Denoised previews (the feature buffers accumulate over the same windows; samples_done
+        gives the filter its norm = spp / done)::
+
+            done0 = 0
+            for done, _ in it.render_progressive(4):
+                it.render_aov(window=SampleWindow(done0, 1, done - done0))
+                show(it.denoise(samples_done=done))
+                done0 = done
+        """
         if batch < 1:
             raise ValueError("render_progressive: batch must be >= 1")
         spp = self.config.spp
@@ -873,6 +911,55 @@ class BDPTIntegrator:
             self.render_frame(window=SampleWindow(done, 1, n))
             done += n
             yield done, (self.rgb if done == spp else self.rgb * np.float32(spp / done))
+
+    def render_aov(self, row_offset: int = 0, row_stride: int = 1, window: SampleWindow | None = None) -> np.ndarray:
+        """bdpt_render_aov_host: the first-hit feature buffers of the (sharded, windowed) frame
+        ADDED to self.aov, (H, W, 8) = albedo rgb, shading normal xyz, t, coverage, each
+        weighted 1 / spp as render_frame weights self.rgb."""
+        if self.aov is None:
+            self.init()
+        p = self.params(row_offset, row_stride, 0)
+        w = window.c() if window is not None else None
+        _check(lib().bdpt_render_aov_host(self._h, ctypes.byref(p), w and ctypes.byref(w), self.aov.ctypes.data))
+        return self.aov
+
+    def render_aov_device(self, aov_ptr: int, stream_ptr: int = 0, row_offset: int = 0, row_stride: int = 1,
+                          window: SampleWindow | None = None) -> None:
+        """bdpt_render_aov: asynchronous, into a device buffer of W * H * 8 floats."""
+        p = self.params(row_offset, row_stride, 0)
+        w = window.c() if window is not None else None
+        _check(lib().bdpt_render_aov(self._h, ctypes.byref(p), w and ctypes.byref(w), ctypes.c_void_p(aov_ptr),
+                                     ctypes.c_void_p(stream_ptr)))
+
+    def denoise(self, rgb=None, aov=None, samples_done: int | None = None, **params) -> np.ndarray:
+        """bdpt_denoise_host of rgb (default self.rgb) guided by aov (default self.aov): a new
+        (H, W, 3) array. samples_done: the samples per pixel both hold so far (norm = spp /
+        samples_done; None = a full frame, norm 1). params: DenoiseSettings fields, or
+        settings=DenoiseSettings(...)."""
+        H, W = self.config.height, self.config.width
+        settings = params.pop("settings", None) or DenoiseSettings()
+        if params:
+            from dataclasses import replace
+            settings = replace(settings, **params)
+        if samples_done is not None and samples_done < 1:
+            raise ValueError("denoise: samples_done must be >= 1")
+        norm = 1.0 if samples_done is None else self.config.spp / samples_done
+        c = np.ascontiguousarray(self.rgb if rgb is None else rgb, np.float32)
+        a = np.ascontiguousarray(self.aov if aov is None else aov, np.float32)
+        if c.size != W * H * 3 or a.size != W * H * 8:
+            raise BdptError(f"denoise: rgb / aov have {c.size} / {a.size} floats, expected {W * H * 3} / {W * H * 8}")
+        out = np.zeros((H, W, 3), np.float32)
+        d = settings.c(norm)
+        _check(lib().bdpt_denoise_host(self._h, W, H, c.ctypes.data, a.ctypes.data, out.ctypes.data, ctypes.byref(d)))
+        return out
+
+    def denoise_device(self, rgb_ptr: int, aov_ptr: int, out_ptr: int, stream_ptr: int = 0, norm: float = 1.0,
+                       settings: "DenoiseSettings | None" = None) -> None:
+        """bdpt_denoise: asynchronous, on device buffers."""
+        d = (settings or DenoiseSettings()).c(norm)
+        _check(lib().bdpt_denoise(self._h, self.config.width, self.config.height, ctypes.c_void_p(rgb_ptr),
+                                  ctypes.c_void_p(aov_ptr), ctypes.c_void_p(out_ptr), ctypes.byref(d),
+                                  ctypes.c_void_p(stream_ptr)))
 
     def stats(self) -> dict:
         s = _Stats()

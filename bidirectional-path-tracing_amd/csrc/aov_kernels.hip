@@ -1,0 +1,212 @@
+// First-hit feature buffers and the edge-avoiding a-trous filter for preview frames
+// (DESIGN.md §11). Neither exists in the reference: the feature buffers are pinned to
+// what the frame kernels compute for a sample's primary query (camera_dir, the product
+// traversal, shade_hit and its texel lookup: the very functions, compiled here with
+// BDPT_TEXTURED 1 so one build serves scenes with and without maps), the filter to the
+// formulas of include/bdpt_amd.h.
+#define BDPT_TEXTURED 1
+#include <hip/hip_runtime.h>
+
+#include "bdpt_path.hpp"
+
+namespace bdpt {
+namespace dev {
+
+// ------------------------------------------------------------ feature buffers
+// One wave per 8 x 8 pixel tile of the shard (local rows x columns): the primary rays
+// of a tile are coherent, so its lanes walk the same nodes. A lane owns its pixel: the
+// window's samples accumulate in registers and are added to aov[pixel][0..8) once, with
+// a plain read-modify-write. Blocks stride over the tiles; a block's lanes keep the
+// traversal-stack overflow columns blockIdx.x * 64 + lane (< nslots) throughout.
+// mats: per material (Kd, mode) (Ks, 0) with mode 0 = albedo 1 (mirror, glass, the null
+// BSDF), 1 = Kd (diffuse), 2 = min(Kd + Ks, 1) (mixture, Phong) of the material as
+// ingested; read from HBM per hit (no LDS table, so no material-count limit).
+constexpr int kAovTile = 8;
+constexpr int kAovBlock = kAovTile * kAovTile;
+constexpr int kAovChannels = 8;
+
+__global__ __launch_bounds__(kAovBlock) void aov_kernel(DevScene sc, DevFrame fr, const float4* __restrict__ mats,
+                                                        float* __restrict__ aov, uint2* __restrict__ gstack,
+                                                        uint32_t nslots, int tiles_x, int ntiles) {
+    __shared__ uint2 stack_mem[kLdsStack * kAovBlock];
+    const uint32_t slot = blockIdx.x * kAovBlock + threadIdx.x;
+    const Stack stk{stack_mem + threadIdx.x, kAovBlock, kLdsStack, gstack, nslots, slot};
+    const int lx = static_cast<int>(threadIdx.x) % kAovTile, ly = static_cast<int>(threadIdx.x) / kAovTile;
+    const f3 eye = mk(fr.cam_o[0], fr.cam_o[1], fr.cam_o[2]);
+    for (int tile = static_cast<int>(blockIdx.x); tile < ntiles; tile += static_cast<int>(gridDim.x)) {
+        const int j = (tile % tiles_x) * kAovTile + lx, lr = (tile / tiles_x) * kAovTile + ly;
+        if (j >= fr.W || lr >= fr.nrows) continue;
+        const int pixel = (fr.row_offset + lr * fr.row_stride) * fr.W + j;
+        float acc[kAovChannels];
+#pragma unroll
+        for (int c = 0; c < kAovChannels; c++) acc[c] = 0.f;
+        for (int i = 0; i < fr.win_count; i++) {
+            const int k = fr.win_first + i * fr.win_stride;
+            LazyMT rng{};
+            // the jitter is the sample's first two draws, taken iff the frame's full spp > 1
+            if (fr.spp != 1)
+                mt_seed(rng, fr.seed_base + static_cast<uint32_t>(pixel) * static_cast<uint32_t>(fr.spp) +
+                                 static_cast<uint32_t>(k));
+            const Ray ray{eye, camera_dir(fr, pixel, rng), 1.f, 1000.f};  // start_sample's primary ray
+            Counts cnt;
+            float t = 0.f, u = 0.f, v = 0.f;
+            const int res = traverse<false, false>(sc, ray, false, stk, t, u, v, cnt, kCullNear);
+            if (!(res >= 0 && t <= ray.max_t && t >= ray.min_t)) continue;  // accel.h:133
+            Hit h;
+            shade_hit(sc, res, u, v, t, ray.d, h);
+            const float4 m0 = gld4(mats + 2 * static_cast<size_t>(h.mat)), m1 = gld4(mats + 2 * static_cast<size_t>(h.mat) + 1);
+            const int mode = __float_as_int(m0.w);
+            f3 alb = mk(1.f, 1.f, 1.f);
+            if (mode != 0) {
+                alb = h.tkd >= 0 ? xyz(gld4(sc.tex_tab + h.tkd)) : xyz(m0);
+                if (mode == 2) {
+                    const f3 ks = h.tks >= 0 ? xyz(gld4(sc.tex_tab + h.tks)) : xyz(m1);
+                    alb = mk(fminf(alb.x + ks.x, 1.f), fminf(alb.y + ks.y, 1.f), fminf(alb.z + ks.z, 1.f));
+                }
+            }
+            acc[0] += alb.x, acc[1] += alb.y, acc[2] += alb.z;
+            acc[3] += h.n.x, acc[4] += h.n.y, acc[5] += h.n.z;
+            acc[6] += t, acc[7] += 1.f;
+        }
+        float* o = aov + kAovChannels * static_cast<size_t>(pixel);
+#pragma unroll
+        for (int c = 0; c < kAovChannels; c++) gst1(o + c, gld1(o + c) + acc[c] * fr.inv_spp);
+    }
+}
+
+// --------------------------------------------------------------------- filter
+// One lane per pixel, 32 x 8 pixel blocks (a wave: two rows of 32). Guides are packed
+// once per call into two float4 per pixel — (albedo, z) and (N, coverage flag) — and the
+// colour ping-pongs between two float4 images, so a tap is three 16-byte cached loads.
+constexpr int kDnX = 32, kDnY = 8;
+
+// c = color * norm, a = aov * norm; guides and I_0 (bdpt_amd.h, bdpt_denoise).
+__global__ __launch_bounds__(kDnX* kDnY) void denoise_prepare_kernel(int W, int H, const float* __restrict__ color,
+                                                                     const float* __restrict__ aov, float norm,
+                                                                     int demodulate, float4* __restrict__ guide,
+                                                                     float4* __restrict__ img) {
+    const int x = blockIdx.x * kDnX + threadIdx.x, y = blockIdx.y * kDnY + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t p = static_cast<size_t>(y) * W + x;
+    float a[kAovChannels];
+#pragma unroll
+    for (int c = 0; c < kAovChannels; c++) a[c] = gld1(aov + kAovChannels * p + c) * norm;
+    const float cov = a[7];
+    f3 alb = mk(1.f, 1.f, 1.f), n = mk(0.f, 0.f, 0.f);
+    float z = 0.f;
+    if (cov > 0.f) {
+        alb = mk(a[0] / cov, a[1] / cov, a[2] / cov);
+        n = mk(a[3] / cov, a[4] / cov, a[5] / cov);
+        z = a[6] / cov;
+    }
+    f3 c = mk(gld1(color + 3 * p) * norm, gld1(color + 3 * p + 1) * norm, gld1(color + 3 * p + 2) * norm);
+    if (demodulate) c = mk(c.x / fmaxf(alb.x, 1e-3f), c.y / fmaxf(alb.y, 1e-3f), c.z / fmaxf(alb.z, 1e-3f));
+    gst4(guide + 2 * p, make_float4(alb.x, alb.y, alb.z, z));
+    gst4(guide + 2 * p + 1, make_float4(n.x, n.y, n.z, cov > 0.f ? 1.f : 0.f));
+    gst4(img + p, make_float4(c.x, c.y, c.z, 0.f));
+}
+
+// iterations == 0: out = color * norm.
+__global__ __launch_bounds__(256) void denoise_scale_kernel(size_t n, const float* __restrict__ color, float norm,
+                                                            float* __restrict__ out) {
+    const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i < n) gst1(out + i, gld1(color + i) * norm);
+}
+
+// One a-trous iteration with step s: 5 x 5 taps at p + s (dx, dy), dy outer and dx inner
+// (a fixed summation order and no atomics: two runs give the same bits). inv_c / inv_n /
+// inv_z2 = 1 / (sigma_color 2^-i)^2, 1 / sigma_normal^2, 1 / sigma_depth^2. LAST: the
+// result goes to out (3 floats per pixel), multiplied back by max(albedo, 1e-3) when
+// demodulated.
+template <bool LAST>
+__global__ __launch_bounds__(kDnX* kDnY) void denoise_iter_kernel(int W, int H, int s, float inv_c, float inv_n,
+                                                                  float sigma_z, int demodulate,
+                                                                  const float4* __restrict__ guide,
+                                                                  const float4* __restrict__ src,
+                                                                  float4* __restrict__ dst, float* __restrict__ out) {
+    const int x = blockIdx.x * kDnX + threadIdx.x, y = blockIdx.y * kDnY + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t p = static_cast<size_t>(y) * W + x;
+    const float4 ip = gld4(src + p), g0 = gld4(guide + 2 * p), g1 = gld4(guide + 2 * p + 1);
+    const float zs = sigma_z * fmaxf(g0.w, 1e-6f);
+    const float inv_z = 1.f / (zs * zs);
+    float sr = 0.f, sg = 0.f, sb = 0.f, sw = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + dy * s;
+        if (qy < 0 || qy >= H) continue;
+        const float hy = (dy == 0 ? 6.f : (dy == -1 || dy == 1 ? 4.f : 1.f)) * 0.0625f;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + dx * s;
+            if (qx < 0 || qx >= W) continue;
+            const float hx = (dx == 0 ? 6.f : (dx == -1 || dx == 1 ? 4.f : 1.f)) * 0.0625f;
+            const size_t q = static_cast<size_t>(qy) * W + qx;
+            const float4 iq = gld4(src + q);
+            float w = 1.f;
+            if (dx != 0 || dy != 0) {
+                const float4 h0 = gld4(guide + 2 * q), h1 = gld4(guide + 2 * q + 1);
+                const float cr = ip.x - iq.x, cg = ip.y - iq.y, cb = ip.z - iq.z;
+                const float nx = g1.x - h1.x, ny = g1.y - h1.y, nz = g1.z - h1.z;
+                const float dz = g0.w - h0.w;
+                const float wc = expf(-fminf(((cr * cr + cg * cg) + cb * cb) * inv_c, 80.f));
+                const float wn = expf(-fminf(((nx * nx + ny * ny) + nz * nz) * inv_n, 80.f));
+                const float wz = expf(-fminf((dz * dz) * inv_z, 80.f));
+                w = g1.w == h1.w ? (wc * wn) * wz : 0.f;
+            }
+            const float hw = (hy * hx) * w;
+            sr += hw * iq.x, sg += hw * iq.y, sb += hw * iq.z, sw += hw;
+        }
+    }
+    float r = sr / sw, g = sg / sw, b = sb / sw;
+    if (LAST) {
+        if (demodulate) r *= fmaxf(g0.x, 1e-3f), g *= fmaxf(g0.y, 1e-3f), b *= fmaxf(g0.z, 1e-3f);
+        gst1(out + 3 * p, r), gst1(out + 3 * p + 1, g), gst1(out + 3 * p + 2, b);
+    } else {
+        gst4(dst + p, make_float4(r, g, b, 0.f));
+    }
+}
+
+}  // namespace dev
+
+// tiles of the shard; the grid never exceeds the lane slots the overflow columns serve
+hipError_t launch_aov(const dev::DevScene& sc, const dev::DevFrame& fr, const void* mats, float* aov, uint2* gstack,
+                      uint32_t nslots, hipStream_t st) {
+    const int tiles_x = (fr.W + dev::kAovTile - 1) / dev::kAovTile, tiles_y = (fr.nrows + dev::kAovTile - 1) / dev::kAovTile;
+    const int64_t ntiles = static_cast<int64_t>(tiles_x) * tiles_y;
+    const int64_t max_grid = nslots / dev::kAovBlock;
+    if (ntiles <= 0 || fr.win_count <= 0) return hipSuccess;
+    if (max_grid < 1 || ntiles > 0x7fffffff) return hipErrorInvalidValue;
+    const unsigned grid = static_cast<unsigned>(ntiles < max_grid ? ntiles : max_grid);
+    hipLaunchKernelGGL(dev::aov_kernel, dim3(grid), dim3(dev::kAovBlock), 0, st, sc, fr,
+                       static_cast<const float4*>(mats), aov, gstack, nslots, tiles_x, static_cast<int>(ntiles));
+    return hipGetLastError();
+}
+
+static dim3 dn_grid(int W, int H) { return dim3((W + dev::kDnX - 1) / dev::kDnX, (H + dev::kDnY - 1) / dev::kDnY); }
+
+hipError_t launch_denoise_prepare(int W, int H, const float* color, const float* aov, float norm, int demodulate,
+                                  void* guide, void* img, hipStream_t st) {
+    hipLaunchKernelGGL(dev::denoise_prepare_kernel, dn_grid(W, H), dim3(dev::kDnX, dev::kDnY), 0, st, W, H, color, aov,
+                       norm, demodulate, static_cast<float4*>(guide), static_cast<float4*>(img));
+    return hipGetLastError();
+}
+hipError_t launch_denoise_scale(size_t n, const float* color, float norm, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(dev::denoise_scale_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, n,
+                       color, norm, out);
+    return hipGetLastError();
+}
+hipError_t launch_denoise_iter(int W, int H, int step, float inv_c, float inv_n, float sigma_z, int demodulate,
+                               const void* guide, const void* src, void* dst, float* out, bool last, hipStream_t st) {
+    if (last)
+        hipLaunchKernelGGL(dev::denoise_iter_kernel<true>, dn_grid(W, H), dim3(dev::kDnX, dev::kDnY), 0, st, W, H, step,
+                           inv_c, inv_n, sigma_z, demodulate, static_cast<const float4*>(guide),
+                           static_cast<const float4*>(src), static_cast<float4*>(dst), out);
+    else
+        hipLaunchKernelGGL(dev::denoise_iter_kernel<false>, dn_grid(W, H), dim3(dev::kDnX, dev::kDnY), 0, st, W, H,
+                           step, inv_c, inv_n, sigma_z, demodulate, static_cast<const float4*>(guide),
+                           static_cast<const float4*>(src), static_cast<float4*>(dst), out);
+    return hipGetLastError();
+}
+
+}  // namespace bdpt

@@ -89,6 +89,14 @@ hipError_t launch_pt(const dev::DevScene& sc, const dev::DevFrame& fr, const int
 int frame_kernel_block();
 int light_vertex_fields();
 hipError_t launch_math_check(int32_t fn, const float* x, const float* y, float* out, int64_t n, hipStream_t st);
+// aov_kernels.hip: first-hit feature buffers and the a-trous filter
+hipError_t launch_aov(const dev::DevScene& sc, const dev::DevFrame& fr, const void* mats, float* aov, uint2* gstack,
+                      uint32_t nslots, hipStream_t st);
+hipError_t launch_denoise_prepare(int W, int H, const float* color, const float* aov, float norm, int demodulate,
+                                  void* guide, void* img, hipStream_t st);
+hipError_t launch_denoise_scale(size_t n, const float* color, float norm, float* out, hipStream_t st);
+hipError_t launch_denoise_iter(int W, int H, int step, float inv_c, float inv_n, float sigma_z, int demodulate,
+                               const void* guide, const void* src, void* dst, float* out, bool last, hipStream_t st);
 }  // namespace bdpt
 
 using namespace bdpt;
@@ -257,6 +265,15 @@ struct bdpt_ctx {
     hipEvent_t last_use = nullptr;
     hipStream_t last_stream = nullptr;
     bool used = false;
+    // feature buffers (bdpt_render_aov): per material (Kd, albedo mode) (Ks, 0) of the records as
+    // ingested, and for a scene without maps a table of "no map" records for shade_hit's lookup
+    void* aov_mats = nullptr;
+    void* aov_no_tex = nullptr;
+    // filter (bdpt_denoise): packed guides (2 float4 per pixel) and the ping-pong images (float4
+    // per pixel each), allocated at first use and grown when a larger frame comes
+    void* dn_guide = nullptr;
+    void* dn_img[2] = {nullptr, nullptr};
+    size_t dn_pixels = 0;
     // stats of the last render
     bool pending_timing = false;
     bdpt_stats stats{};
@@ -571,7 +588,8 @@ int bdpt_ctx_destroy(bdpt_ctx* c) {
                     static_cast<void*>(c->mt_ring), static_cast<void*>(c->mt_state), static_cast<void*>(c->capped),
                     static_cast<void*>(c->diag),
                     static_cast<void*>(c->splat_list), static_cast<void*>(c->park), static_cast<void*>(c->tasks),
-                    static_cast<void*>(c->row_order), static_cast<void*>(c->row_cost)})
+                    static_cast<void*>(c->row_order), static_cast<void*>(c->row_cost), c->aov_mats, c->aov_no_tex,
+                    c->dn_guide, c->dn_img[0], c->dn_img[1]})
         if (p) (void)hipFree(p);
     if (c->last_use) (void)hipEventDestroy(c->last_use);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -650,6 +668,25 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
         c->sc.tex_tab = static_cast<const float4*>(p);
         c->textured = true;
         for (size_t m = 0; m < L.bsdfs.size(); m++) c->mat_textured.push_back(L.mat_tex[2 * m] >= 0 || L.mat_tex[2 * m + 1] >= 0);
+    }
+    {  // bdpt_render_aov's albedo table, from the records as ingested (bdpt_bsdf_type's kinds)
+        std::vector<float4_t> mats(2 * std::max<size_t>(L.bsdfs.size(), 1), float4_t{0.f, 0.f, 0.f, 0.f});
+        std::vector<float4_t> no_tex(mats.size());
+        for (size_t m = 0; m < L.bsdfs.size(); m++) {
+            const BsdfRecord& b = L.bsdfs[m];
+            const int32_t mode = b.kind == BSDF_DIFFUSE ? 1 : (b.kind == BSDF_MIXTURE || b.kind == BSDF_PHONG ? 2 : 0);
+            float fmode;
+            std::memcpy(&fmode, &mode, 4);
+            mats[2 * m] = float4_t{b.kd[0], b.kd[1], b.kd[2], fmode};
+            mats[2 * m + 1] = float4_t{b.ks[0], b.ks[1], b.ks[2], 0.f};
+        }
+        std::memset(no_tex.data(), 0xff, no_tex.size() * sizeof(float4_t));  // first texel -1: no map
+        HIP_TRY(hipMalloc(&c->aov_mats, mats.size() * 16));
+        HIP_TRY(hipMemcpy(c->aov_mats, mats.data(), mats.size() * 16, hipMemcpyHostToDevice));
+        if (!L.textured()) {
+            HIP_TRY(hipMalloc(&c->aov_no_tex, no_tex.size() * 16));
+            HIP_TRY(hipMemcpy(c->aov_no_tex, no_tex.data(), no_tex.size() * 16, hipMemcpyHostToDevice));
+        }
     }
     c->sc.root_link = L.root_link;
     c->sc.node_slack = 1u;  // per render: node_slack_needed
@@ -1726,6 +1763,145 @@ int bdpt_intersect_from(bdpt_ctx* c, int64_t n, const float* rays, const float* 
     }
     HIP_TRY(hipMemcpyAsync(out, dout, 80 * N, hipMemcpyDeviceToHost, c->stream));
     if ((rc = end_use(c, c->stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+// ---- first-hit feature buffers and the filter for preview frames (aov_kernels.hip) ----
+static int check_aov_params(const bdpt_frame_params* p) {
+    if (!p) return fail(BDPT_ERR_INVALID, "null params");
+    if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(BDPT_ERR_INVALID, "width/height/spp must be > 0");
+    if (static_cast<int64_t>(p->width) * p->height >= (1ll << 31))
+        return fail(BDPT_ERR_INVALID, "image too large (W*H must fit int32, as in the reference)");
+    if (p->flags != 0) return fail(BDPT_ERR_UNSUPPORTED, "bdpt_render_aov: flags must be 0 (no counting pass or full traversal)");
+    if (p->row_stride < 1 || p->row_offset < 0) return fail(BDPT_ERR_INVALID, "bad row shard");
+    return BDPT_OK;
+}
+
+// Events and stats of a call that is not a frame render: kernel_ms, samples, launches.
+static int begin_timed(bdpt_ctx* c, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(unsigned long long) * kCounterWords, st));
+    HIP_TRY(hipMemsetAsync(c->capped, 0, sizeof(uint32_t), st));
+    HIP_TRY(hipEventRecord(c->ev0, st));
+    return BDPT_OK;
+}
+static int end_timed(bdpt_ctx* c, hipStream_t st, int64_t samples, int64_t launches) {
+    HIP_TRY(hipEventRecord(c->ev1, st));
+    if (int rc = end_use(c, st)) return rc;
+    c->pending_timing = true;
+    c->diag_pending = false;
+    c->stats = bdpt_stats{};
+    c->stats.samples = samples;
+    c->stats.launches = launches;
+    return BDPT_OK;
+}
+
+int bdpt_render_aov(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* aov,
+                    void* hip_stream) {
+    if (!c || !aov) return fail(BDPT_ERR_INVALID, "null argument");
+    int rc = check_aov_params(p);
+    if (rc) return rc;
+    if ((rc = check_window(p, w))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    const dev::DevFrame fr = make_frame(p, w);
+    dev::DevScene sc = c->sc;
+    const float* eye[1] = {p->camera.eye};
+    sc.node_slack = node_slack_needed(c, eye, 1);  // the interior-box test a frame of this camera uses
+    if (!sc.tex_tab) sc.tex_tab = static_cast<const float4*>(c->aov_no_tex);
+    if ((rc = begin_use(c, st))) return rc;
+    if ((rc = begin_timed(c, st))) return rc;
+    HIP_TRY(launch_aov(sc, fr, c->aov_mats, aov, c->gstack, c->nslots, st));
+    return end_timed(c, st, static_cast<int64_t>(fr.total_samples), fr.total_samples > 0 ? 1 : 0);
+}
+
+int bdpt_render_aov_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* aov_host) {
+    if (!c || !aov_host) return fail(BDPT_ERR_INVALID, "null argument");
+    int rc = check_aov_params(p);
+    if (rc) return rc;
+    if ((rc = check_window(p, w))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = static_cast<size_t>(p->width) * p->height * 8;
+    if ((rc = ensure_tmp_fb(c, n))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->tmp_fb, aov_host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((rc = bdpt_render_aov(c, p, w, c->tmp_fb, c->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(aov_host, c->tmp_fb, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+static int check_denoise(int32_t width, int32_t height, const float* color, const float* aov, const float* out,
+                         const bdpt_denoise_params* d) {
+    if (!color || !aov || !out || !d) return fail(BDPT_ERR_INVALID, "null argument");
+    if (width <= 0 || height <= 0 || static_cast<int64_t>(width) * height >= (1ll << 31))
+        return fail(BDPT_ERR_INVALID, "bdpt_denoise: width/height must be > 0 and W*H fit int32");
+    if (d->iterations < 0 || d->iterations > 8) return fail(BDPT_ERR_INVALID, "bdpt_denoise: iterations must be in [0, 8]");
+    if (!(d->sigma_color > 0.f)) return fail(BDPT_ERR_INVALID, "bdpt_denoise: sigma_color must be > 0");
+    if (!(d->sigma_normal > 0.f)) return fail(BDPT_ERR_INVALID, "bdpt_denoise: sigma_normal must be > 0");
+    if (!(d->sigma_depth > 0.f)) return fail(BDPT_ERR_INVALID, "bdpt_denoise: sigma_depth must be > 0");
+    if (d->demodulate != 0 && d->demodulate != 1) return fail(BDPT_ERR_INVALID, "bdpt_denoise: demodulate must be 0 or 1");
+    if (!(d->norm > 0.f) || !std::isfinite(d->norm)) return fail(BDPT_ERR_INVALID, "bdpt_denoise: norm must be > 0");
+    const size_t px = static_cast<size_t>(width) * height;
+    auto overlaps = [&](const float* a, size_t na) {
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + px * 3 * sizeof(float);
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), a1 = a0 + na * sizeof(float);
+        return o0 < a1 && a0 < o1;
+    };
+    if (overlaps(color, px * 3)) return fail(BDPT_ERR_INVALID, "bdpt_denoise: out overlaps color");
+    if (overlaps(aov, px * 8)) return fail(BDPT_ERR_INVALID, "bdpt_denoise: out overlaps aov");
+    return BDPT_OK;
+}
+
+int bdpt_denoise(bdpt_ctx* c, int32_t width, int32_t height, const float* color, const float* aov, float* out,
+                 const bdpt_denoise_params* d, void* hip_stream) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_denoise(width, height, color, aov, out, d);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    const size_t px = static_cast<size_t>(width) * height;
+    if ((rc = begin_use(c, st))) return rc;
+    if (d->iterations > 0 && px > c->dn_pixels) {  // the stream's earlier work may still read the old buffers
+        HIP_TRY(hipStreamSynchronize(st));
+        for (void** q : {&c->dn_guide, &c->dn_img[0], &c->dn_img[1]}) {
+            if (*q) HIP_TRY(hipFree(*q));
+            *q = nullptr;
+        }
+        c->dn_pixels = 0;
+        HIP_TRY(hipMalloc(&c->dn_guide, px * 32));
+        HIP_TRY(hipMalloc(&c->dn_img[0], px * 16));
+        HIP_TRY(hipMalloc(&c->dn_img[1], px * 16));
+        c->dn_pixels = px;
+    }
+    if ((rc = begin_timed(c, st))) return rc;
+    if (d->iterations == 0) {
+        HIP_TRY(launch_denoise_scale(px * 3, color, d->norm, out, st));
+    } else {
+        HIP_TRY(launch_denoise_prepare(width, height, color, aov, d->norm, d->demodulate, c->dn_guide, c->dn_img[0], st));
+        const float inv_n = 1.f / (d->sigma_normal * d->sigma_normal);
+        for (int i = 0; i < d->iterations; i++) {
+            const float sc_i = d->sigma_color * std::ldexp(1.f, -i);
+            HIP_TRY(launch_denoise_iter(width, height, 1 << i, 1.f / (sc_i * sc_i), inv_n, d->sigma_depth, d->demodulate,
+                                        c->dn_guide, c->dn_img[i & 1], c->dn_img[(i + 1) & 1], out,
+                                        i + 1 == d->iterations, st));
+        }
+    }
+    return end_timed(c, st, 0, d->iterations == 0 ? 1 : d->iterations + 1);
+}
+
+int bdpt_denoise_host(bdpt_ctx* c, int32_t width, int32_t height, const float* color, const float* aov, float* out,
+                      const bdpt_denoise_params* d) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_denoise(width, height, color, aov, out, d);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t px = static_cast<size_t>(width) * height;
+    if ((rc = ensure_tmp_fb(c, px * 14))) return rc;
+    float *dc = c->tmp_fb, *da = c->tmp_fb + px * 3, *dout = c->tmp_fb + px * 11;  // color, aov (16-byte aligned or not: scalar loads), out
+    HIP_TRY(hipMemcpyAsync(dc, color, px * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(da, aov, px * 8 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((rc = bdpt_denoise(c, width, height, dc, da, dout, d, c->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout, px * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BDPT_OK;
 }

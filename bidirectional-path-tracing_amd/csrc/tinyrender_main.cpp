@@ -16,6 +16,12 @@
 // F, F + S, ... (C of them) of every pixel and writes that partial image
 // (bdpt_render_window_host; partial images of windows that partition the spp sum
 // to the frame). A malformed or out-of-range window is refused before any device is used.
+// --aov also writes <out>_albedo.exr and <out>_normal.exr (the first-hit feature buffers of
+// bdpt_render_aov_host, 3 channels each, divided by the coverage), --denoise[=ITER] also
+// <out>_denoised.exr (bdpt_denoise_host with the header's defaults, ITER iterations 0..8);
+// the main EXR is the same bytes with or without them. Both combine with --sample-window
+// (the filter's norm is spp / count); with several devices the first one renders the
+// feature buffers and filters the reduced frame.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -58,13 +64,19 @@ bool parse_window(const char* text, bdpt_sample_window* w) {
     return true;
 }
 
+// "<out minus .exr><suffix>.exr"
+std::string side_path(const std::string& exr, const char* suffix) {
+    const bool ext = exr.size() >= 4 && exr.compare(exr.size() - 4, 4, ".exr") == 0;
+    return (ext ? exr.substr(0, exr.size() - 4) : exr) + suffix + ".exr";
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Syntax: %s <scene.toml> [nogui] [--width W --height H --spp N --rr D --device K "
                              "--out FILE.exr --seed S --gpus N --devices a,b,... --shard samples|rows "
-                             "--sample-window F:S:C]\n", argv[0]);
+                             "--sample-window F:S:C --aov --denoise[=ITER]]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string toml = argv[1];
@@ -75,6 +87,8 @@ int main(int argc, char** argv) {
     int32_t sharding = BDPT_SHARD_ROWS;
     bool shard_given = false, windowed = false;
     bdpt_sample_window window = {0, 1, 0};
+    bool want_aov = false, want_denoise = false;
+    int denoise_iterations = BDPT_DENOISE_ITERATIONS;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -113,6 +127,20 @@ int main(int argc, char** argv) {
                 return EXIT_FAILURE;
             }
             windowed = true;
+        } else if (a == "--aov") {
+            want_aov = true;
+        } else if (a == "--denoise") {
+            want_denoise = true;
+        } else if (a.compare(0, 10, "--denoise=") == 0) {
+            const char* v = argv[i] + 10;
+            char* end = nullptr;
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 0 || n > 8) {
+                std::fprintf(stderr, "--denoise=%s: the iteration count must be an integer in [0, 8]\n", v);
+                return EXIT_FAILURE;
+            }
+            want_denoise = true;
+            denoise_iterations = static_cast<int>(n);
         } else if (a == "--gpus") {
             const int n = std::atoi(next("--gpus"));
             devices.clear();
@@ -132,6 +160,10 @@ int main(int argc, char** argv) {
     }
     if (windowed && !devices.empty()) {
         std::fprintf(stderr, "--sample-window renders on one device (--gpus / --devices split the frame themselves)\n");
+        return EXIT_FAILURE;
+    }
+    if (want_denoise && windowed && window.count == 0) {
+        std::fprintf(stderr, "--denoise of an empty --sample-window (count 0): there is no sample to normalise by\n");
         return EXIT_FAILURE;
     }
     if (shard_given && devices.empty()) {
@@ -226,6 +258,36 @@ int main(int argc, char** argv) {
     const std::string exr = out.empty() ? exr_path_of(toml) : out;
     if (bdpt_save_exr(rgb.data(), cfg.width, cfg.height, exr.c_str()) != BDPT_OK) return die("saveEXR");
     std::printf("\nSaved EXR image to %s\n", exr.c_str());  // utils.h:149
+    if (want_aov || want_denoise) {
+        bdpt_ctx* fctx = ctx;  // several devices: the first renders the feature buffers and filters
+        if (!fctx && bdpt_ctx_create(scene, devices[0], &fctx) != BDPT_OK) return die("bdpt_ctx_create (feature buffers)");
+        const size_t px = static_cast<size_t>(cfg.width) * cfg.height;
+        std::vector<float> aov(px * 8, 0.f);
+        if (bdpt_render_aov_host(fctx, &p, win, aov.data()) != BDPT_OK) return die("bdpt_render_aov_host");
+        if (want_aov) {
+            std::vector<float> img(px * 3);
+            for (int part = 0; part < 2; part++) {  // albedo, normal: divided by the coverage, 0 where nothing was hit
+                for (size_t i = 0; i < px; i++)
+                    for (int ch = 0; ch < 3; ch++)
+                        img[3 * i + ch] = aov[8 * i + 7] > 0.f ? aov[8 * i + 3 * part + ch] / aov[8 * i + 7] : 0.f;
+                const std::string side = side_path(exr, part ? "_normal" : "_albedo");
+                if (bdpt_save_exr(img.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
+                std::printf("Saved EXR image to %s\n", side.c_str());
+            }
+        }
+        if (want_denoise) {
+            bdpt_denoise_params d = {denoise_iterations, BDPT_DENOISE_SIGMA_COLOR, BDPT_DENOISE_SIGMA_NORMAL,
+                                     BDPT_DENOISE_SIGMA_DEPTH, BDPT_DENOISE_DEMODULATE, 1.f};
+            if (windowed) d.norm = static_cast<float>(cfg.spp) / static_cast<float>(window.count);
+            std::vector<float> den(px * 3);
+            if (bdpt_denoise_host(fctx, cfg.width, cfg.height, rgb.data(), aov.data(), den.data(), &d) != BDPT_OK)
+                return die("bdpt_denoise_host");
+            const std::string side = side_path(exr, "_denoised");
+            if (bdpt_save_exr(den.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
+            std::printf("Saved EXR image to %s\n", side.c_str());
+        }
+        if (fctx != ctx) bdpt_ctx_destroy(fctx);
+    }
     if (multi) bdpt_multi_destroy(multi);
     if (ctx) bdpt_ctx_destroy(ctx);
     bdpt_scene_free(scene);

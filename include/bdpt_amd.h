@@ -39,6 +39,9 @@
  *   bdpt_render_window       a part of the offline loop's inner sample loop (renderer.cpp:160, the
  *                            samples k = first + i * stride of every pixel) for any of the three
  *                            integrators: progressive, resumable and sample-sharded frames
+ *   bdpt_render_aov          (no counterpart) the primary query of every camera sample of that loop
+ *                            (renderer.cpp:162-192, accel.h:125-172) as albedo / normal / depth / coverage
+ *   bdpt_denoise             (no counterpart) an edge-avoiding filter of a low-spp frame on the device
  *
  * Conventions: plain C types only; status 0 = OK, < 0 = error (message from
  * bdpt_last_error(), thread-local). A context is bound to one HIP device and is
@@ -431,6 +434,68 @@ int bdpt_render_window(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdp
                        void* hip_stream);
 int bdpt_render_window_host(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
                             const bdpt_path_params* path, const bdpt_direct_params* direct, float* fb_host);
+
+/* ---- first-hit feature buffers and a device filter for preview frames ---- */
+/* (new) Neither exists in the reference; both are defined by what the frame entries compute.
+ * For every pixel of the row shard and every sample k of the window (NULL = all; validation and
+ * count == 0 as bdpt_render_window), the primary ray the frame kernels build for sample (p, k) -
+ * seed seed_base + p * spp + k, the two jitter draws iff the full spp > 1, min_t 1, max_t 1000 -
+ * and its closest hit by the frame kernels' traversal (the interior-box test a frame of this camera
+ * uses, accepted iff min_t <= t <= max_t). ADDS, with weight 1 / spp of the full spp, eight floats
+ * to aov[pixel][8] (interleaved, width * height * 8 floats), so row shards and windows that
+ * partition the frame sum to the full buffers as the framebuffers do:
+ *   [0..2] albedo   [3..5] frameNs.n in world space as bdpt_hit.ns (not flipped; an average of unit
+ *   vectors, not renormalised)   [6] t   [7] 1 (coverage);   all 0 on a miss.
+ * Albedo by this build's material kind (bdpt_bsdf_type): diffuse Kd; mixture and Phong Kd + Ks, each
+ * channel clamped to at most 1; mirror, glass and the null BSDF of illum 5 (emitters) (1, 1, 1). With a
+ * map_Kd / map_Ks, Kd / Ks is the texel at the hit (BitmapTexture3f::eval, as the textured frames read it).
+ * Materials are read from HBM per hit: no material-count limit, and textured scenes with many
+ * materials run. rr_depth, strategy and russian_roulette are not read (they do not affect a first
+ * hit); flags other than 0 are BDPT_ERR_UNSUPPORTED. bdpt_get_stats afterwards: kernel_ms, samples,
+ * launches of this call. Asynchronous on `hip_stream` like bdpt_render; the host form is synchronous. */
+int bdpt_render_aov(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                    float* aov_device, void* hip_stream);
+int bdpt_render_aov_host(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                         float* aov_host);
+
+/* (new) Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by the feature buffers.
+ * With c = color * norm and a = aov * norm per pixel p: cov = a[7]; if cov > 0, alb = a[0:3] / cov,
+ * N = a[3:6] / cov, z = a[6] / cov, else alb = (1, 1, 1), N = 0, z = 0;
+ * I_0 = demodulate ? c / max(alb, 1e-3) : c per channel. Iteration i = 0 .. iterations - 1, step s = 2^i:
+ *   I_{i+1}(p) = sum_q h(q - p) w(p, q) I_i(q) / sum_q h(q - p) w(p, q),
+ *   q = p + s (dx, dy), dx, dy in -2..2, taps outside the image skipped, h the outer product of
+ *   [1, 4, 6, 4, 1] / 16, w = w_c w_n w_z w_cov, the centre tap w = 1, and
+ *   w_c = exp(-min(|I_i(p) - I_i(q)|^2 / (sigma_color 2^-i)^2, 80)),
+ *   w_n = exp(-min(|N_p - N_q|^2 / sigma_normal^2, 80)),
+ *   w_z = exp(-min((z_p - z_q)^2 / (sigma_depth max(z_p, 1e-6))^2, 80)),
+ *   w_cov = 1 if (cov_p > 0) == (cov_q > 0), else 0.
+ * out = I_iterations * (demodulate ? max(alb, 1e-3) : 1); iterations == 0 copies color * norm. No
+ * atomics and a fixed summation order (dy outer, dx inner): two runs give the same bits. out
+ * (width * height * 3 floats) must not overlap color or aov (BDPT_ERR_INVALID, as is a bad field, named
+ * in the message). The context owns the scratch (packed guides and two ping-pong images, 64 bytes per
+ * pixel, allocated at first use and grown when needed). bdpt_get_stats afterwards: kernel_ms and
+ * launches of this call. Asynchronous on `hip_stream`; the host form is synchronous. */
+typedef struct {
+    int32_t iterations;      /* 0..8; 0 copies (color * norm) to out */
+    float sigma_color, sigma_normal, sigma_depth; /* each > 0 */
+    int32_t demodulate;      /* 0 / 1: filter color / max(albedo, 1e-3), multiply back afterwards */
+    float norm;              /* multiplies color and aov on load: spp / samples_done for a partial frame, 1 for
+                                a full one; > 0 */
+} bdpt_denoise_params;
+/* Defaults, chosen on the 4-spp HardLight 64 x 64 frame of tests/test_gpu_denoise.py against its
+ * 256-spp frame and on nothing else (a grid over iterations 3..5, sigma_color 0.1..4, sigma_normal
+ * 0.1..1, sigma_depth 0.002..0.5, both demodulate: mean squared error 0.00190 against the unfiltered
+ * frame's 0.00295; still smaller depth sigmas score a little better there only by leaving sloped
+ * surfaces unfiltered). */
+#define BDPT_DENOISE_ITERATIONS 5
+#define BDPT_DENOISE_SIGMA_COLOR 2.0f
+#define BDPT_DENOISE_SIGMA_NORMAL 0.3f
+#define BDPT_DENOISE_SIGMA_DEPTH 0.02f
+#define BDPT_DENOISE_DEMODULATE 1
+int bdpt_denoise(bdpt_ctx* ctx, int32_t width, int32_t height, const float* color_dev, const float* aov_dev,
+                 float* out_dev, const bdpt_denoise_params* params, void* hip_stream);
+int bdpt_denoise_host(bdpt_ctx* ctx, int32_t width, int32_t height, const float* color_host, const float* aov_host,
+                      float* out_host, const bdpt_denoise_params* params);
 
 /* ---- several HIP devices in one process ---- */
 /* The reference fans the offline loop out over host threads (parallel_for,
