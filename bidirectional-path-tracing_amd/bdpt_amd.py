@@ -209,7 +209,7 @@ class _Stats(ctypes.Structure):
 
 # Sources that make up the frame kernels' code objects: their hash stamps the
 # profiles (PMC passes) so bench.py only reuses a measurement of the same kernel.
-KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
+KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
                   "csrc/powf_restated.inc", "csrc/bdpt_types.h", "Makefile")
 
 
@@ -245,6 +245,7 @@ def lib():
         L.bdpt_version.restype = ctypes.c_char_p
         L.bdpt_last_kernel.restype = ctypes.c_char_p
         L.bdpt_last_kernel.argtypes = [ctypes.c_void_p]
+        L.bdpt_last_kernel_glossy.argtypes = [ctypes.c_void_p]
         L.bdpt_set_row_order.argtypes = [vp, vp, i32]
         L.bdpt_get_row_costs.argtypes = [vp, vp, i32]
         L.bdpt_scene_load_obj.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -970,7 +971,8 @@ class BDPTIntegrator:
                     max_eye_depth=s.max_eye_depth, max_queries=s.max_queries, schedule_errors=s.schedule_errors, parked_samples=s.parked_samples,
                     rr_long_walks_max=s.rr_long_walks_max, rr_express_iters=list(s.rr_express_iters),
                     sched=dict(zip(("step_tasks", "shade_steps", "steps_ge32", "steps_ge64"), list(s.sched))),
-                    kernel=(lib().bdpt_last_kernel(self._h) or b"").decode())
+                    kernel=(lib().bdpt_last_kernel(self._h) or b"").decode(),
+                    kernel_glossy=int(lib().bdpt_last_kernel_glossy(self._h)))
 
     def synchronize(self) -> None:
         _check(lib().bdpt_synchronize(self._h))

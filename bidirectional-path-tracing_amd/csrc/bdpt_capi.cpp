@@ -79,6 +79,12 @@ hipError_t launch_frame_tex(const dev::DevScene& sc, const dev::DevFrame& fr, fl
                             hipStream_t stream, void* dparams);
 int frame_kernel_blocks_per_cu_tex(size_t dyn_lds);
 int light_vertex_fields_tex();
+// bdpt_kernels_ng.hip: the default megakernel without the Mixture / Phong lobes (BDPT_GLOSSY 0),
+// for material tables of diffuse, mirror and glass records only
+hipError_t launch_frame_ng(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf, uint2* gstack,
+                           uint32_t nslots, unsigned long long* work, unsigned long long* counters, int grid,
+                           hipStream_t stream, void* dparams);
+int frame_kernel_blocks_per_cu_ng(size_t dyn_lds);
 hipError_t launch_sample_tex(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf,
                              uint2* gstack, const dev::Ray& ray, float* out, hipStream_t stream);
 size_t pt_params_bytes();
@@ -207,6 +213,7 @@ struct bdpt_scene {
 
 struct bdpt_ctx {
     const char* last_kernel = "";  // the frame kernel build the last render launched (bdpt_last_kernel)
+    int last_kernel_glossy = 1;    // 0: that build has no Mixture / Phong lobes (bdpt_last_kernel_glossy)
     int device = 0;
     int cus = 0;
     int grid = 0;
@@ -246,6 +253,8 @@ struct bdpt_ctx {
     bool textured = false;        // the scene has bitmap textures: bdpt_render runs bdpt_kernels_tex.hip
     std::vector<uint8_t> mat_textured;  // per material: it reads a map (bdpt_bsdf_* carry no hit to look one up)
     bool has_glass = false;       // a GlassBSDF material: Russian-roulette renders run bdpt_kernels_rrc.hip
+    bool has_glossy = false;      // a Mixture / Phong record in the device table (after device_bsdfs)
+    bool has_null = false;        // a null BSDF (illum 5): not delta, not diffuse
     int32_t* row_order = nullptr;  // bdpt_set_row_order (device copy; DevFrame::row_order)
     int32_t row_order_n = 0;       // its row count (0: top to bottom)
     unsigned long long* row_cost = nullptr;  // counting renders: queries per local row (DevFrame::row_cost)
@@ -646,7 +655,11 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     {
         const std::vector<BsdfRecord> dev_bsdfs = device_bsdfs(L.bsdfs, L.mat_tex);
         if ((rc = upload(c.get(), dev_bsdfs.data(), dev_bsdfs.size() * sizeof(BsdfRecord), &p))) return rc;
-        for (const BsdfRecord& b : dev_bsdfs) c->has_glass = c->has_glass || b.kind == BSDF_GLASS;
+        for (const BsdfRecord& b : dev_bsdfs) {
+            c->has_glass = c->has_glass || b.kind == BSDF_GLASS;
+            c->has_glossy = c->has_glossy || b.kind == BSDF_MIXTURE || b.kind == BSDF_PHONG;
+            c->has_null = c->has_null || b.kind == BSDF_NULL;
+        }
     }
     c->sc.bsdf = static_cast<const BsdfRecord*>(p);
     if ((rc = upload(c.get(), L.emitters.data(), L.emitters.size() * sizeof(EmitterRecord), &p))) return rc;
@@ -1001,6 +1014,7 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
     HIP_TRY(hipEventRecord(c->ev0, st));
     int64_t launches = 0;
     if (fr.total_samples > 0) {
+        c->last_kernel_glossy = 1;
         if (c->textured) {  // (no Russian roulette, rr_depth <= 28, LDS records: textured_frame_check)
             const int grid = std::min(c->grid, c->cus * frame_kernel_blocks_per_cu_tex(
                                                            4 * static_cast<size_t>(c->sc.lds_words)));
@@ -1056,8 +1070,22 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
                                        c->dparams));
             c->last_kernel = "bdpt_frame_kernel_split";
         } else {
-            HIP_TRY(launch_frame(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, c->grid, st,
-                                 c->dparams));
+            // a table of diffuse, mirror and glass records only runs the build without the
+            // Mixture / Phong lobes (bdpt_kernels_ng.hip: a vertex that is not delta is diffuse
+            // there, so a null BSDF keeps the full build too); BDPT_NG_BUILD=0 forces the full
+            // build, =1 asks for the other and is ignored where the table does not allow it
+            const char* ne = std::getenv("BDPT_NG_BUILD");
+            const bool ng = !c->has_glossy && !c->has_null && !(ne && *ne == '0');
+            if (ng) {  // never more resident blocks than the slots allocated
+                const int grid = std::min(c->grid, c->cus * frame_kernel_blocks_per_cu_ng(
+                                                               4 * static_cast<size_t>(c->sc.lds_words)));
+                HIP_TRY(launch_frame_ng(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, grid, st,
+                                        c->dparams));
+                c->last_kernel_glossy = 0;
+            } else {
+                HIP_TRY(launch_frame(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, c->grid, st,
+                                     c->dparams));
+            }
             c->last_kernel = "bdpt_frame_kernel";
         }
         launches += 1;
@@ -1400,6 +1428,7 @@ int bdpt_debug_math(int32_t device, int32_t fn, const float* x, const float* y, 
 }
 
 const char* bdpt_last_kernel(const bdpt_ctx* c) { return c ? c->last_kernel : ""; }
+int bdpt_last_kernel_glossy(const bdpt_ctx* c) { return c ? c->last_kernel_glossy : 1; }
 
 int bdpt_set_row_order(bdpt_ctx* c, const int32_t* order, int32_t n) {
     if (!c || n < 0 || (n > 0 && !order)) return fail(BDPT_ERR_INVALID, "bdpt_set_row_order: bad argument");

@@ -1955,6 +1955,15 @@ __device__ __forceinline__ Ray shadow_ray(f3 start, f3 end) {
 // -------------------------------------------------------------------- BSDFs
 __device__ __forceinline__ f3 ld3(const float* p) { return mk(p[0], p[1], p[2]); }
 
+// BDPT_GLOSSY 0 (bdpt_kernels_ng.hip): a build for material tables whose records are all
+// DiffuseBSDF, PerfectMirrorBSDF or GlassBSDF (no Mixture / Phong record, no null BSDF; the
+// host checks the table, bdpt_capi.cpp). The Mixture / Phong branches, their out-of-line calls
+// and powf are compiled out, and a vertex that is not delta is then diffuse without a test of
+// its kind (bsdf_eval_pdfs, local_for). The remaining lobes run the same operations in the
+// same order.
+#ifndef BDPT_GLOSSY
+#define BDPT_GLOSSY 1
+#endif
 #ifndef BDPT_GLOSSY_ATTR
 #define BDPT_GLOSSY_ATTR __forceinline__  // the Phong-bearing eval / pdf (measured: inline +2 %)
 #endif
@@ -1996,7 +2005,9 @@ __device__ __forceinline__ f3 bsdf_eval(const BsdfRecord& b, f3 wi, f3 wo) {
         if (wi.z >= 0.f && wo.z >= 0.f) return (ld3(b.kd) * kInvPi) * wi.z;
         return mk(0.f, 0.f, 0.f);
     }
+#if BDPT_GLOSSY
     if (kind == BSDF_MIXTURE || kind == BSDF_PHONG) return glossy_eval_call(b, wi, wo);
+#endif
     return mk(0.f, 0.f, 0.f);  // delta lobes (perfectmirror.h:41-47, glass.h:55-59)
 }
 
@@ -2020,9 +2031,13 @@ __device__ BDPT_GLOSSY_ATTR float glossy_pdf_call(const BsdfRecord& b, f3 wi, f3
 }
 __device__ __forceinline__ float bsdf_pdf(const BsdfRecord& b, f3 wi, f3 wo) {
     const int kind = b.kind;
+#if BDPT_GLOSSY
     if (kind == BSDF_DIFFUSE || (kind == BSDF_MIXTURE && b.specw == 0.f))  // diffuse.h:45-50
         return cosine_hemisphere_pdf(wi);
     if (kind == BSDF_MIXTURE || kind == BSDF_PHONG) return glossy_pdf_call(b, wi, wo);
+#else
+    if (kind == BSDF_DIFFUSE) return cosine_hemisphere_pdf(wi);  // diffuse.h:45-50
+#endif
     return 0.f;
 }
 
@@ -2034,12 +2049,20 @@ __device__ __forceinline__ float bsdf_pdf(const BsdfRecord& b, f3 wi, f3 wo) {
 // order) are one value z. eval takes powf(clamp(z)), the pdfs powf(z) for
 // z >= 0: the same call unless z > 1, where eval's powf(1, n) is exactly 1.
 // Each output is bit-identical to bsdf_eval / bsdf_pdf above.
+// Its callers connect vertices that are not delta (connectToLight, connectToCamera,
+// connectVertices); in a BDPT_GLOSSY 0 build those are diffuse, so the kind is not read.
 struct EvalPdfs {
     f3 f;
     float fwd, rev;  // pdf(wi, wo), pdf(wo, wi)
 };
 __device__ __forceinline__ EvalPdfs bsdf_eval_pdfs(const BsdfRecord& b, f3 wi, f3 wo) {
-#if BDPT_EVAL_PDFS
+#if !BDPT_GLOSSY
+    EvalPdfs r{mk(0.f, 0.f, 0.f), 0.f, 0.f};
+    if (wi.z >= 0.f && wo.z >= 0.f) r.f = (ld3(b.kd) * kInvPi) * wi.z;
+    r.fwd = cosine_hemisphere_pdf(wi);
+    r.rev = cosine_hemisphere_pdf(wo);
+    return r;
+#elif BDPT_EVAL_PDFS
     EvalPdfs r{mk(0.f, 0.f, 0.f), 0.f, 0.f};
     const int kind = b.kind;
     if (kind == BSDF_DIFFUSE) {
@@ -2134,6 +2157,7 @@ __device__ BDPT_NOINLINE f3 bsdf_sample_call(const BsdfRecord& b, f3 wo, F2 u, f
         // bdpt.h:253), so the Phong powers here stay glibc's powf in every build: the
         // fast-weight pow_w flushes results below 2^-126 to 0, which for a
         // lobe with Kd = 0 would end a path the reference continues.
+#if BDPT_GLOSSY
         case BSDF_MIXTURE: {  // mixture.h:102-151
             f3 val;
             if (u.x < b.specw) {
@@ -2160,6 +2184,7 @@ __device__ BDPT_NOINLINE f3 bsdf_sample_call(const BsdfRecord& b, f3 wo, F2 u, f
             wi = to_world(rs, rt, rn, ls);
             return glossy_eval<true>(b, wi, wo);
         }
+#endif
         default:  // null BSDF (illum 5): the reference dereferences nullptr
             pdf = 0.f;
             wi = mk(0.f, 0.f, 0.f);
@@ -2191,7 +2216,7 @@ __device__ __forceinline__ f3 bsdf_sample(const BsdfRecord& b, f3 wo, F2 u, f3& 
         pdf = cosine_hemisphere_pdf(wi);
         return bsdf_eval(b, wi, wo);
     }
-#if BDPT_GLASS_INLINE
+#if BDPT_GLASS_INLINE || !BDPT_GLOSSY
     if (b.kind == BSDF_GLASS) return glass_sample(b, wo, u, wi, pdf);
     if (b.kind == BSDF_MIRROR) {  // perfectmirror.h:49-59
         pdf = 1.f;
@@ -2199,7 +2224,13 @@ __device__ __forceinline__ f3 bsdf_sample(const BsdfRecord& b, f3 wo, F2 u, f3& 
         return mk(1.f, 1.f, 1.f);
     }
 #endif
+#if BDPT_GLOSSY
     return bsdf_sample_call(b, wo, u, wi, pdf);
+#else
+    pdf = 0.f;  // (no other kind in this build's tables; bsdf_sample_body's default)
+    wi = mk(0.f, 0.f, 0.f);
+    return mk(0.f, 0.f, 0.f);
+#endif
 }
 
 __device__ __forceinline__ bool is_delta(const BsdfRecord& b) { return (b.type & kTypeDelta) != 0; }
@@ -2229,15 +2260,20 @@ __device__ __forceinline__ BsdfRecord bsdf_tex(const DevScene& sc, int mat, int 
 // The direction v in the shading frame of normal n, for evaluating BSDF b:
 // DiffuseBSDF's eval and pdf read only the z component, dot(v, n) (to_local),
 // so a diffuse lane skips Frame(n) (a sqrt, a division and a branch); the x, y
-// it leaves at 0 are never read. BDPT_DIFFUSE_Z 0 builds every frame.
+// it leaves at 0 are never read. BDPT_DIFFUSE_Z 0 builds every frame. Called for
+// the ends of a connection, which are not delta: diffuse in a BDPT_GLOSSY 0 build.
 #ifndef BDPT_DIFFUSE_Z
 #define BDPT_DIFFUSE_Z 1
 #endif
 __device__ __forceinline__ f3 local_for(const BsdfRecord& b, f3 n, f3 v) {
+#if !BDPT_GLOSSY
+    return mk(0.f, 0.f, dot(v, n));
+#else
 #if BDPT_DIFFUSE_Z
     if (b.kind == BSDF_DIFFUSE) return mk(0.f, 0.f, dot(v, n));
 #endif
     return local_at(n, v);
+#endif
 }
 
 // ---------------------------------------------------------------- emitters

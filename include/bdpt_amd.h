@@ -331,6 +331,11 @@ int bdpt_get_stats(bdpt_ctx* ctx, bdpt_stats* out);
  * total internal reflection bounces inline) or "_hbm" (BSDF records in HBM); "" before the first render. For
  * matching profiler records to the kernel that ran. */
 const char* bdpt_last_kernel(const bdpt_ctx* ctx);
+/* (new) Whether that build carries the Mixture / Phong lobes: 1, or 0 for the build that a scene
+ * whose materials are all diffuse, mirror or glass (after the Ks = 0 mixture is run as diffuse)
+ * renders with where it would otherwise launch "bdpt_frame_kernel" (same name; the environment
+ * variable BDPT_NG_BUILD=0 forces the full build). 1 before the first render. */
+int bdpt_last_kernel_glossy(const bdpt_ctx* ctx);
 /* Waits for all work queued by this context (on every stream it was given). */
 int bdpt_synchronize(bdpt_ctx* ctx);
 /* (new) Claim order of the shard's rows for the context's later bdpt_render calls: order[i]
