@@ -20,10 +20,9 @@
 #include "scene.hpp"
 
 namespace bdpt {
-hipError_t launch_frame(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf, uint2* gstack,
-                        uint32_t nslots, unsigned long long* work, unsigned long long* counters, int grid,
-                        hipStream_t stream, void* dparams);
-size_t frame_params_bytes();
+// The builds of the BDPT frame kernel (bdpt_kernels_<x>.hip; FrameBuild: bdpt_device.hpp)
+extern FrameBuild frame_build, frame_build_tex, frame_build_rr, frame_build_rrc, frame_build_deep,
+    frame_build_hbm, frame_build_split, frame_build_ng;
 // sample_state.hip: the single-sample kernels (the caller's std::mt19937 state at sc.mt_ring)
 hipError_t launch_sample(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf, uint2* gstack,
                          const dev::Ray& ray, float* out, hipStream_t stream);
@@ -38,53 +37,7 @@ hipError_t launch_triangle_kat(int64_t n, const float* rays, const float* verts,
 hipError_t launch_intersect_kat(const dev::DevScene& sc, int64_t n, int occlusion, const float* rays, const float* nrm,
                                 const int32_t* otri, uint2* gstack, uint32_t nslots, float* out, hipStream_t st);
 hipError_t launch_splat_kat(const dev::DevFrame& fr, int64_t n, const float* p, int32_t* xy, hipStream_t st);
-int frame_kernel_lds_stack();
-int frame_kernel_blocks_per_cu(size_t dyn_lds);
-// bdpt_kernels_deep.hip: the same megakernel for rrDepth > 28
-hipError_t launch_frame_deep(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf,
-                             uint2* gstack, uint32_t nslots, unsigned long long* work, unsigned long long* counters,
-                             int grid, hipStream_t stream, void* dparams);
-int frame_kernel_blocks_per_cu_deep(size_t dyn_lds);
-// bdpt_kernels_hbm.hip: the same megakernel with the BSDF records in HBM
-hipError_t launch_frame_hbm(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf, uint2* gstack,
-                            uint32_t nslots, unsigned long long* work, unsigned long long* counters, int grid,
-                            hipStream_t stream, void* dparams);
-int frame_kernel_blocks_per_cu_hbm(size_t dyn_lds);
-// bdpt_kernels_rr.hip: the same megakernel with Russian roulette (NO_RR = 0)
-hipError_t launch_frame_rr(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf, uint2* gstack,
-                           uint32_t nslots, unsigned long long* work, unsigned long long* counters, int grid,
-                           hipStream_t stream, void* dparams);
-int frame_kernel_blocks_per_cu_rr(size_t dyn_lds);
-// its continuation pass: one wave per sample parked past park_depth bounces (bdpt_kernels.hip, park_lane)
-hipError_t launch_chain_rr(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf, uint2* gstack,
-                           uint32_t nslots, unsigned long long* work, unsigned long long* counters, int grid,
-                           hipStream_t stream, void* dparams);
-// bdpt_kernels_rrc.hip: the Russian-roulette megakernel for scenes with glass (lone trapped chains inline)
-hipError_t launch_frame_rrc(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf, uint2* gstack,
-                            uint32_t nslots, unsigned long long* work, unsigned long long* counters, int grid,
-                            hipStream_t stream, void* dparams);
-int frame_kernel_blocks_per_cu_rrc(size_t dyn_lds);
-hipError_t launch_chain_rrc(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf, uint2* gstack,
-                            uint32_t nslots, unsigned long long* work, unsigned long long* counters, int grid,
-                            hipStream_t stream, void* dparams);
-// bdpt_kernels_split.hip: the same megakernel for short subpaths (no ST_DEFER step)
-hipError_t launch_frame_split(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf,
-                              uint2* gstack, uint32_t nslots, unsigned long long* work, unsigned long long* counters,
-                              int grid, hipStream_t stream, void* dparams);
-int frame_kernel_blocks_per_cu_split(size_t dyn_lds);
-// bdpt_kernels_tex.hip / sample_state_tex.hip: the megakernel and the single-sample kernel for
-// scenes with bitmap textures (BDPT_TEXTURED: texel lookup at every closest hit, 80-byte light vertices)
-hipError_t launch_frame_tex(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf, uint2* gstack,
-                            uint32_t nslots, unsigned long long* work, unsigned long long* counters, int grid,
-                            hipStream_t stream, void* dparams);
-int frame_kernel_blocks_per_cu_tex(size_t dyn_lds);
-int light_vertex_fields_tex();
-// bdpt_kernels_ng.hip: the default megakernel without the Mixture / Phong lobes (BDPT_GLOSSY 0),
-// for material tables of diffuse, mirror and glass records only
-hipError_t launch_frame_ng(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf, uint2* gstack,
-                           uint32_t nslots, unsigned long long* work, unsigned long long* counters, int grid,
-                           hipStream_t stream, void* dparams);
-int frame_kernel_blocks_per_cu_ng(size_t dyn_lds);
+// sample_state_tex.hip: the single-sample kernel for scenes with bitmap textures
 hipError_t launch_sample_tex(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf,
                              uint2* gstack, const dev::Ray& ray, float* out, hipStream_t stream);
 size_t pt_params_bytes();
@@ -92,8 +45,6 @@ int pt_blocks_per_cu(size_t dyn_lds);
 hipError_t launch_pt(const dev::DevScene& sc, const dev::DevFrame& fr, const int32_t settings[8], float* fb,
                      float4* levels, uint32_t* ring, uint2* gstack, uint32_t nslots, unsigned long long* work,
                      unsigned long long* counters, int grid, hipStream_t stream, void* dparams);
-int frame_kernel_block();
-int light_vertex_fields();
 hipError_t launch_math_check(int32_t fn, const float* x, const float* y, float* out, int64_t n, hipStream_t st);
 // aov_kernels.hip: first-hit feature buffers and the a-trous filter
 hipError_t launch_aov(const dev::DevScene& sc, const dev::DevFrame& fr, const void* mats, float* aov, uint2* gstack,
@@ -224,7 +175,7 @@ struct bdpt_ctx {
     dev::DevScene sc{};
     int max_depth = 0;
     bool tri_tree = false;              // traversal boxes padded (wide_bvh.hpp kTriBoxPad)
-    int64_t wnode_bytes = 0;            // the 4-wide node array (BDPT_SLAB_SIGN: 32-bit offsets into it)
+    int64_t wnode_bytes = 0;            // the 4-wide node array (load_wnode_nf: 32-bit offsets into it)
     double box_lo[3] = {}, box_hi[3] = {};  // scene bounds (the reference BVH's root box)
     int64_t scene_bytes = 0;
     int64_t ntri = 0;  // triangles (shade records)
@@ -676,7 +627,7 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     c->sc.tex_tab = nullptr;
     if (L.textured()) {  // map records + texel pool; the texture coordinates ride in the shade records
         if (kShadeStride < kShadeSt + 2)
-            return fail(BDPT_ERR_UNSUPPORTED, "bitmap textures need the wide shade records (BDPT_SHADE_WIDE)");
+            return fail(BDPT_ERR_UNSUPPORTED, "bitmap textures need the wide shade records");
         if ((rc = upload(c.get(), L.tex_tab.data(), L.tex_tab.size() * 16, &p))) return rc;
         c->sc.tex_tab = static_cast<const float4*>(p);
         c->textured = true;
@@ -751,7 +702,7 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
         const uint32_t with = up4(ecdf + static_cast<uint32_t>(c->sc.n_ecdf));
         auto blocks = [&](uint32_t words) {
             const size_t bytes = 4 * static_cast<size_t>(words);
-            return hbm ? frame_kernel_blocks_per_cu_hbm(bytes) : frame_kernel_blocks_per_cu(bytes);
+            return (hbm ? frame_build_hbm : frame_build).blocks_per_cu(bytes);
         };
         if (with * 4u <= kBudget && blocks(with) >= blocks(c->sc.lds_words)) {
             c->sc.lds_etri_off = etri;
@@ -771,13 +722,12 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     HIP_TRY(hipMalloc(&c->sample_out, 16 * sizeof(float)));
     HIP_TRY(hipMalloc(&c->capped, sizeof(uint32_t)));
     HIP_TRY(hipMemset(c->capped, 0, sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&c->dparams, frame_params_bytes()));
+    HIP_TRY(hipMalloc(&c->dparams, frame_build.params_bytes));
     // Persistent grid: exactly the resident blocks (no co-residency is assumed:
     // the work queue has no inter-block waits, extra blocks would just queue).
     const size_t dyn = 4 * static_cast<size_t>(c->sc.lds_words);
-    c->grid = c->cus * (c->sc.lds_bsdf_off == dev::kNoLds ? frame_kernel_blocks_per_cu_hbm(dyn)
-                                                          : frame_kernel_blocks_per_cu(dyn));
-    c->nslots = static_cast<uint32_t>(c->grid * frame_kernel_block());
+    c->grid = c->cus * (c->sc.lds_bsdf_off == dev::kNoLds ? frame_build_hbm : frame_build).blocks_per_cu(dyn);
+    c->nslots = static_cast<uint32_t>(c->grid * frame_build.block);
     // BDPT_GRID_BLOCKS=n (debugging knob): at most n blocks per frame-kernel launch; the slots
     // stay allocated for the whole grid. With few blocks a small frame gives each wave many
     // chunks, which is what reuses its eye slots (tests/test_gpu_sample_window.py).
@@ -789,7 +739,7 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     // right children; 4-wide: the host-computed bound), the part beyond the
     // kernel's LDS entries in HBM.
     const int depth = std::max(s->host.max_depth + 2, L.wmax_stack + 1);
-    const int lds_entries = frame_kernel_lds_stack();
+    const int lds_entries = frame_build.lds_stack;
     c->sc.gdepth = static_cast<uint32_t>(std::max(1, depth - lds_entries));  // per slot (DevScene::gdepth)
     const size_t spill_mega = static_cast<size_t>(c->sc.gdepth) * c->nslots;
     HIP_TRY(hipMalloc(&c->gstack, sizeof(uint2) * std::max<size_t>(1, spill_mega)));
@@ -861,7 +811,7 @@ static dev::DevFrame make_frame(const bdpt_frame_params* p, const bdpt_sample_wi
 }
 
 static int ensure_lv(bdpt_ctx* c, int lv_max, uint32_t nslots) {
-    const int fields = c->textured ? light_vertex_fields_tex() : light_vertex_fields();
+    const int fields = (c->textured ? frame_build_tex : frame_build).light_vertex_fields;
     const size_t need = static_cast<size_t>(std::max(lv_max, 1)) * fields * nslots;
     if (need > c->lv_floats) {
         if (c->lv) HIP_TRY(hipFree(c->lv));
@@ -906,9 +856,9 @@ static int textured_frame_check(const bdpt_ctx* c, const bdpt_frame_params* p) {
 // conservative and the ambiguity slack is skipped. Other rays
 // (bdpt_intersect's, the refleaf tree's unpadded boxes) keep it.
 //
-// BDPT_SLAB_FMA builds test those boxes by one fma per plane (slab_fma), whose
+// The slack-free walk tests those boxes by one fma per plane (slab_fma), whose
 // error also grows with the origin's distance from 0 (2^-24 |o_i| per plane in
-// scene units): they skip the slack only while the origins and the scene box
+// scene units): it skips the slack only while the origins and the scene box
 // also lie within kFmaCoordDiags diagonals of 0, where the per-plane error,
 // 2^-23 · 101 + 2^-24 · 300 < 3e-5 diagonals, stays below slab_fast's own bound
 // at 100 diagonals (3.6e-7 · 202 = 7.3e-5) and far inside the padding.
@@ -918,10 +868,9 @@ static uint32_t node_slack_needed(const bdpt_ctx* c, const float* const* origins
     double diag2 = 0.0;
     for (int a = 0; a < 3; a++) diag2 += (c->box_hi[a] - c->box_lo[a]) * (c->box_hi[a] - c->box_lo[a]);
     if (!(diag2 > 0.0) || !std::isfinite(diag2)) return 1u;
-    // BDPT_SLAB_SIGN builds address the node planes by 32-bit offsets (load_wnode_nf)
-    if (BDPT_SLAB_SIGN && c->wnode_bytes >= (int64_t{1} << 32)) return 1u;
-    constexpr bool kFmaPlanes = BDPT_SLAB_FMA != 0 || BDPT_SLAB_SIGN != 0;
-    const double coord_max = kFmaPlanes ? kFmaCoordDiags * std::sqrt(diag2) : HUGE_VAL;
+    // the slack-free walk addresses the node planes by 32-bit offsets (load_wnode_nf)
+    if (c->wnode_bytes >= (int64_t{1} << 32)) return 1u;
+    const double coord_max = kFmaCoordDiags * std::sqrt(diag2);
     for (int a = 0; a < 3; a++)
         if (!(std::fabs(c->box_lo[a]) <= coord_max && std::fabs(c->box_hi[a]) <= coord_max)) return 1u;
     for (int k = 0; k < n; k++) {
@@ -935,6 +884,32 @@ static uint32_t node_slack_needed(const bdpt_ctx* c, const float* const* origins
         if (!std::isfinite(far2) || far2 > 1.0e4 * diag2) return 1u;
     }
     return 0u;
+}
+
+// The frame-kernel build of a render that textured_frame_check and render_bdpt's own
+// checks have accepted. The order of the decisions matters (a textured scene with
+// rr_depth 2 runs the textured build, not the short-subpath one). Read per render:
+// BDPT_RR_CHAIN=0/1 forces the Russian-roulette build without / with the inline chain,
+// BDPT_SPLIT_MAX_RR moves the short-subpath threshold (use_split_build), BDPT_NG_BUILD=0
+// keeps the full build (=1 asks for the other and is ignored where the table does not
+// allow it). BDPT_BSDF_IN_HBM=1 acts earlier, on the table layout bdpt_ctx_create chose.
+static const FrameBuild& pick_frame_build(const bdpt_ctx* c, const bdpt_frame_params* p) {
+    if (c->textured) return frame_build_tex;
+    if (p->russian_roulette == BDPT_RR_LUMINANCE) {
+        // scenes with a dielectric can trap a subpath in a chain of delta bounces: the
+        // build that runs a lone chain inline (bdpt_kernels_rrc.hip)
+        const char* ce = std::getenv("BDPT_RR_CHAIN");
+        return (ce ? *ce == '1' : c->has_glass) ? frame_build_rrc : frame_build_rr;
+    }
+    if (p->rr_depth > kLazyRrDepth) return frame_build_deep;
+    if (c->sc.lds_bsdf_off == dev::kNoLds) return frame_build_hbm;
+    if (use_split_build(p->rr_depth)) return frame_build_split;
+    // a table of diffuse, mirror and glass records only runs the build without the
+    // Mixture / Phong lobes (bdpt_kernels_ng.hip: a vertex that is not delta is diffuse
+    // there, so a null BSDF keeps the full build too)
+    const char* ne = std::getenv("BDPT_NG_BUILD");
+    if (!c->has_glossy && !c->has_null && !(ne && *ne == '0')) return frame_build_ng;
+    return frame_build;
 }
 
 // bdpt_render and the BDPT form of bdpt_render_window (w null: every sample).
@@ -1014,81 +989,38 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
     HIP_TRY(hipEventRecord(c->ev0, st));
     int64_t launches = 0;
     if (fr.total_samples > 0) {
-        c->last_kernel_glossy = 1;
-        if (c->textured) {  // (no Russian roulette, rr_depth <= 28, LDS records: textured_frame_check)
-            const int grid = std::min(c->grid, c->cus * frame_kernel_blocks_per_cu_tex(
-                                                           4 * static_cast<size_t>(c->sc.lds_words)));
-            HIP_TRY(launch_frame_tex(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, grid, st,
-                                     c->dparams));
-            c->last_kernel = "bdpt_frame_kernel_tex";
-        } else if (rr) {  // never more resident blocks than the slots allocated
-            // scenes with a dielectric can trap a subpath in a chain of delta bounces: the
-            // build that runs a lone chain inline (bdpt_kernels_rrc.hip); BDPT_RR_CHAIN=0/1 forces
-            const char* ce = std::getenv("BDPT_RR_CHAIN");
-            const bool chain = ce ? *ce == '1' : c->has_glass;
-            auto launch_rr = chain ? launch_frame_rrc : launch_frame_rr;
-            auto launch_chain_k = chain ? launch_chain_rrc : launch_chain_rr;
-            const int grid = std::min(c->grid, c->cus * (chain ? frame_kernel_blocks_per_cu_rrc : frame_kernel_blocks_per_cu_rr)(
-                                                           4 * static_cast<size_t>(c->sc.lds_words)));
-            const int park_depth = park_depth_setting();
-            const bool park = park_depth > 0 && !(p->flags & BDPT_FLAG_COUNT);
-            if (park) {
-                const size_t words = static_cast<size_t>(c->nslots) * (kParkSlotWords + 1) + 1;
-                if (!c->park) HIP_TRY(hipMalloc(&c->park, words * sizeof(uint32_t)));
-                HIP_TRY(hipMemsetAsync(c->park, 0, words * sizeof(uint32_t), st));
-                fr.park = c->park;
-                fr.park_depth = park_depth;
-                fr.park_flags = dev::kParkOn;
-            }
-            HIP_TRY(launch_rr(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, grid, st, c->dparams));
-            const int rounds = park ? park_rounds_setting() : 0;
-            uint32_t* const list = c->park + static_cast<size_t>(c->nslots) * kParkSlotWords;
-            for (int k = 0; k < rounds; k++) {
-                HIP_TRY(launch_chain_k(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, kChainGrid, st,
-                                       c->dparams));
-                HIP_TRY(hipMemsetAsync(list, 0, sizeof(uint32_t), st));  // the resume launch parks anew
-                dev::DevFrame fres = fr;
-                fres.park_flags = dev::kParkResume | (k + 1 < rounds ? dev::kParkOn : 0u);
-                HIP_TRY(launch_rr(sc, fres, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, grid, st, c->dparams));
-            }
-            launches += 2 * rounds;
-            c->last_kernel = chain ? "bdpt_frame_kernel_rrc" : "bdpt_frame_kernel_rr";
-        } else if (p->rr_depth > kLazyRrDepth) {  // never more resident blocks than the slots allocated
-            const int grid = std::min(c->grid, c->cus * frame_kernel_blocks_per_cu_deep(
-                                                           4 * static_cast<size_t>(c->sc.lds_words)));
-            HIP_TRY(launch_frame_deep(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, grid, st,
-                                      c->dparams));
-            c->last_kernel = "bdpt_frame_kernel_deep";
-        } else if (hbm) {
-            HIP_TRY(launch_frame_hbm(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, c->grid, st,
-                                     c->dparams));
-            c->last_kernel = "bdpt_frame_kernel_hbm";
-        } else if (use_split_build(p->rr_depth)) {  // never more resident blocks than the slots allocated
-            const int grid = std::min(c->grid, c->cus * frame_kernel_blocks_per_cu_split(
-                                                           4 * static_cast<size_t>(c->sc.lds_words)));
-            HIP_TRY(launch_frame_split(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, grid, st,
-                                       c->dparams));
-            c->last_kernel = "bdpt_frame_kernel_split";
-        } else {
-            // a table of diffuse, mirror and glass records only runs the build without the
-            // Mixture / Phong lobes (bdpt_kernels_ng.hip: a vertex that is not delta is diffuse
-            // there, so a null BSDF keeps the full build too); BDPT_NG_BUILD=0 forces the full
-            // build, =1 asks for the other and is ignored where the table does not allow it
-            const char* ne = std::getenv("BDPT_NG_BUILD");
-            const bool ng = !c->has_glossy && !c->has_null && !(ne && *ne == '0');
-            if (ng) {  // never more resident blocks than the slots allocated
-                const int grid = std::min(c->grid, c->cus * frame_kernel_blocks_per_cu_ng(
-                                                               4 * static_cast<size_t>(c->sc.lds_words)));
-                HIP_TRY(launch_frame_ng(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, grid, st,
-                                        c->dparams));
-                c->last_kernel_glossy = 0;
-            } else {
-                HIP_TRY(launch_frame(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, c->grid, st,
-                                     c->dparams));
-            }
-            c->last_kernel = "bdpt_frame_kernel";
+        const FrameBuild& b = pick_frame_build(c, p);
+        c->last_kernel_glossy = 1;  // (until the launches below have succeeded)
+        // Never more resident blocks than the slots allocated. c->grid is the default build's
+        // blocks_per_cu of these LDS bytes (the HBM build's on an HBM table; bdpt_ctx_create),
+        // so for those two builds the clamp changes nothing.
+        const int grid = std::min(c->grid, c->cus * b.blocks_per_cu(4 * static_cast<size_t>(c->sc.lds_words)));
+        // the Russian-roulette builds' continuation pass (park_depth_setting)
+        const int park_depth = b.launch_chain ? park_depth_setting() : 0;
+        const bool park = park_depth > 0 && !(p->flags & BDPT_FLAG_COUNT);
+        if (park) {
+            const size_t words = static_cast<size_t>(c->nslots) * (kParkSlotWords + 1) + 1;
+            if (!c->park) HIP_TRY(hipMalloc(&c->park, words * sizeof(uint32_t)));
+            HIP_TRY(hipMemsetAsync(c->park, 0, words * sizeof(uint32_t), st));
+            fr.park = c->park;
+            fr.park_depth = park_depth;
+            fr.park_flags = dev::kParkOn;
         }
-        launches += 1;
+        HIP_TRY(b.launch_frame(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, grid, st, c->dparams));
+        const int rounds = park ? park_rounds_setting() : 0;
+        for (int k = 0; k < rounds; k++) {
+            HIP_TRY(b.launch_chain(sc, fr, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, kChainGrid, st,
+                                   c->dparams));
+            uint32_t* const list = c->park + static_cast<size_t>(c->nslots) * kParkSlotWords;
+            HIP_TRY(hipMemsetAsync(list, 0, sizeof(uint32_t), st));  // the resume launch parks anew
+            dev::DevFrame fres = fr;
+            fres.park_flags = dev::kParkResume | (k + 1 < rounds ? dev::kParkOn : 0u);
+            HIP_TRY(b.launch_frame(sc, fres, fb, c->lv, c->gstack, c->nslots, c->work, c->counters, grid, st,
+                                   c->dparams));
+        }
+        c->last_kernel = b.name;
+        c->last_kernel_glossy = b.glossy;
+        launches += 1 + 2 * rounds;
     }
     HIP_TRY(hipEventRecord(c->ev1, st));
     if ((rc = end_use(c, st))) return rc;

@@ -18,13 +18,6 @@ constexpr float kInvTwoPi = 0.15915494309189533577f;  // platform.h:52
 constexpr float kEpsilon = 1e-8f;                     // platform.h:56
 constexpr float kTriMinT = 0x1.0624dep-10f;           // smallest float t with (double)t > 1e-3 (accel.h:43)
 constexpr int kCounters = 32;
-#ifndef BDPT_HELP_CLOCKS
-#define BDPT_HELP_CLOCKS 0  // (bdpt_kernels.hip) the stack-depth probe words carry other clocks
-#endif
-
-#ifndef BDPT_TRAV_WHILE_WHILE
-#define BDPT_TRAV_WHILE_WHILE 1  // megakernel traversal loop shape (0: one node or leaf per iteration)
-#endif
 
 // ------------------------------------------------------------------ inputs
 // Loads through an address-space-1 pointer compile to global_load (SGPR/VGPR
@@ -49,10 +42,7 @@ __device__ __forceinline__ void gst2(float2* p, float2 x) { *(__attribute__((add
 
 // Bytes of a shadow-ray task record in the waves' rings (bdpt_path.hpp task_push;
 // the host sizes DevFrame::tasks by it).
-#ifndef BDPT_HELP_SOA
-#define BDPT_HELP_SOA 1  // the ring as planes of 16- and 8-byte vectors (consecutive slots' pushes and claims coalesce)
-#endif
-constexpr uint32_t kTaskBytes = BDPT_HELP_SOA ? 40 : 48;  // 0: whole records of 3 float4 (the last half unused)
+constexpr uint32_t kTaskBytes = 40;
 
 struct DevScene {
     const float4* __restrict__ tri;
@@ -95,7 +85,7 @@ struct DevScene {
     // in o - v0), so the reference can accept a triangle the ray's line misses by
     // more than the traversal tree's padding.
     float near_lo[3], near_hi[3];
-    uint32_t q_ok;  // qnodes present: the BDPT_QNODES kernels walk the 4-wide tree (else the binary one)
+    uint32_t q_ok;  // qnodes present (no kernel reads them: the walk takes the float records, wnodes)
     uint32_t gdepth;  // traversal-stack overflow entries per lane slot (beyond the LDS ones)
     // Bitmap textures (null without; read by the BDPT_TEXTURED builds only): per material two
     // int4 records — diffuse, specular map: (first texel's index in this table, w, h, 0), index
@@ -542,10 +532,6 @@ __device__ __forceinline__ f3 uniform_hemisphere(F2 u) {
 __device__ __forceinline__ f3 cosine_hemisphere(F2 u) {
     float rx = (2.f * u.x) - 1.f;
     float ry = (2.f * u.y) - 1.f;
-#ifndef BDPT_DISK_SELECT
-#define BDPT_DISK_SELECT 1
-#endif
-#if BDPT_DISK_SELECT
     // Both branches of the reference as selects (one division, one sincos per
     // lane, same operations and bits); the (0, 0) sample keeps dx = dy = 0.
     const bool zero = rx == 0 && ry == 0;
@@ -556,22 +542,6 @@ __device__ __forceinline__ f3 cosine_hemisphere(F2 u) {
     const SinCos sc = glibc_sincosf2(phi);
     const float dx = zero ? 0.f : radius * sc.c;
     const float dy = zero ? 0.f : radius * sc.s;
-#else
-    float dx = 0.f, dy = 0.f;
-    if (!(rx == 0 && ry == 0)) {
-        float radius, phi;
-        if ((rx * rx) > (ry * ry)) {
-            radius = rx;
-            phi = (kPi * 0.25f) * (ry * rcp_cr(rx));
-        } else {
-            radius = ry;
-            phi = (kPi * 0.5f) - ((kPi * 0.25f) * (rx * rcp_cr(ry)));
-        }
-        const SinCos sc = glibc_sincosf2(phi);
-        dx = radius * sc.c;
-        dy = radius * sc.s;
-    }
-#endif
     float z = 1.0f - (dx * dx + dy * dy);
     z = glibc_fmaxf(z, 0.f);
     return mk(dx, dy, sqrt_cr(z));
@@ -598,17 +568,7 @@ __device__ __forceinline__ F2 uniform_triangle(F2 s) {
 
 // -------------------------------------------------------------------- frame
 // Frame(n) with coordinateSystem (core.h:155-157, math.h:42-51): t = c, s = cross(c, n).
-#ifndef BDPT_FRAME_SELECT
-#define BDPT_FRAME_SELECT 0  // 1: the operand selected first, one sqrt + division per lane
-#endif
 __device__ __forceinline__ void make_frame(f3 a, f3& s, f3& t) {
-#if BDPT_FRAME_SELECT
-    const bool xb = fabsf(a.x) > fabsf(a.y);
-    const float u = xb ? a.x : a.y;
-    const float inv = rcp_cr(sqrt_cr(u * u + a.z * a.z));
-    const float w = a.z * inv, m = -u * inv;
-    t = xb ? mk(w, 0.f, m) : mk(0.f, w, m);
-#else
     if (fabsf(a.x) > fabsf(a.y)) {
         float inv = rcp_cr(sqrt_cr(a.x * a.x + a.z * a.z));
         t = mk(a.z * inv, 0.f, -a.x * inv);
@@ -616,7 +576,6 @@ __device__ __forceinline__ void make_frame(f3 a, f3& s, f3& t) {
         float inv = rcp_cr(sqrt_cr(a.y * a.y + a.z * a.z));
         t = mk(0.f, a.z * inv, -a.y * inv);
     }
-#endif
     s = cross(t, a);
 }
 __device__ __forceinline__ f3 to_local(f3 s, f3 t, f3 n, f3 v) { return mk(dot(v, s), dot(v, t), dot(v, n)); }
@@ -666,10 +625,7 @@ __device__ __forceinline__ bool slab(float lx, float ly, float lz, float hx, flo
 // hit / miss outcome is always the reference's. Rays whose reciprocal
 // direction or origin is not finite (where 0 * inf = NaN could arise) take
 // slab() for every box (RayInv::fast == false).
-#ifndef BDPT_CULL_NEAR
-#define BDPT_CULL_NEAR 1  // 0: no box is culled for lying before t = 5e-4 (only the far cull remains)
-#endif
-constexpr float kCullNear = BDPT_CULL_NEAR ? 5e-4f : -__builtin_huge_valf();
+constexpr float kCullNear = 5e-4f;
 // The near cull assumes Moller-Trumbore puts a hit where the ray meets its
 // triangle. For a ray nearly parallel to a triangle's plane whose origin lies on
 // that plane (a grazing ray leaving a surface) the computed t, u, v are rounding
@@ -686,29 +642,17 @@ constexpr float kGrazeCos = 0.02f;
 // kGrazeCos + code / 64 covers every |dot(d, n_g)| < kGrazeCos. Code 0 (flat
 // triangles: n_s is n_g) leaves the plain test.
 __device__ __forceinline__ int shape_id(int packed) { return packed & 0xffffff; }
-#ifndef BDPT_GRAZE
-#define BDPT_GRAZE 1  // 0: the plain |cos| < kGrazeCos test (A/B only; not exact on smooth meshes)
-#endif
 __device__ __forceinline__ float graze_threshold(int packed) {
-    return BDPT_GRAZE ? kGrazeCos + static_cast<float>(static_cast<uint32_t>(packed) >> 24) * 0.015625f : kGrazeCos;
+    return kGrazeCos + static_cast<float>(static_cast<uint32_t>(packed) >> 24) * 0.015625f;
 }
 __device__ __forceinline__ bool graze_exempt(f3 d, f3 n, int packed) { return fabsf(dot(d, n)) < graze_threshold(packed); }
-#ifndef BDPT_SLAB_FMA
-#define BDPT_SLAB_FMA 2  // slack-free interior boxes by one fma per plane (slab_fma; 1: o inv formed per node step; 0: slab_fast)
-#endif
 enum : int { kSlabMiss = 0, kSlabHit = 1, kSlabAmbiguous = 2 };
 struct RayInv {
     f3 inv;
     bool fast;
     float near;  // boxes left before t = near are culled (kCullNear, or -inf: no near cull, see cull_near_for)
 };
-#ifndef BDPT_QNODES
-#define BDPT_QNODES 0  // 1: the walk reads the 64-byte compressed node records (wide_bvh.hpp quantize_wide_nodes)
-#endif
 __device__ __forceinline__ bool far_origin(const DevScene& sc, f3 o) {
-#if BDPT_QNODES
-    if (!sc.q_ok) return true;  // no compressed records: every query walks the reference's tree
-#endif
     return !(o.x >= sc.near_lo[0] && o.x <= sc.near_hi[0] && o.y >= sc.near_lo[1] && o.y <= sc.near_hi[1] &&
              o.z >= sc.near_lo[2] && o.z <= sc.near_hi[2]);
 }
@@ -718,20 +662,10 @@ __device__ __forceinline__ RayInv ray_inv(const Ray& r, float near) {
     RayInv ri;
     ri.near = near;
     ri.inv = mk(rcp_cr(r.d.x), rcp_cr(r.d.y), rcp_cr(r.d.z));
-#if BDPT_SLAB_FMA
     // slab_fma's o inv must be finite too
     const float probe = (ri.inv.x + ri.inv.y + ri.inv.z) * 0.f + ((r.o.x + r.o.y + r.o.z) * 0.f) +
                         ((r.o.x * ri.inv.x + r.o.y * ri.inv.y + r.o.z * ri.inv.z) * 0.f);
-#else
-    const float probe = (ri.inv.x + ri.inv.y + ri.inv.z) * 0.f + ((r.o.x + r.o.y + r.o.z) * 0.f);
-#endif
     ri.fast = (probe == 0.f);  // false iff some component is +-inf or NaN
-#if BDPT_QNODES
-    // the compressed records' 2^e / d must stay normal and finite (wide_bvh.hpp kQuantExpMin/Max)
-    const float m = fmaxf(fmaxf(fabsf(ri.inv.x), fabsf(ri.inv.y)), fabsf(ri.inv.z));
-    const float n = fminf(fminf(fabsf(ri.inv.x), fabsf(ri.inv.y)), fabsf(ri.inv.z));
-    ri.fast = ri.fast && m <= 0x1p96f && n >= 0x1p-40f;
-#endif
     return ri;
 }
 __device__ __forceinline__ int slab_planes(float x0, float x1, float y0, float y1, float z0, float z1, float& tn,
@@ -758,9 +692,6 @@ __device__ __forceinline__ int slab_fast(float lx, float ly, float lz, float hx,
 // it stays below slab_fast's own bound and inside the boxes' padding.
 __device__ __forceinline__ f3 slab_fma_origin(f3 o, f3 inv) {
     f3 oi = mk(-(o.x * inv.x), -(o.y * inv.y), -(o.z * inv.z));
-#if BDPT_SLAB_FMA == 1
-    asm volatile("" : "+v"(oi.x), "+v"(oi.y), "+v"(oi.z));  // formed per node step, not held across the walk
-#endif
     return oi;
 }
 __device__ __forceinline__ void slab_fma(float lx, float ly, float lz, float hx, float hy, float hz, f3 oi, f3 inv,
@@ -843,23 +774,12 @@ constexpr uint32_t kEmptyLinkDev = 0xffffffffu;  // unused 4-wide child slot
 // the generic pointers the compiler merged the two branches into one FLAT
 // access, and every FLAT load waits for vmcnt(0) and lgkmcnt(0) together —
 // each pop then also waited for all of the wave's outstanding global loads.
-#ifndef BDPT_STACK_AS
-#define BDPT_STACK_AS 1
-#endif
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-#if BDPT_STACK_AS
 typedef __attribute__((address_space(3))) u32x2 lds_uint2;
 typedef __attribute__((address_space(1))) u32x2 gbl_uint2;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef __attribute__((address_space(1))) uint32_t gbl_u32;
 typedef __attribute__((address_space(1))) int32_t gbl_i32;
-#else
-typedef u32x2 lds_uint2;
-typedef u32x2 gbl_uint2;
-typedef uint32_t lds_u32;
-typedef uint32_t gbl_u32;
-typedef int32_t gbl_i32;
-#endif
 // threadIdx.x, re-read at each use (opaque to the optimiser): per-lane
 // addresses derived from it at their use are not held in registers across the
 // persistent loop (only threadIdx.x itself is).
@@ -914,19 +834,12 @@ struct LinkStack {
 // ALL reachable leaves, first-found (= lowest leaf index) on ties. Boxes
 // entered beyond best + margin, or exited before t = 5e-4, cannot hold a
 // triangle that changes that result.
-#ifndef BDPT_CULL_FMA
-#define BDPT_CULL_FMA 1  // the margin's product and sum as one fma (the same bound within an ulp; the margin is 1e-3 relative)
-#endif
 __device__ __forceinline__ float cull_far(float best) {
-    return BDPT_CULL_FMA ? fmaf(fabsf(best), 1e-3f, best) + 1e-4f : best + fabsf(best) * 1e-3f + 1e-4f;
+    return fmaf(fabsf(best), 1e-3f, best) + 1e-4f;
 }
-// The far bound of a walk in progress. An occlusion query's best_t stays its
-// max_t (trav_begin; wleaf_tests returns at its first hit without lowering it),
-// so ts.best_t serves both kinds of query.
-#ifndef BDPT_FAR_BEST
-#define BDPT_FAR_BEST 1  // 0: the select on the query kind (with CULL_FMA and ROOT_NF: Caustic +0.65 %, HardLight +0.65 %, synth1m +0.6 %)
-#endif
-#define BDPT_WALK_FAR(any, r, ts) cull_far(BDPT_FAR_BEST ? (ts).best_t : ((any) ? (r).max_t : (ts).best_t))
+// (A walk in progress passes ts.best_t for either kind of query: an occlusion
+// query's best_t stays its max_t — trav_begin; wleaf_tests returns at its first
+// hit without lowering it.)
 
 struct Counts {
     uint32_t c[kCounters];
@@ -958,21 +871,12 @@ __device__ __forceinline__ int lanes_below(uint64_t m) {
 }
 
 // Lane i's value in every lane, for a wave-uniform i: v_readlane (a scalar
-// result, a few cycles) where __shfl's ds_bpermute takes an LDS round trip
-// (BDPT_READLANE; 0 keeps the shuffles). The value is the lane's register whether
-// or not it is active.
-#ifndef BDPT_READLANE
-#define BDPT_READLANE 1
-#endif
-#if BDPT_READLANE
+// result, a few cycles) where __shfl's ds_bpermute takes an LDS round trip.
+// The value is the lane's register whether or not it is active.
 __device__ __forceinline__ int lane_val(int x, int i) { return __builtin_amdgcn_readlane(x, i); }
 __device__ __forceinline__ float lane_val(float x, int i) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), i));
 }
-#else
-__device__ __forceinline__ int lane_val(int x, int i) { return __shfl(x, i); }
-__device__ __forceinline__ float lane_val(float x, int i) { return __shfl(x, i); }
-#endif
 
 // SIMD-efficiency probe: true on the lowest active lane of the wave only.
 __device__ __forceinline__ bool first_active_lane() {
@@ -990,38 +894,11 @@ __device__ __forceinline__ bool first_active_lane() {
 #ifndef BDPT_LEAF_GROUP
 #define BDPT_LEAF_GROUP 1
 #endif
-#ifndef BDPT_LEAF_PIPELINE
-#define BDPT_LEAF_PIPELINE 0  // 1: fetch triangle k + 1 while testing triangle k
-#endif
 template <bool COUNT>
 __device__ __forceinline__ bool leaf_tests(const float4* __restrict__ tri, uint32_t link, const Ray& r, bool any, float& best_t,
                                            int& best, float& best_u, float& best_v, uint32_t& tri_count) {
     constexpr uint32_t G = BDPT_LEAF_GROUP;
     const uint32_t start = (link >> 3) & 0x0fffffffu, count = link & 7u;
-#if BDPT_LEAF_PIPELINE
-    float4 n0 = gld4(tri + 3 * start), n1 = gld4(tri + 3 * start + 1), n2 = gld4(tri + 3 * start + 2);
-    for (uint32_t k = 0; k < count; k++) {
-        const float4 a0 = n0, a1 = n1, a2 = n2;
-        const uint32_t nx = start + (k + 1 < count ? k + 1 : k);
-        n0 = gld4(tri + 3 * nx), n1 = gld4(tri + 3 * nx + 1), n2 = gld4(tri + 3 * nx + 2);
-        asm volatile("" ::"v"(a0.x), "v"(a0.y), "v"(a0.z), "v"(a1.x), "v"(a1.y), "v"(a1.z), "v"(a2.x), "v"(a2.y),
-                     "v"(a2.z));
-        const uint32_t i = start + k;
-        float t, u, v;
-        if (COUNT) tri_count++;
-        if (tri_test_edges(xyz(a0), xyz(a1), xyz(a2), r, t, u, v)) {
-            if (any) {
-                if (t <= r.max_t && t >= r.min_t) {
-                    best = 1;
-                    return true;
-                }
-            } else if (t < best_t || (t == best_t && best >= 0 && static_cast<int>(i) < best)) {
-                best_t = t, best = static_cast<int>(i), best_u = u, best_v = v;
-            }
-        }
-    }
-    return false;
-#endif
     for (uint32_t k0 = 0; k0 < count; k0 += G) {
         float4 q[G][3];
 #pragma unroll
@@ -1125,7 +1002,7 @@ __device__ __forceinline__ int child_fast(float lx, float hx, float ly, float hy
 struct TravScene {
     const float4* __restrict__ wtri;
     const float4* __restrict__ lbox;
-    const float4* __restrict__ wnodes;  // the records the walk reads (qnodes in the BDPT_QNODES build)
+    const float4* __restrict__ wnodes;  // the records the walk reads
     uint32_t wroot_link;
     uint32_t node_slack;  // 0: interior boxes tested without the ambiguity slack (DevScene::node_slack)
 };
@@ -1136,7 +1013,7 @@ __device__ __forceinline__ const float4* uniform_ptr(const float4* p) {
     return reinterpret_cast<const float4*>((static_cast<uint64_t>(hi) << 32) | lo);
 }
 __device__ __forceinline__ TravScene trav_scene(const DevScene& sc) {
-    return TravScene{uniform_ptr(sc.wtri), uniform_ptr(sc.lbox), uniform_ptr(BDPT_QNODES ? sc.qnodes : sc.wnodes),
+    return TravScene{uniform_ptr(sc.wtri), uniform_ptr(sc.lbox), uniform_ptr(sc.wnodes),
                      static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(sc.wroot_link))),
                      static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(sc.node_slack)))};
 }
@@ -1200,7 +1077,7 @@ __device__ __forceinline__ bool trav_pop(const Ray& r, bool any, TravState& ts, 
                                          uint32_t* culled = nullptr) {
     while (ts.sp > 0) {
         const uint2 e = stk.get(--ts.sp);
-        if (!(__uint_as_float(e.y) > BDPT_WALK_FAR(any, r, ts))) {
+        if (!(__uint_as_float(e.y) > cull_far(ts.best_t))) {
             ts.link = e.x;
             return true;
         }
@@ -1210,14 +1087,8 @@ __device__ __forceinline__ bool trav_pop(const Ray& r, bool any, TravState& ts, 
 }
 
 // A 4-wide node record as the walk reads it: the 128-byte float record
-// (wide_bvh.hpp; v[0..5] = lo.x hi.x lo.y hi.y lo.z hi.z, v[6] = links) or, in
-// the BDPT_QNODES build, the 64-byte compressed one (v[0] = grid origin and
-// exponents, v[1..2] = 8-bit child bounds, v[3] = links).
-#if BDPT_QNODES
-constexpr int kNodeVecs = 4, kNodeStride = 4, kNodeLinks = 3;
-#else
+// (wide_bvh.hpp; v[0..5] = lo.x hi.x lo.y hi.y lo.z hi.z, v[6] = links).
 constexpr int kNodeVecs = 7, kNodeStride = 8, kNodeLinks = 6;
-#endif
 struct WNode {
     float4 v[kNodeVecs];
 };
@@ -1228,13 +1099,6 @@ __device__ __forceinline__ WNode load_wnode(const float4* __restrict__ base, uin
     for (int j = 0; j < kNodeVecs; j++) n.v[j] = gld4(nd + j);
     return n;
 }
-#ifndef BDPT_SLAB_SIGN
-#define BDPT_SLAB_SIGN 2  // slack-free interior test: each axis's near / far planes picked by the ray's sign at the load (1: the offsets formed per node step; 0: off)
-#endif
-#ifndef BDPT_HIT_MERGE
-#define BDPT_HIT_MERGE 1  // that test's culls as one comparison, max(tn, near) <= min(tf, far)
-#endif
-#if !BDPT_QNODES && BDPT_SLAB_SIGN
 // The node as the slack-free test reads it (NF): v[0] / v[1] the near / far x
 // planes of the four children for this ray — lo.x / hi.x when d.x > 0, hi.x /
 // lo.x otherwise (RayInv::fast: inv is finite and nonzero) — likewise v[2..5] for
@@ -1251,9 +1115,6 @@ __device__ __forceinline__ WNode load_wnode_nf(const float4* __restrict__ base, 
     const char* b = reinterpret_cast<const char*>(base);
     const uint32_t off = link << 7;
     uint32_t sx = plane_sel(inv.x), sy = plane_sel(inv.y), sz = plane_sel(inv.z);
-#if BDPT_SLAB_SIGN == 1
-    asm volatile("" : "+v"(sx), "+v"(sy), "+v"(sz));  // formed per node step, not held across the walk
-#endif
     const uint32_t ax = off | sx, ay = off | sy, az = off | sz;
     WNode n;
     n.v[0] = gld4(reinterpret_cast<const float4*>(b + ax));
@@ -1265,10 +1126,6 @@ __device__ __forceinline__ WNode load_wnode_nf(const float4* __restrict__ base, 
     n.v[6] = gld4(reinterpret_cast<const float4*>(b + off + 96));
     return n;
 }
-#endif
-__device__ __forceinline__ float qbyte(float w, int c) {  // byte c of the word, as a float (v_cvt_f32_ubyteN)
-    return static_cast<float>((__float_as_uint(w) >> (8 * c)) & 0xffu);
-}
 
 // Interior 4-wide node ts.link: tests the four children, descends into the
 // nearest hit child (true) and stacks the others far-to-near; false when no
@@ -1279,9 +1136,7 @@ __device__ __forceinline__ bool trav_node_vals(const WNode& n, const Ray& r, con
 template <bool COUNT, bool SLACK>
 __device__ __forceinline__ bool trav_node(const TravScene& sc, const Ray& r, const RayInv& ri, bool any, TravState& ts,
                                           const Stack& stk, Counts& cnt) {
-#if !BDPT_QNODES && BDPT_SLAB_SIGN
     if (!SLACK) return trav_node_vals<COUNT, false, true>(load_wnode_nf(sc.wnodes, ts.link, ri.inv), r, ri, any, ts, stk, cnt);
-#endif
     return trav_node_vals<COUNT, SLACK>(load_wnode(sc.wnodes, ts.link), r, ri, any, ts, stk, cnt);
 }
 // The four children of a 4-wide node: key = entry distance of each child the
@@ -1291,48 +1146,28 @@ template <bool SLACK, bool NF = false>
 __device__ __forceinline__ void node_child_keys(const WNode& n, const Ray& r, const RayInv& ri, float far, float (&key)[4],
                                                 uint32_t (&lnk)[4]) {
     const float4 lk = n.v[kNodeLinks];
-#if BDPT_QNODES
-    // plane distance of bound org + q 2^e: fma(q, 2^e / d, (org - o) / d); 2^e / d is exact
-    const uint32_t eb = __float_as_uint(n.v[0].w);
-    const float ax = __uint_as_float((eb & 0xffu) << 23) * ri.inv.x;
-    const float ay = __uint_as_float(((eb >> 8) & 0xffu) << 23) * ri.inv.y;
-    const float az = __uint_as_float(((eb >> 16) & 0xffu) << 23) * ri.inv.z;
-    const float bx = (n.v[0].x - r.o.x) * ri.inv.x, by = (n.v[0].y - r.o.y) * ri.inv.y,
-                bz = (n.v[0].z - r.o.z) * ri.inv.z;
-#else
-    const f3 oi = SLACK || !(BDPT_SLAB_FMA || NF) ? mk(0.f, 0.f, 0.f) : slab_fma_origin(r.o, ri.inv);
-#endif
+    const f3 oi = SLACK ? mk(0.f, 0.f, 0.f) : slab_fma_origin(r.o, ri.inv);
 #pragma unroll
     for (int c = 0; c < 4; c++) {
         const uint32_t l = __float_as_uint((&lk.x)[c]);
         float tn, tf;
-#if BDPT_QNODES
-        const int d = slab_planes(fmaf(qbyte(n.v[1].x, c), ax, bx), fmaf(qbyte(n.v[1].y, c), ax, bx),
-                                  fmaf(qbyte(n.v[1].z, c), ay, by), fmaf(qbyte(n.v[1].w, c), ay, by),
-                                  fmaf(qbyte(n.v[2].x, c), az, bz), fmaf(qbyte(n.v[2].y, c), az, bz), tn, tf);
-#else
         const float clx = (&n.v[0].x)[c], chx = (&n.v[1].x)[c], cly = (&n.v[2].x)[c], chy = (&n.v[3].x)[c],
                     clz = (&n.v[4].x)[c], chz = (&n.v[5].x)[c];
         int d = kSlabHit;
         if (NF) {  // v[0], v[2], v[4]: near planes; v[1], v[3], v[5]: far planes (load_wnode_nf)
             tn = fmaxf(fmaxf(fmaf(clx, ri.inv.x, oi.x), fmaf(cly, ri.inv.y, oi.y)), fmaf(clz, ri.inv.z, oi.z));
             tf = fminf(fminf(fmaf(chx, ri.inv.x, oi.x), fmaf(chy, ri.inv.y, oi.y)), fmaf(chz, ri.inv.z, oi.z));
-        } else if (SLACK || !BDPT_SLAB_FMA) {
+        } else if (SLACK) {
             d = slab_fast(clx, cly, clz, chx, chy, chz, r.o, ri.inv, tn, tf);
         } else {
             slab_fma(clx, cly, clz, chx, chy, chz, oi, ri.inv, tn, tf);
         }
-#endif
         const bool pass = SLACK ? d != kSlabMiss : !(tn > tf);
-#if BDPT_HIT_MERGE
         // !(tn > tf), !(tn > far) and !(tf < near) as one comparison: it also drops the
         // boxes when far < near, where no hit can be accepted (the query's max_t or
         // best hit lies below kTriMinT); tn, tf are finite here (RayInv::fast)
         const bool hit = NF ? l != kEmptyLinkDev && !(fmaxf(tn, ri.near) > fminf(tf, far))
                             : l != kEmptyLinkDev && pass && !(tn > far) && !(tf < ri.near);
-#else
-        const bool hit = l != kEmptyLinkDev && pass && !(tn > far) && !(tf < ri.near);
-#endif
         key[c] = hit ? tn : __builtin_inff();
         lnk[c] = hit ? l : kEmptyLinkDev;
     }
@@ -1353,12 +1188,12 @@ __device__ __forceinline__ bool trav_node_vals(const WNode& n, const Ray& r, con
     if (COUNT) cnt.c[2]++;
     float key[4];
     uint32_t lnk[4];
-    node_child_keys<SLACK, NF>(n, r, ri, BDPT_WALK_FAR(any, r, ts), key, lnk);
+    node_child_keys<SLACK, NF>(n, r, ri, cull_far(ts.best_t), key, lnk);
     if (lnk[0] == kEmptyLinkDev) return false;
     if (lnk[3] != kEmptyLinkDev) stk.put(ts.sp++, lnk[3], key[3]);
     if (lnk[2] != kEmptyLinkDev) stk.put(ts.sp++, lnk[2], key[2]);
     if (lnk[1] != kEmptyLinkDev) stk.put(ts.sp++, lnk[1], key[1]);
-    if (COUNT && !BDPT_HELP_CLOCKS) {  // stack-depth probe: entries held at depth >= 8, >= 12, >= 16
+    if (COUNT) {  // stack-depth probe: entries held at depth >= 8, >= 12, >= 16
         cnt.c[16] += ts.sp > 8 ? ts.sp - 8 : 0;
         cnt.c[17] += ts.sp > 12 ? ts.sp - 12 : 0;
         cnt.c[18] += ts.sp > 16 ? ts.sp - 16 : 0;
@@ -1377,23 +1212,10 @@ struct RootLds {
     WNode root;
     WNode kid[4];
 };
-#ifndef BDPT_COOP_ROOT_LDS
-#define BDPT_COOP_ROOT_LDS 0  // cooperative walks read the root and its children from the block's LDS copy
-#endif
 __device__ __forceinline__ bool root_lds_usable(const DevScene& sc) { return !(sc.wroot_link & kLeafBit); }
-__device__ __forceinline__ WNode coop_node(const TravScene& sc, uint32_t link, const RootLds* rl) {
-    if (BDPT_COOP_ROOT_LDS && rl) {
-        if (link == sc.wroot_link) return rl->root;
-        const float4 lk = rl->root.v[kNodeLinks];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (link == __float_as_uint((&lk.x)[k])) return rl->kid[k];  // (a leaf link never reaches here)
-    }
-    return load_wnode(sc.wnodes, link);
-}
 __device__ __forceinline__ void root_lds_fill(RootLds& m, const DevScene& sc) {
     if (!root_lds_usable(sc)) return;
-    const float4* const base = BDPT_QNODES ? sc.qnodes : sc.wnodes;
+    const float4* const base = sc.wnodes;
     const float4* rn = base + kNodeStride * static_cast<size_t>(sc.wroot_link);
     if (threadIdx.x < kNodeVecs) {
         m.root.v[threadIdx.x] = gld4(rn + threadIdx.x);
@@ -1406,10 +1228,6 @@ __device__ __forceinline__ void root_lds_fill(RootLds& m, const DevScene& sc) {
 }
 // The root and (when the walk descends into an interior child) that child;
 // false when the query is already complete (a miss: nothing below was hit).
-#ifndef BDPT_ROOT_NF
-#define BDPT_ROOT_NF 1  // the LDS root and children through the sign-picked planes too (lds_wnode_nf)
-#endif
-#if !BDPT_QNODES && BDPT_SLAB_SIGN && BDPT_ROOT_NF
 // load_wnode_nf's plane vectors from an LDS copy of a node (the same 16-byte
 // vectors at the same offsets: the copy is the record's first 112 bytes)
 __device__ __forceinline__ WNode lds_wnode_nf(const WNode& m, f3 inv) {
@@ -1425,13 +1243,10 @@ __device__ __forceinline__ WNode lds_wnode_nf(const WNode& m, f3 inv) {
     n.v[6] = m.v[6];
     return n;
 }
-#endif
 template <bool COUNT, bool SLACK>
 __device__ __forceinline__ bool root_node_vals(const WNode& m, const Ray& r, const RayInv& ri, bool any, TravState& ts,
                                                const Stack& stk, Counts& cnt) {
-#if !BDPT_QNODES && BDPT_SLAB_SIGN && BDPT_ROOT_NF
     if (!SLACK) return trav_node_vals<COUNT, false, true>(lds_wnode_nf(m, ri.inv), r, ri, any, ts, stk, cnt);
-#endif
     return trav_node_vals<COUNT, SLACK>(m, r, ri, any, ts, stk, cnt);
 }
 template <bool COUNT, bool SLACK>
@@ -1510,71 +1325,31 @@ __device__ __forceinline__ int traverse(const DevScene& sc, const Ray& r, bool a
     }
     const TravScene tsc = trav_scene(sc);
     TravState ts = trav_begin(tsc, r);
-#if BDPT_TRAV_WHILE_WHILE
     trav_while_while<COUNT>(tsc, r, ri, any, ts, stk, cnt);
-#else
-    if (tsc.node_slack) {  // a query-level (uniform) choice: the node step itself has no branch on it
-        while (!trav_step<COUNT, true>(tsc, r, ri, any, ts, stk, cnt)) {
-        }
-    } else {
-        while (!trav_step<COUNT, false>(tsc, r, ri, any, ts, stk, cnt)) {
-        }
-    }
-#endif
     bt = ts.best_t, bu = ts.best_u, bv = ts.best_v;
     return ts.best;
 }
 
 // The closest hit of ONE ray (the same in every lane of the wave) walked by the
-// whole wave: each round pops up to 64 pending entries (one per lane) from an
-// LDS stack, tests them (a 4-wide node: node_child_keys; a leaf: wleaf_tests
-// against the best so far), takes the lexicographic minimum (t, reference
-// index) over the lanes and pushes the children far-first. The result is the
-// serial walk's: the minimum over the candidates of every entry the walk cannot
-// cull (the same conservative per-entry tests, cull_far of the best so far), ties
-// to the lowest reference index, accepted only below r.max_t — the order the
-// entries are visited in does not enter it. For the Russian-roulette
-// continuation pass (bdpt_kernels.hip, chain kernel): a trapped subpath's walk
-// takes ~9 rounds instead of ~30 dependent steps. `stack` holds `cap` entries;
-// false if they did not suffice (the caller reports it). With bound < r.max_t
-// only candidates below `bound` are accepted (and entries beyond it culled): a
-// hit found is then the same result — the minimum over all candidates lies below
-// it — and none found (best -1) means the walk must be repeated unbounded.
+// whole wave (coop_closest below): each round pops pending entries from an LDS
+// stack, tests them (a 4-wide node's children, a leaf's triangles against the
+// best so far), takes the lexicographic minimum (t, reference index) over the
+// lanes and pushes the children. The result is the serial walk's: the minimum
+// over the candidates of every entry the walk cannot cull (the same conservative
+// per-entry tests, cull_far of the best so far), ties to the lowest reference
+// index, accepted only below r.max_t — the order the entries are visited in does
+// not enter it. For the Russian-roulette build's trapped subpaths (bdpt_kernels.hip,
+// express mode and the chain kernel): a walk takes ~9 rounds instead of ~30
+// dependent steps. `stack` holds `cap` entries; false if they did not suffice
+// (the caller reports it). With bound < r.max_t only candidates below `bound`
+// are accepted (and entries beyond it culled): a hit found is then the same
+// result — the minimum over all candidates lies below it — and none found
+// (best -1) means the walk must be repeated unbounded.
 __device__ __forceinline__ uint64_t coop_key(float t, int idx) {
     const uint32_t b = __float_as_uint(t);
     const uint32_t o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);  // float order as unsigned order
     return (static_cast<uint64_t>(o) << 32) | static_cast<uint32_t>(idx);
 }
-// A leaf of up to 4 triangles (the triangle tree's kTriLeafMax) for coop_closest:
-// every triangle's loads issued before the first test (wleaf_tests' loop waits
-// for each triangle in turn); the same acceptance rule, so the same minimum.
-__device__ __forceinline__ void coop_leaf(const TravScene& sc, uint32_t link, const Ray& r, const RayInv& ri, float& bt,
-                                          int& bb, float& bu, float& bv) {
-    const uint32_t start = (link >> 3) & 0x0fffffffu, count = link & 7u;
-    Counts cnt;  // (not a counting pass)
-    if (count > 4) {
-        wleaf_tests<false>(sc.wtri, sc.lbox, link, r, ri, false, bt, bb, bu, bv, cnt);
-        return;
-    }
-    float4 q[4][3];
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++)
-        if (k < count) {
-            const float4* p = sc.wtri + 3 * static_cast<size_t>(start + k);
-            q[k][0] = gld4(p), q[k][1] = gld4(p + 1), q[k][2] = gld4(p + 2);
-        }
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++) {
-        if (k >= count) break;
-        float t, u, v;
-        if (!tri_test_edges(xyz(q[k][0]), xyz(q[k][1]), xyz(q[k][2]), r, t, u, v)) continue;
-        const int idx = __float_as_int(q[k][0].w);
-        if ((t < bt || (t == bt && bb >= 0 && idx < bb)) &&
-            ref_leaf_passes<false>(sc.lbox, __float_as_uint(q[k][1].w), r, ri, cnt))
-            bt = t, bb = idx, bu = u, bv = v;
-    }
-}
-
 // The walk's LDS stack: entry e at base[e] (a wave's own array), or spread over
 // the columns a wave's lanes own in a block's per-lane stack (entry e at
 // base[(e / 64) * stride + e % 64], base = the wave's first lane).
@@ -1586,33 +1361,14 @@ struct CoopStack {
         return (coop_lds_e*)base + (stride ? (e >> 6) * stride + (e & 63) : e);
     }
 };
-// A node of a cooperative walk: from the block's LDS copy when it is the root or
-// one of its interior children (RootLds; rl non-null), else from HBM. The
-// trapped glass chains' walks start at the root, so their first two rounds read
-// LDS instead of waiting on two dependent loads (BDPT_COOP_ROOT_LDS).
-struct RootLds;
-__device__ __forceinline__ WNode coop_node(const TravScene& sc, uint32_t link, const RootLds* rl);
-#ifndef BDPT_COOP_CP
-#define BDPT_COOP_CP 1  // coop_closest walks 16 entries per round, one child box / leaf triangle per lane (coop_closest_cp)
-#endif
-#if BDPT_COOP_CP && !BDPT_QNODES
-// coop_closest with the work of an entry spread over 4 lanes: each round pops up
-// to 16 entries, and lane 4s + c takes child c of entry s (its six planes and its
-// link: seven dword loads instead of the node's seven 16-byte vectors) or the
-// leaf's triangles c, c + 4 — one box or triangle test per lane where the
-// 64-entry round ran four box tests, a sort and up to four triangle tests in every
-// busy lane. A lone walk's frontier rarely holds more than 16 entries, and a
-// round of one wave alone on its SIMD costs its instructions, not its loads. The
-// per-child test is node_child_keys' (slab_fast with the slack, slab_fma without;
-// the same culls), the per-triangle acceptance coop_leaf's, so the result is the
-// same minimum (t, index) over the same candidates; entries are pushed unsorted
-// (the visiting order does not enter the result).
-// A lane's share of a cooperative walk's entry `link` (coop_closest_cp): child c
-// of an interior node — node_child_keys' test of that child, its entry distance
-// and link in (key, lnk) when the walk must visit it — or triangles c, c + 4 of a
-// leaf, with coop_leaf's acceptance rule against (lt, lb).
+// A lane's share of a cooperative walk's entry `link`: child c of an interior
+// node (its six planes and its link: seven dword loads instead of the node's
+// seven 16-byte vectors) — node_child_keys' test of that child (slab_fast with
+// the slack, slab_fma without; the same culls), its entry distance and link in
+// (key, lnk) when the walk must visit it — or triangles c, c + 4 of a leaf, with
+// wleaf_tests' acceptance rule against (lt, lb).
 template <bool SLACK>
-__device__ __forceinline__ void coop_entry_cp(const TravScene& sc, const Ray& r, const RayInv& ri, f3 oi, float far,
+__device__ __forceinline__ void coop_entry(const TravScene& sc, const Ray& r, const RayInv& ri, f3 oi, float far,
                                               uint32_t link, int c, float& lt, int& lb, float& lu, float& lv,
                                               float& key, uint32_t& lnk) {
     if (link & kLeafBit) {
@@ -1636,33 +1392,30 @@ __device__ __forceinline__ void coop_entry_cp(const TravScene& sc, const Ray& r,
         const uint32_t l = __float_as_uint(gld1(nd + 24));
         float tn, tf;
         int d = kSlabHit;
-        if (SLACK || !BDPT_SLAB_FMA) d = slab_fast(clx, cly, clz, chx, chy, chz, r.o, ri.inv, tn, tf);
+        if (SLACK) d = slab_fast(clx, cly, clz, chx, chy, chz, r.o, ri.inv, tn, tf);
         else slab_fma(clx, cly, clz, chx, chy, chz, oi, ri.inv, tn, tf);
         const bool pass = SLACK ? d != kSlabMiss : !(tn > tf);
         if (l != kEmptyLinkDev && pass && !(tn > far) && !(tf < ri.near)) key = tn, lnk = l;
     }
 }
-#ifndef BDPT_COOP_CP_CALL
-#define BDPT_COOP_CP_CALL 0  // 1: coop_closest_cp out of line (its registers not part of the caller's allocation)
-#endif
-#if BDPT_COOP_CP_CALL
-#define BDPT_COOP_CP_INLINE __noinline__
-#else
-#define BDPT_COOP_CP_INLINE __forceinline__
-#endif
+// The walk with the work of an entry spread over 4 lanes: each round pops up to 16
+// entries, and lane 4s + c takes child c (or triangles c, c + 4) of entry s, one
+// box or triangle test per lane. A lone walk's frontier rarely holds more than 16
+// entries, and a round of one wave alone on its SIMD costs its instructions, not
+// its loads. Entries are pushed unsorted (the visiting order does not enter the
+// result).
 template <bool SLACK>
-__device__ BDPT_COOP_CP_INLINE bool coop_closest_cp(const TravScene& sc, const Ray& r, const RayInv& ri, float bound,
-                                                CoopStack stk, int cap, float& best_t, int& best, float& best_u,
-                                                float& best_v, uint32_t* rounds) {
+__device__ __forceinline__ bool coop_closest(const TravScene& sc, const Ray& r, const RayInv& ri, float bound,
+                                             CoopStack stk, int cap, float& best_t, int& best, float& best_u,
+                                             float& best_v) {
     const uint32_t lane = __lane_id();
     const int slot = static_cast<int>(lane >> 2), c = static_cast<int>(lane & 3u);
-    const f3 oi = SLACK || !BDPT_SLAB_FMA ? mk(0.f, 0.f, 0.f) : slab_fma_origin(r.o, ri.inv);
+    const f3 oi = SLACK ? mk(0.f, 0.f, 0.f) : slab_fma_origin(r.o, ri.inv);
     best_t = bound < r.max_t ? bound : r.max_t, best = -1, best_u = best_v = 0.f;
     if (lane == 0) *stk.at(0) = u32x2{sc.wroot_link, __float_as_uint(-__builtin_inff())};
     int sp = 1;
     bool ok = true;
     while (sp > 0) {
-        if (rounds) (*rounds)++;
         const int k = sp < 16 ? sp : 16;
         u32x2 e = {kEmptyLinkDev, 0u};
         if (slot < k) e = *stk.at(sp - k + slot);
@@ -1673,7 +1426,7 @@ __device__ BDPT_COOP_CP_INLINE bool coop_closest_cp(const TravScene& sc, const R
         int lb = best;
         float key = __builtin_inff();
         uint32_t lnk = kEmptyLinkDev;
-        if (live) coop_entry_cp<SLACK>(sc, r, ri, oi, far, e.x, c, lt, lb, lu, lv, key, lnk);
+        if (live) coop_entry<SLACK>(sc, r, ri, oi, far, e.x, c, lt, lb, lu, lv, key, lnk);
         // the wave's lexicographic minimum of (t, index) over the lanes that found a better hit
         uint64_t imp = __ballot(lb != best);
         if (imp) {
@@ -1698,77 +1451,6 @@ __device__ BDPT_COOP_CP_INLINE bool coop_closest_cp(const TravScene& sc, const R
     }
     return ok;
 }
-#endif
-
-// BATCH: coop_leaf (a leaf's triangle loads issued together, 48 more live
-// registers) rather than wleaf_tests.
-template <bool SLACK, bool BATCH = true>
-__device__ __forceinline__ bool coop_closest(const TravScene& sc, const Ray& r, const RayInv& ri, float bound,
-                                             CoopStack stk, int cap, float& best_t, int& best, float& best_u,
-                                             float& best_v, uint32_t* rounds = nullptr, const RootLds* rl = nullptr) {
-#if BDPT_COOP_CP && !BDPT_QNODES
-    (void)rl;  // (the block's LDS copy of the root: not read by the 4-lane entries)
-    return coop_closest_cp<SLACK>(sc, r, ri, bound, stk, cap, best_t, best, best_u, best_v, rounds);
-#endif
-    const uint32_t lane = __lane_id();
-    best_t = bound < r.max_t ? bound : r.max_t, best = -1, best_u = best_v = 0.f;
-    if (lane == 0) *stk.at(0) = u32x2{sc.wroot_link, __float_as_uint(-__builtin_inff())};
-    int sp = 1;
-    bool ok = true;
-    while (sp > 0) {
-        if (rounds) (*rounds)++;
-        const int k = sp < 64 ? sp : 64;
-        u32x2 e = {kEmptyLinkDev, 0u};
-        if (static_cast<int>(lane) < k) e = *stk.at(sp - k + static_cast<int>(lane));
-        sp -= k;
-        const float far = cull_far(best_t);
-        const bool live = e.x != kEmptyLinkDev && !(__uint_as_float(e.y) > far);
-        float lt = best_t, lu = best_u, lv = best_v;
-        int lb = best;
-        float key[4] = {__builtin_inff(), __builtin_inff(), __builtin_inff(), __builtin_inff()};
-        uint32_t lnk[4] = {kEmptyLinkDev, kEmptyLinkDev, kEmptyLinkDev, kEmptyLinkDev};
-        if (live) {
-            if (e.x & kLeafBit) {
-                if (BATCH) {
-                    coop_leaf(sc, e.x, r, ri, lt, lb, lu, lv);
-                } else {
-                    Counts cnt;  // (not a counting pass)
-                    wleaf_tests<false>(sc.wtri, sc.lbox, e.x, r, ri, false, lt, lb, lu, lv, cnt);
-                }
-            }
-            else node_child_keys<SLACK>(coop_node(sc, e.x, rl), r, ri, far, key, lnk);
-        }
-        // the wave's lexicographic minimum of (t, index) over the lanes that found
-        // a better hit (usually none or one): a scalar loop over their keys
-        uint64_t imp = __ballot(lb != best);
-        if (imp) {
-            uint64_t m = ~0ull;
-            int w = 0;
-            while (imp) {
-                const int i = __ffsll(static_cast<unsigned long long>(imp)) - 1;
-                imp &= imp - 1;
-                const uint64_t ki = coop_key(lane_val(lt, i), lane_val(lb, i));
-                if (ki < m) m = ki, w = i;
-            }
-            best_t = lane_val(lt, w), best = lane_val(lb, w), best_u = lane_val(lu, w), best_v = lane_val(lv, w);
-        }
-        // children far-first, so the nearest are popped first
-#pragma unroll
-        for (int c = 3; c >= 0; c--) {
-            const uint64_t has = __ballot(lnk[c] != kEmptyLinkDev);
-            const int pos = sp + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                     static_cast<uint32_t>(has >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(has), 0u)));
-            const int n = popc64(has);
-            if (sp + n > cap) {
-                ok = false;
-            } else if (lnk[c] != kEmptyLinkDev) {
-                *stk.at(pos) = u32x2{lnk[c], __float_as_uint(key[c])};
-            }
-            if (sp + n <= cap) sp += n;
-        }
-    }
-    return ok;
-}
 
 // coop_closest for up to four rays at once: the wave split into 64 / G groups
 // of G lanes (G = 32 or 16), group g walking its own ray on its own range
@@ -1776,24 +1458,17 @@ __device__ __forceinline__ bool coop_closest(const TravScene& sc, const Ray& r, 
 // result is coop_closest's for its ray (the same per-entry tests, the minimum
 // (t, index) over the group's candidates); false for a group whose entries did
 // not fit. For the Russian-roulette build's express waves holding 2-4 long walks,
-// which otherwise take turns with all 64 lanes.
-#ifndef BDPT_COOP_GROUPS_CP
-#define BDPT_COOP_GROUPS_CP 1  // coop_closest_groups with coop_closest_cp's 4 lanes per entry (G / 4 entries per round)
-#endif
-#if BDPT_COOP_CP && BDPT_COOP_GROUPS_CP && !BDPT_QNODES
-// coop_closest_groups in coop_closest_cp's layout: group g's lane 4s + c takes child
-// c (or triangles c, c + 4) of the group's entry s, G / 4 entries per round; the
-// same per-entry tests and per-group minimum, so each group's result is
-// coop_closest's for its ray.
+// which otherwise take turns with all 64 lanes. Group g's lane 4s + c takes child
+// c (or triangles c, c + 4) of the group's entry s, G / 4 entries per round.
 template <bool SLACK>
-__device__ __forceinline__ bool coop_closest_groups_cp(const TravScene& sc, const Ray& r, const RayInv& ri,
-                                                       float bound, bool active, CoopStack stk, int base, int cap,
-                                                       int G, float& best_t, int& best, float& best_u, float& best_v) {
+__device__ __forceinline__ bool coop_closest_groups(const TravScene& sc, const Ray& r, const RayInv& ri, float bound,
+                                                    bool active, CoopStack stk, int base, int cap, int G,
+                                                    float& best_t, int& best, float& best_u, float& best_v) {
     const uint32_t lane = __lane_id();
     const int gl = static_cast<int>(lane) & (G - 1);
     const uint64_t gmask = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << (static_cast<int>(lane) - gl);
     const int slot = gl >> 2, c = gl & 3, per = G >> 2;
-    const f3 oi = SLACK || !BDPT_SLAB_FMA ? mk(0.f, 0.f, 0.f) : slab_fma_origin(r.o, ri.inv);
+    const f3 oi = SLACK ? mk(0.f, 0.f, 0.f) : slab_fma_origin(r.o, ri.inv);
     best_t = bound < r.max_t ? bound : r.max_t, best = -1, best_u = best_v = 0.f;
     if (active && gl == 0) *stk.at(base) = u32x2{sc.wroot_link, __float_as_uint(-__builtin_inff())};
     int sp = active ? 1 : 0;
@@ -1809,7 +1484,7 @@ __device__ __forceinline__ bool coop_closest_groups_cp(const TravScene& sc, cons
         int lb = best;
         float key = __builtin_inff();
         uint32_t lnk = kEmptyLinkDev;
-        if (live) coop_entry_cp<SLACK>(sc, r, ri, oi, far, e.x, c, lt, lb, lu, lv, key, lnk);
+        if (live) coop_entry<SLACK>(sc, r, ri, oi, far, e.x, c, lt, lb, lu, lv, key, lnk);
         // each group's lexicographic minimum of (t, index) over its improving lanes
         uint64_t imp = __ballot(lb != best);
         if (imp) {
@@ -1834,73 +1509,6 @@ __device__ __forceinline__ bool coop_closest_groups_cp(const TravScene& sc, cons
     }
     return ok;
 }
-#endif
-template <bool SLACK>
-__device__ __forceinline__ bool coop_closest_groups(const TravScene& sc, const Ray& r, const RayInv& ri, float bound,
-                                                    bool active, CoopStack stk, int base, int cap, int G,
-                                                    float& best_t, int& best, float& best_u, float& best_v,
-                                                    const RootLds* rl = nullptr) {
-#if BDPT_COOP_CP && BDPT_COOP_GROUPS_CP && !BDPT_QNODES
-    (void)rl;
-    return coop_closest_groups_cp<SLACK>(sc, r, ri, bound, active, stk, base, cap, G, best_t, best, best_u, best_v);
-#endif
-    const uint32_t lane = __lane_id();
-    const int gl = static_cast<int>(lane) & (G - 1);
-    const uint64_t gmask = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << (static_cast<int>(lane) - gl);
-    best_t = bound < r.max_t ? bound : r.max_t, best = -1, best_u = best_v = 0.f;
-    if (active && gl == 0) *stk.at(base) = u32x2{sc.wroot_link, __float_as_uint(-__builtin_inff())};
-    int sp = active ? 1 : 0;
-    bool ok = true;
-    while (__ballot(sp > 0)) {
-        const int k = sp < G ? sp : G;
-        u32x2 e = {kEmptyLinkDev, 0u};
-        if (gl < k) e = *stk.at(base + sp - k + gl);
-        sp -= k;
-        const float far = cull_far(best_t);
-        const bool live = e.x != kEmptyLinkDev && !(__uint_as_float(e.y) > far);
-        float lt = best_t, lu = best_u, lv = best_v;
-        int lb = best;
-        float key[4] = {__builtin_inff(), __builtin_inff(), __builtin_inff(), __builtin_inff()};
-        uint32_t lnk[4] = {kEmptyLinkDev, kEmptyLinkDev, kEmptyLinkDev, kEmptyLinkDev};
-        if (live) {
-            if (e.x & kLeafBit) {
-                Counts cnt;  // (not a counting pass)
-                wleaf_tests<false>(sc.wtri, sc.lbox, e.x, r, ri, false, lt, lb, lu, lv, cnt);
-            } else {
-                node_child_keys<SLACK>(coop_node(sc, e.x, rl), r, ri, far, key, lnk);
-            }
-        }
-        // each group's lexicographic minimum of (t, index) over its improving lanes
-        uint64_t imp = __ballot(lb != best);
-        if (imp) {
-            uint64_t m = ~0ull;
-            int w = static_cast<int>(lane);
-            while (imp) {
-                const int i = __ffsll(static_cast<unsigned long long>(imp)) - 1;
-                imp &= imp - 1;
-                const uint64_t ki = coop_key(lane_val(lt, i), lane_val(lb, i));
-                if ((gmask >> i) & 1ull && ki < m) m = ki, w = i;
-            }
-            best_t = __shfl(lt, w), best = __shfl(lb, w), best_u = __shfl(lu, w), best_v = __shfl(lv, w);
-        }
-        // children far-first, each group on its own range
-#pragma unroll
-        for (int c = 3; c >= 0; c--) {
-            const uint64_t has = __ballot(lnk[c] != kEmptyLinkDev) & gmask;
-            const int pos = sp + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                     static_cast<uint32_t>(has >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(has), 0u)));
-            const int n = popc64(has);
-            if (sp + n > cap) {
-                ok = false;
-            } else if (lnk[c] != kEmptyLinkDev) {
-                *stk.at(base + pos) = u32x2{lnk[c], __float_as_uint(key[c])};
-            }
-            if (sp + n <= cap) sp += n;
-        }
-    }
-    return ok;
-}
-
 #if BDPT_TEXTURED
 // w * y + x of core.h:582-584 (int(float) as x86's cvttss2si, clamp to [0, size - 1]).
 __device__ __forceinline__ int texel_of(float sx, float sy, int tw, int th) {
@@ -1913,7 +1521,7 @@ __device__ __forceinline__ int texel_of(float sx, float sy, int tw, int th) {
 // AcceleratorBVH::intersect's shading of a closest hit (accel.h:133-166).
 __device__ __forceinline__ void shade_hit(const DevScene& sc, int i, float u, float v, float t, f3 dir, Hit& h) {
     const float4* sh = sc.shade + kShadeStride * static_cast<size_t>(i);
-    const f3 v0 = xyz(gld4(BDPT_SHADE_WIDE ? sh + kShadeV0 : sc.tri + 3 * static_cast<size_t>(i))),
+    const f3 v0 = xyz(gld4(sh + kShadeV0)),
              v1 = xyz(gld4(sh + 3)), v2 = xyz(gld4(sh + 4));
     const float4 s0 = gld4(sh), s1 = gld4(sh + 1), s2 = gld4(sh + 2);
     const float w = 1 - u - v;
@@ -1966,12 +1574,6 @@ __device__ __forceinline__ f3 ld3(const float* p) { return mk(p[0], p[1], p[2]);
 #endif
 #ifndef BDPT_GLOSSY_ATTR
 #define BDPT_GLOSSY_ATTR __forceinline__  // the Phong-bearing eval / pdf (measured: inline +2 %)
-#endif
-#ifndef BDPT_EVAL_PDFS
-#define BDPT_EVAL_PDFS 1  // 0: eval and the two pdfs through separate calls (round 2: 195.9 vs 190.8 for 1; round 3 without SLP: 245.2 vs 250.0)
-#endif
-#ifndef BDPT_GLASS_INLINE
-#define BDPT_GLASS_INLINE 1  // the delta lobes' samplers inline, the Phong-bearing ones out of line (+1.1 %)
 #endif
 #ifndef BDPT_SAMPLE_ATTR
 #define BDPT_SAMPLE_ATTR BDPT_NOINLINE  // the non-diffuse BSDF samplers out of line
@@ -2062,7 +1664,7 @@ __device__ __forceinline__ EvalPdfs bsdf_eval_pdfs(const BsdfRecord& b, f3 wi, f
     r.fwd = cosine_hemisphere_pdf(wi);
     r.rev = cosine_hemisphere_pdf(wo);
     return r;
-#elif BDPT_EVAL_PDFS
+#else
     EvalPdfs r{mk(0.f, 0.f, 0.f), 0.f, 0.f};
     const int kind = b.kind;
     if (kind == BSDF_DIFFUSE) {
@@ -2098,8 +1700,6 @@ __device__ __forceinline__ EvalPdfs bsdf_eval_pdfs(const BsdfRecord& b, f3 wi, f
         r.rev = (pp * b.specw) + (cosine_hemisphere_pdf(wo) * (1.f - b.specw));
     }
     return r;
-#else
-    return EvalPdfs{bsdf_eval(b, wi, wo), bsdf_pdf(b, wi, wo), bsdf_pdf(b, wo, wi)};
 #endif
 }
 
@@ -2138,14 +1738,7 @@ __device__ __forceinline__ f3 glass_sample(const BsdfRecord& b, f3 wo, F2 u, f3&
 }
 
 // BSDF::sample: sets wi, returns f*cos, writes the solid-angle pdf.
-#ifndef BDPT_SAMPLE_STRUCT
-#define BDPT_SAMPLE_STRUCT 1
-#endif
-#if BDPT_SAMPLE_STRUCT
 __device__ __forceinline__ f3 bsdf_sample_body(const BsdfRecord& b, f3 wo, F2 u, f3& wi, float& pdf) {
-#else
-__device__ BDPT_NOINLINE f3 bsdf_sample_call(const BsdfRecord& b, f3 wo, F2 u, f3& wi, float& pdf) {
-#endif
     switch (b.kind) {
         case BSDF_MIRROR:  // perfectmirror.h:49-59
             pdf = 1.f;
@@ -2191,7 +1784,6 @@ __device__ BDPT_NOINLINE f3 bsdf_sample_call(const BsdfRecord& b, f3 wo, F2 u, f
             return mk(0.f, 0.f, 0.f);
     }
 }
-#if BDPT_SAMPLE_STRUCT
 // The call returns everything by value (in VGPRs): with reference outputs the
 // caller's wi / pdf went through scratch around every call.
 struct BsdfSample {
@@ -2209,21 +1801,18 @@ __device__ __forceinline__ f3 bsdf_sample_call(const BsdfRecord& b, f3 wo, F2 u,
     pdf = s.pdf;
     return s.f;
 }
-#endif
 __device__ __forceinline__ f3 bsdf_sample(const BsdfRecord& b, f3 wo, F2 u, f3& wi, float& pdf) {
     if (b.kind == BSDF_DIFFUSE) {  // diffuse.h:52-61
         wi = cosine_hemisphere(u);
         pdf = cosine_hemisphere_pdf(wi);
         return bsdf_eval(b, wi, wo);
     }
-#if BDPT_GLASS_INLINE || !BDPT_GLOSSY
     if (b.kind == BSDF_GLASS) return glass_sample(b, wo, u, wi, pdf);
     if (b.kind == BSDF_MIRROR) {  // perfectmirror.h:49-59
         pdf = 1.f;
         wi = reflect_z(wo);
         return mk(1.f, 1.f, 1.f);
     }
-#endif
 #if BDPT_GLOSSY
     return bsdf_sample_call(b, wo, u, wi, pdf);
 #else
@@ -2260,18 +1849,13 @@ __device__ __forceinline__ BsdfRecord bsdf_tex(const DevScene& sc, int mat, int 
 // The direction v in the shading frame of normal n, for evaluating BSDF b:
 // DiffuseBSDF's eval and pdf read only the z component, dot(v, n) (to_local),
 // so a diffuse lane skips Frame(n) (a sqrt, a division and a branch); the x, y
-// it leaves at 0 are never read. BDPT_DIFFUSE_Z 0 builds every frame. Called for
+// it leaves at 0 are never read. Called for
 // the ends of a connection, which are not delta: diffuse in a BDPT_GLOSSY 0 build.
-#ifndef BDPT_DIFFUSE_Z
-#define BDPT_DIFFUSE_Z 1
-#endif
 __device__ __forceinline__ f3 local_for(const BsdfRecord& b, f3 n, f3 v) {
 #if !BDPT_GLOSSY
     return mk(0.f, 0.f, dot(v, n));
 #else
-#if BDPT_DIFFUSE_Z
     if (b.kind == BSDF_DIFFUSE) return mk(0.f, 0.f, dot(v, n));
-#endif
     return local_at(n, v);
 #endif
 }
@@ -2347,4 +1931,22 @@ __device__ __forceinline__ int sample_emitter(const DevScene& sc, Rng& rng, floa
 }
 
 }  // namespace dev
+
+// One build of the BDPT frame kernel (bdpt_kernels.hip, compiled once per
+// bdpt_kernels_<x>.hip), as bdpt_capi.cpp picks and launches it. `dparams` is a
+// device buffer of params_bytes owned by the caller; a launch fills it on
+// `stream` first (stream order protects reuse).
+struct FrameBuild {
+    typedef hipError_t (*Launch)(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf,
+                                 uint2* gstack, uint32_t nslots, unsigned long long* work,
+                                 unsigned long long* counters, int grid, hipStream_t stream, void* dparams);
+    const char* name;  // what bdpt_last_kernel reports
+    int glossy;        // 0: no Mixture / Phong lobes (bdpt_last_kernel_glossy)
+    Launch launch_frame;
+    Launch launch_chain;                   // the continuation pass's chain kernel (BDPT_PARK builds), or null
+    int (*blocks_per_cu)(size_t dyn_lds);  // resident 256-lane blocks per CU (VGPR and LDS limited)
+    int light_vertex_fields;               // floats per light-vertex record
+    int block, lds_stack;                  // lanes per block; traversal-stack entries per lane in LDS
+    size_t params_bytes;
+};
 }  // namespace bdpt

@@ -18,7 +18,20 @@
 // bdpt_sample_kernel — a single (ray, sampler) call for the drop-in
 // Integrator::render(const Ray&, Sampler&) entry point (same state machine,
 // one lane).
+//
+// This file is compiled once per build: bdpt_kernels_<x>.hip and sample_state*.hip
+// set their feature macros and BDPT_VARIANT, the suffix (_deep, _rr, ...; empty for
+// the default build) of the build's kernels and of its host-visible names.
 #include <hip/hip_runtime.h>
+
+#ifndef BDPT_VARIANT
+#define BDPT_VARIANT
+#endif
+#define BDPT_PASTE(a, b) a##b
+#define BDPT_NAME_(a, b) BDPT_PASTE(a, b)
+#define BDPT_NAME(x) BDPT_NAME_(x, BDPT_VARIANT)  // x with the build's suffix
+#define BDPT_STR_(x) #x
+#define BDPT_STR(x) BDPT_STR_(x)
 
 #ifndef BDPT_BSDF_TABLE
 #if BDPT_SAMPLER_STATE
@@ -46,8 +59,7 @@
 #ifndef BDPT_HELP
 #define BDPT_HELP 1
 #endif
-#if (defined(BDPT_RR) && BDPT_RR) || (defined(BDPT_SAMPLER_STATE) && BDPT_SAMPLER_STATE) || \
-    (defined(BDPT_OVERLAP) && !BDPT_OVERLAP)
+#if (defined(BDPT_RR) && BDPT_RR) || (defined(BDPT_SAMPLER_STATE) && BDPT_SAMPLER_STATE)
 #undef BDPT_HELP
 #define BDPT_HELP 0
 #endif
@@ -65,9 +77,6 @@ namespace dev {
 #define BDPT_WAVES_PER_EU 4  // waves per SIMD the register allocator must leave room for
 #endif
 constexpr int kBlock = 256;
-#ifndef BDPT_OVERLAP
-#define BDPT_OVERLAP 1  // overlapped walk / shade schedule in the megakernel (0: one query then shade, in lockstep)
-#endif
 #ifndef BDPT_TRAV_SPLIT
 #define BDPT_TRAV_SPLIT 8  // > 0: leaf and interior-node steps in separate iterations (leaf step if 4 * leaf lanes >= SPLIT * node lanes; round 5: 6 over 8, then 8 over 6 / 10 / 12 once node steps also follow leaf iterations)
 #endif
@@ -80,17 +89,11 @@ constexpr int kBlock = 256;
 #ifndef BDPT_SHADE_READY
 #define BDPT_SHADE_READY 44  // lanes with a finished query that trigger the wave's shading step (round 5 re-sweep: 44 over 48)
 #endif
-#ifndef BDPT_TAIL_SHADE
-#define BDPT_TAIL_SHADE 2  // once a wave has no samples left to claim: 1 shade at 1 ready lane, 2 at BDPT_TAIL_FRAC / 8 of its busy lanes
-#endif
 #ifndef BDPT_TAIL_FRAC
 #define BDPT_TAIL_FRAC 6  // (measured, 512x512x256 1/8 shard: end tail 2.19 -> 1.93 ms, steady state unchanged)
 #endif
 #ifndef BDPT_EXPRESS_DEPTH
 #define BDPT_EXPRESS_DEPTH 512  // Russian-roulette build: a subpath this deep puts its wave in express mode (below; DevFrame::express_depth, set per render)
-#endif
-#ifndef BDPT_ROOT_LDS
-#define BDPT_ROOT_LDS 1  // 1: the traversal root and its interior children in LDS, tested when a walk begins (RootLds; measured +1.6 %)
 #endif
 
 #ifndef BDPT_COOP_ALONE
@@ -98,70 +101,6 @@ constexpr int kBlock = 256;
 #endif
 #ifndef BDPT_COOP_MAX
 #define BDPT_COOP_MAX 4  // express waves with up to this many busy lanes walk their closest hits in turn with the whole wave
-#endif
-#ifndef BDPT_RR_DIAG
-#define BDPT_RR_DIAG 1
-#endif
-#ifndef BDPT_COOP_BATCH
-#define BDPT_COOP_BATCH 0  // the megakernel's wave walk tests leaves with wleaf_tests (coop_leaf's batched loads cost spills)
-#endif
-#ifndef BDPT_EXPRESS_WALK
-#define BDPT_EXPRESS_WALK 0  // 1: a lone trapped lane's delta chain out of line (express_walk; 1.5 % faster on the trapped chain, +49 VGPR spills in the RR build)
-#endif
-#if BDPT_RR == 1 && !BDPT_SAMPLER_STATE && BDPT_EXPRESS_WALK
-// Russian roulette: a subpath trapped by total internal reflection bounces
-// between delta surfaces for up to millions of steps, each a
-// closest-hit walk plus the sweep's work for a delta vertex. Once its wave holds
-// nothing else (express mode with one busy lane) those bounces run here, back to
-// back: the walk, then exactly what the sweep does at a delta, non-emitting
-// vertex — the vertex update (bdpt.h:73-136 / :193-209, no connection: delta),
-// ContinuePathRandomWalk (bdpt.h:243-291), the loop test (bdpt.h:68 / :188) —
-// until the chain ends. Out of line: the loop keeps only its own state in
-// registers, where the megakernel's sweep spills (a lone lane waits out every
-// scratch access). Returns true with the result (res, t, u, v) of a query the
-// sweep resolves (a miss, a non-delta or emitting hit); false when the walk
-// ended here (light: ST_DEFER, the eye subpath next; eye: the sample finished).
-__device__ __noinline__ bool express_walk(Lane& Lcaller, const DevScene& sc, const DevFrame& fr, float* __restrict__ fb,
-                                          const Stack stk, int& res, float& rt, float& ru, float& rv) {
-    Counts cnt;  // (not a counting pass)
-    // the lane's register state as locals (the caller's copy is written back on return)
-    Lane L(Lcaller.c);
-    L.rng = Lcaller.rng, L.state = Lcaller.state, L.ray = Lcaller.ray, L.h = Lcaller.h;
-    struct WriteBack {
-        Lane& to;
-        const Lane& from;
-        __device__ ~WriteBack() { to.rng = from.rng, to.state = from.state, to.ray = from.ray, to.h = from.h; }
-    } wb{Lcaller, L};
-    for (;;) {
-        const bool light = L.state == ST_LIGHT;
-        float t = 0.f, u = 0.f, v = 0.f;
-        const int r = traverse<false, false>(sc, L.ray, false, stk, t, u, v, cnt, cull_near_for(L));
-        const bool hit = r >= 0 && t <= L.ray.max_t && t >= L.ray.min_t;  // accel.h:133
-        const BsdfRecord* b = nullptr;
-        if (hit) b = &bsdf_of(sc, __float_as_int(gld4(sc.shade + kShadeStride * static_cast<size_t>(r)).w));
-        if (!hit || !is_delta(*b) || !is_zero(ld3(b->emission)) || L.c.steps + 1 > (1 << 30)) {
-            res = r, rt = t, ru = u, rv = v;  // the sweep resolves it
-            return true;
-        }
-        ++L.c.steps;  // resolve(): one more query, the hit shaded
-        shade_hit(sc, r, u, v, t, L.ray.d, L.h);
-        const float dist2 = L.h.dist * L.h.dist;
-        BDPT_DIST_TO_GRAZE
-        const float absCosIn = fabsf(L.h.wo.z);
-#if BDPT_RING_AHEAD
-        if (L.rng.n + BDPT_RING_AHEAD >= 227 && !mt_ring_ahead(L.rng) && fr.diag) gadd(fr.diag + kDiagErrors, 1ull);
-#endif
-        L.c.vcm *= div_cr(dist2, absCosIn);
-        L.c.vc *= rcp_cr(absCosIn);
-        L.c.rr = rr_probability(fr, L.c.depth, L.c.tp);  // bdpt.h:129-134 / :201-204
-        const bool more = continue_walk(*b, L.h, L.rng, L.c.tp, L.c.depth, L.c.vc, L.c.vcm, L.ray, L.c.rr);
-        if (!more || !walk_continues(L, fr)) {
-            if (light) L.state = ST_DEFER;  // the eye subpath starts next step
-            else finish<false>(L, fr, fb, cnt);  // L.state = ST_IDLE
-            return false;
-        }
-    }
-}
 #endif
 
 #ifndef BDPT_PARK
@@ -179,7 +118,7 @@ __device__ __noinline__ bool express_walk(Lane& Lcaller, const DevScene& sc, con
 // — until the chain reaches a vertex the megakernel must shade (a miss, a
 // non-delta or emitting hit) or the subpath ends; a resume launch of the
 // megakernel on the same grid then continues each sample in its own slot. The
-// same functions in the same order (express_walk's bounce), so the same bits.
+// same functions in the same order as the sweep's bounce, so the same bits.
 constexpr uint32_t kParkWords = kParkSlotWords;
 enum : uint32_t {
     kParkStatus = 0,        // 0 none, 1 parked, 2 returned by the chain kernel
@@ -246,81 +185,6 @@ __device__ __forceinline__ bool park_lane(const DevFrame& fr, uint32_t nslots, u
 #define BDPT_BUSY(st) ((st) != ST_IDLE)
 #endif
 
-#if BDPT_RR == 1 && !BDPT_SAMPLER_STATE && BDPT_EXPRESS_CHAIN == 2
-// The lone long walk's chain of delta bounces (express mode, one busy lane b): each
-// closest hit walked by the whole wave (coop_closest), the bounce itself on lane b,
-// back to back until the chain reaches a vertex the sweep must shade. Out of line,
-// called by all 64 lanes, so the megakernel's register allocation is not sized for
-// it. Returns -1 with the last walk's result in (t, r, u, v, ok) for the sweep; 0 when
-// the chain ended here (lane b: ST_DEFER or finished); 2 when lane b's next query
-// must begin at the loop top (the reference's tree, or a culled root).
-template <bool SLACK>
-__device__ __noinline__ int express_chain(Lane& Lcaller, int b, RayInv& ri_caller, const DevScene& sc,
-                                          const DevFrame& fr, float* __restrict__ fb, const TravScene& tsc,
-                                          uint2* stack_base, const RootLds* coop_rl, float& t, int& r, float& u,
-                                          float& v, bool& ok) {
-    Counts cnt;  // (not a counting pass)
-    Lane L(Lcaller.c);
-    L.rng = Lcaller.rng, L.state = Lcaller.state, L.ray = Lcaller.ray, L.h = Lcaller.h;
-    RayInv ri = ri_caller;
-    const int me = static_cast<int>(__lane_id());
-    const CoopStack cs{stack_base, kBlock};
-    int bounced = -1;
-    for (;;) {
-        Ray q;
-        q.o = mk(lane_val(L.ray.o.x, b), lane_val(L.ray.o.y, b), lane_val(L.ray.o.z, b));
-        q.d = mk(lane_val(L.ray.d.x, b), lane_val(L.ray.d.y, b), lane_val(L.ray.d.z, b));
-        q.min_t = lane_val(L.ray.min_t, b), q.max_t = lane_val(L.ray.max_t, b);
-        RayInv qi;
-        qi.inv = mk(lane_val(ri.inv.x, b), lane_val(ri.inv.y, b), lane_val(ri.inv.z, b));
-        qi.near = lane_val(ri.near, b);
-        qi.fast = true;
-        const float guess = BDPT_GRAZE_IN_DIST ? -1.f : lane_val(L.h.dist, b);
-        r = -1;
-        ok = true;
-        for (int pass = guess > 0.f ? 0 : 1; pass < 2 && r < 0 && ok; pass++) {
-            const float bound = pass == 0 ? 2.f * guess : q.max_t;
-            ok = coop_closest<SLACK, BDPT_COOP_BATCH>(tsc, q, qi, bound, cs, 64 * kLdsStack, t, r, u, v, nullptr, coop_rl);
-        }
-        if (!ok) break;
-        int more = -1;
-        if (me == b && r >= 0 && t <= L.ray.max_t && t >= L.ray.min_t) {  // accel.h:133
-            const BsdfRecord& bb = bsdf_of(sc, __float_as_int(gld4(sc.shade + kShadeStride * static_cast<size_t>(r)).w));
-            if (is_delta(bb) && is_zero(ld3(bb.emission)) && L.c.steps + 1 <= (1 << 30)) {
-                ++L.c.steps;  // resolve(): one more query, the hit shaded
-                shade_hit(sc, r, u, v, t, L.ray.d, L.h);
-                const float dist2 = L.h.dist * L.h.dist;
-                BDPT_DIST_TO_GRAZE
-                const float absCosIn = fabsf(L.h.wo.z);
-#if BDPT_RING_AHEAD
-                if (L.rng.n + BDPT_RING_AHEAD >= 227 && !mt_ring_ahead(L.rng) && fr.diag) gadd(fr.diag + kDiagErrors, 1ull);
-#endif
-                L.c.vcm *= div_w(dist2, absCosIn);  // bdpt.h:193-209 / :73-136 (no connection at a delta vertex)
-                L.c.vc *= rcp_w(absCosIn);
-                L.c.rr = rr_probability(fr, L.c.depth, L.c.tp);
-                const bool light = L.state == ST_LIGHT;
-                const bool cont = continue_walk(bb, L.h, L.rng, L.c.tp, L.c.depth, L.c.vc, L.c.vcm, L.ray, L.c.rr);
-                if (cont && walk_continues(L, fr)) {  // bdpt.h:188 / :68
-                    ri = ray_inv(L.ray, cull_near_for(L));
-                    more = ri.fast && !far_origin(sc, L.ray.o) && !(L.ray.min_t > L.ray.max_t) ? 1 : 2;
-                } else {
-                    if (light) L.state = ST_DEFER;  // the eye subpath starts next step
-                    else finish<false>(L, fr, fb, cnt);  // L.state = ST_IDLE
-                    more = 0;
-                }
-            }
-        }
-        more = lane_val(more, b);
-        if (more == 1) continue;
-        bounced = more;
-        break;
-    }
-    Lcaller.rng = L.rng, Lcaller.state = L.state, Lcaller.ray = L.ray, Lcaller.h = L.h;
-    ri_caller = ri;
-    return bounced;
-}
-#endif
-
 // One query for the lane's pending state, then the state advance.
 template <bool FULL, bool COUNT>
 __device__ __forceinline__ void step(Lane& L, const DevScene& sc, const DevFrame& fr, float* __restrict__ fb,
@@ -362,12 +226,6 @@ struct KParams {
 // SLACK: interior boxes with slab_fast's ambiguity slack (DevScene::node_slack,
 // decided per render on the host); a template parameter so the node step of
 // the walk loop carries no branch on it.
-#ifndef BDPT_UNROLL_ANY
-#define BDPT_UNROLL_ANY 1  // the extra node step also after a leaf iteration, for lanes that popped to an interior node (with split 8: Caustic +1.0 %, HardLight +1.8 %, synth1m +1.0 %)
-#endif
-#ifndef BDPT_COOP_GROUPS
-#define BDPT_COOP_GROUPS 1  // express waves with 2-4 long walks walk them at once in groups of 32 / 16 lanes (coop_closest_groups; RR Caustic frames 42.7-45.2 s vs 43.8-54.0)
-#endif
 #ifndef BDPT_HELP_BATCH
 #define BDPT_HELP_BATCH 1  // BDPT_HELP: the shading step's connections flattened over the wave (conn_batch; serial: 283.0 vs 322.8)
 #endif
@@ -375,16 +233,13 @@ struct KParams {
 #undef BDPT_HELP_BATCH
 #define BDPT_HELP_BATCH 0
 #endif
-#ifndef BDPT_HELP_CLOCKS
-#define BDPT_HELP_CLOCKS 0  // measurement only: the counting pass's stack-depth words carry the claim / completion / batch clocks
-#endif
 #ifndef BDPT_EXPRESS_CHAIN
 #define BDPT_EXPRESS_CHAIN 0  // RR build: a lone long walk's delta bounces back to back inside the express block
 #endif
 #ifndef BDPT_CHAIN_RING_WAVE
 #define BDPT_CHAIN_RING_WAVE 1  // the inline chain's generator ring refilled by the whole wave (mt_ring_ahead_wave)
 #endif
-#if !(BDPT_EXPRESS_CHAIN == 1 && BDPT_DEEP_RNG && BDPT_RING_AHEAD)
+#if !(BDPT_EXPRESS_CHAIN && BDPT_DEEP_RNG && BDPT_RING_AHEAD)
 #undef BDPT_CHAIN_RING_WAVE
 #define BDPT_CHAIN_RING_WAVE 0
 #endif
@@ -395,35 +250,14 @@ struct KParams {
 #undef BDPT_EXPRESS_PROBE
 #define BDPT_EXPRESS_PROBE 0
 #endif
-#ifndef BDPT_HELP_SREG
-#define BDPT_HELP_SREG 1  // BDPT_HELP: the ring positions held in SGPRs during the walk loop (no LDS reads per iteration; 324.6 vs 322.7)
-#endif
-#ifndef BDPT_HELP_HOIST
-#define BDPT_HELP_HOIST 0  // BDPT_HELP: a claim's record loads issued before the lane's own hit is shaded
-#endif
-#ifndef BDPT_HELP_DEFER
-#define BDPT_HELP_DEFER 0  // BDPT_HELP: a claimed task's walk begins one walk iteration after its record loads (305.8 vs 323.5: not kept)
-#endif
-#ifndef BDPT_HELP_LAZY_TAIL
-#define BDPT_HELP_LAZY_TAIL 0  // BDPT_HELP: a claim loads the record's plane C only once plane A shows no splat (a second exposed load latency per round for 8 bytes fewer per splat)
-#endif
 #ifndef BDPT_HELP_MIN
 #define BDPT_HELP_MIN 16  // BDPT_HELP: fewest waiting lanes that start a claim round (unless the ring holds fewer tasks; 1 / 8 / 12 / 16 / 20 / 24: 264.9 / 322.7 / 323.3 / 323.4 / 319.8 / 266.4)
 #endif
 #ifndef BDPT_TAIL_PROBE
 #define BDPT_TAIL_PROBE 0  // measurement only (non-RR builds): the drain phase in the RR diag words (tools/tail_probe.py)
 #endif
-#ifndef BDPT_READY_HOIST
-#define BDPT_READY_HOIST 1  // the shade threshold read before the walk loop instead of in it (Caustic +0.85 %, synth1m +1.2 %)
-#endif
-#ifndef BDPT_TID_REMAT
-#define BDPT_TID_REMAT 1  // the lane's traversal-stack and light-vertex addresses re-derived from threadIdx.x at each use
-#endif
 // "this is lane 0" from an opaque threadIdx.x (lanes_below: bdpt_device.hpp).
 __device__ __forceinline__ bool lane0() { return (opaque_tid() & 63) == 0; }
-#ifndef BDPT_TAIL_CHUNK
-#define BDPT_TAIL_CHUNK 4  // 0: 64-sample chunks throughout; else finer claims near the end (below)
-#endif
 // Where the finer claims begin, in quarters of the grid's lanes from the frame's end:
 // 16-sample claims from BDPT_TAIL_Z16 / 4 x lanes, 4-sample ones from BDPT_TAIL_Z4 / 4 x
 // lanes. Round 6 re-measured them on the task build (each claim seeds a whole wave's
@@ -437,42 +271,28 @@ __device__ __forceinline__ bool lane0() { return (opaque_tid() & 63) == 0; }
 #ifndef BDPT_TAIL_Z4
 #define BDPT_TAIL_Z4 2
 #endif
-#ifndef BDPT_CLAIM_SCALAR
-#define BDPT_CLAIM_SCALAR 1  // the claimed chunk base broadcast by readfirstlane (scalar) instead of a shuffle
-#endif
 // Samples the wave claims next, from the last chunk it claimed (wave-uniform).
 __device__ __forceinline__ uint64_t tail_chunk(uint64_t last_base, uint64_t total) {
-    if (!BDPT_TAIL_CHUNK) return 64;
     const uint64_t lanes = static_cast<uint64_t>(gridDim.x) * kBlock;
     return last_base + BDPT_TAIL_Z16 * lanes / 4 < total ? 64 : last_base + BDPT_TAIL_Z4 * lanes / 4 < total ? 16 : 4;
 }
 
 template <bool FULL, bool COUNT, bool SLACK>
-__global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(const KParams* __restrict__ kpp) {
+__global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_frame_kernel)(const KParams* __restrict__ kpp) {
     const KParams& kp = *kpp;
     __shared__ uint2 stack_mem[kLdsStack * kBlock];
-#if BDPT_ROOT_LDS && BDPT_OVERLAP
     __shared__ RootLds root_lds;
     const bool root_in_lds = !FULL && root_lds_usable(kp.sc);
     if (!FULL) root_lds_fill(root_lds, kp.sc);
-#endif
     scene_tables_to_lds(kp.sc);
-#if BDPT_TID_REMAT
     const Stack stk{stack_mem, kBlock, kLdsStack, kp.gstack, kp.nslots, blockIdx.x * kBlock, true};
-#else
-    const Stack stk{stack_mem + threadIdx.x, kBlock, kLdsStack, kp.gstack, kp.nslots, blockIdx.x * kBlock + threadIdx.x};
-#endif
     Counts cnt;
     for (int i = 0; i < kCounters; i++) cnt.c[i] = 0;
     cnt.m[0] = cnt.m[1] = cnt.m[2] = 0;
     cnt.q[0] = cnt.q[1] = cnt.q[2] = cnt.q[3] = 0;
     cnt.t_step = 0;
-#if BDPT_TID_REMAT
     LightStore ls = light_store(kp.lv, kp.fr.lv_max, blockIdx.x * kBlock);
     ls.tid_rel = true;
-#else
-    const LightStore ls = light_store(kp.lv, kp.fr.lv_max, blockIdx.x * kBlock + threadIdx.x);
-#endif
     unsigned long long* const work = kp.work;
     const uint64_t total = kp.fr.total_samples;
     __shared__ LaneCold cold_mem[kBlock];
@@ -502,14 +322,12 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
         for (int k = 0; k < BDPT_EYE_SLOTS; k++) wave_eye_slots()[k] = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
 #endif
 #endif
-#if BDPT_OVERLAP
     const TravScene tsc = trav_scene(kp.sc);
     bool tracing = false, has_res = false, q_any = false;
     TravState ts{};
     RayInv ri{};
     int res = -1;
     float rt = 0.f, ru = 0.f, rv = 0.f;
-#endif
     // Russian roulette: a subpath trapped in glass by total internal reflection
     // runs for millions of bounces, one bounce per shading step of
     // its wave. A wave holding a subpath past BDPT_EXPRESS_DEPTH stops refilling
@@ -522,12 +340,8 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
     bool xp_prev = false;
 #endif
 #if BDPT_HELP
-    // helping: the lane walks a task's shadow ray (tracing is set too) or, with BDPT_HELP_DEFER,
-    // waits one iteration for its claimed record (hwait)
+    // helping: the lane walks a task's shadow ray (tracing is set too)
     bool helping = false;
-#if BDPT_HELP_DEFER
-    bool hwait = false;
-#endif
     {
         const TaskCtl ctl = task_ctl(L.c);
         if (lane0()) *ctl.head = *ctl.tail = 0u;
@@ -542,12 +356,9 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
 #if BDPT_TAIL_PROBE && BDPT_RR != 1
     uint64_t t_drain = 0, t_few = 0;  // wave-uniform (BDPT_TAIL_PROBE)
 #endif
-#ifndef BDPT_DIAG
-#define BDPT_DIAG 1  // 0: no timeline stamps (A/B only)
-#endif
     // the kernel's timeline (DevFrame::diag), read through the parameter block
     // where it is stamped (a pointer held across the loop costs SGPR spills)
-    if (BDPT_DIAG && kp.fr.diag && lane0()) gmin(kp.fr.diag + kDiagStart, __builtin_amdgcn_s_memrealtime());
+    if (kp.fr.diag && lane0()) gmin(kp.fr.diag + kDiagStart, __builtin_amdgcn_s_memrealtime());
     for (;;) {
         // Re-derived every iteration (opaque to the optimiser) so constants are
         // read where they are used instead of being pinned in registers; typed
@@ -570,7 +381,7 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
         }
 #endif
 #if BDPT_RR == 1
-        if (BDPT_DIAG && BDPT_RR_DIAG && express && lane0() && P->fr.diag) {  // how many trapped walks share a wave (bdpt_stats)
+        if (express && lane0() && P->fr.diag) {  // how many trapped walks share a wave (bdpt_stats)
             const int k = popc64(longs);
             gmax(P->fr.diag + kDiagLongMax, static_cast<unsigned long long>(k));
             gadd(P->fr.diag + (k == 1 ? kDiagExpress1 : k <= BDPT_COOP_MAX ? kDiagExpressCoop : kDiagExpressMore), 1ull);
@@ -598,14 +409,10 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                 const uint64_t want = tail_chunk(chunk_base, total);
                 unsigned long long base = 0;
                 if (lane0()) base = gadd(work, static_cast<unsigned long long>(want));
-#if BDPT_CLAIM_SCALAR
                 // wave-uniform in scalar registers (a shuffle's result is a VGPR pair)
                 base = static_cast<unsigned long long>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(base))) |
                        static_cast<unsigned long long>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(base >> 32)))
                            << 32;
-#else
-                base = __shfl(base, 0);
-#endif
                 if (base >= total) {
                     exhausted = true;
                     break;
@@ -614,7 +421,7 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                 chunk_n = static_cast<int>(total - base < want ? total - base : want);
                 chunk_pos = 0;
                 global_done = base + want >= total;
-                if (BDPT_DIAG && global_done && lane0() && P->fr.diag)  // the frame's last chunk (one wave claims it)
+                if (global_done && lane0() && P->fr.diag)  // the frame's last chunk (one wave claims it)
                     P->fr.diag[kDiagLastClaim] = __builtin_amdgcn_s_memrealtime();
                 int px;
                 chunk_x397 = mt_x397(sample_seed(base + (opaque_tid() & 63), P->fr, px));
@@ -665,23 +472,10 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
             if (!t_few && popc64(__ballot(BDPT_BUSY(L.state))) <= 4) t_few = __builtin_amdgcn_s_memrealtime();
         }
 #endif
-#if BDPT_OVERLAP
         // Overlapped schedule: lanes keep walking their query across loop
         // iterations; a lane whose query finished waits (result kept) until
         // enough lanes of the wave are ready, then those lanes shade together
         // while the slow walkers resume afterwards from where they stopped.
-#if BDPT_RR == 1 && BDPT_EXPRESS_WALK
-        if (!COUNT && express) {  // a trapped subpath alone in its wave: its delta chain out of line
-            const bool alone = popc64(__ballot(BDPT_BUSY(L.state))) == 1;
-            if (alone && !tracing && !has_res && (L.state == ST_LIGHT || L.state == ST_EYE)) {
-                if (express_walk(L, P->sc, P->fr, P->fb, stk, res, rt, ru, rv)) has_res = true;
-                if (!has_res) {
-                    long_walk = false;  // the chain ended: the lane's next step comes from the sweep
-                    continue;
-                }
-            }
-        }
-#endif
 #if BDPT_PARK
         if (!COUNT && (P->fr.park_flags & kParkOn) && !tracing && !has_res && (L.state == ST_LIGHT || L.state == ST_EYE) &&
             L.c.depth > P->fr.park_depth && park_lane(P->fr, P->nslots, blockIdx.x * kBlock + opaque_tid(), L)) {
@@ -720,7 +514,6 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
 #if BDPT_COOP_ALONE
                 began = !q_any;
 #endif
-#if BDPT_ROOT_LDS
                 if (root_in_lds && !walk_begin_lds<COUNT, SLACK>(root_lds, L.ray, ri, q_any, ts, stk, cnt)) {
                     res = -1, rt = ts.best_t, ru = ts.best_u, rv = ts.best_v;  // no child hit: a miss
                     tracing = false;
@@ -729,7 +522,6 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                     began = false;  // (complete: nothing for the wave to walk)
 #endif
                 }
-#endif
             }
         }
 #if BDPT_COOP_ALONE
@@ -749,13 +541,7 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
         const uint64_t xc0 = __builtin_amdgcn_s_memtime();
 #endif
         if (!COUNT && express) {
-#if BDPT_ROOT_LDS
-            const RootLds* const coop_rl = root_in_lds ? &root_lds : nullptr;
-#else
-            const RootLds* const coop_rl = nullptr;
-#endif
             const uint64_t busy = __ballot(BDPT_BUSY(L.state)), wt = __ballot(coop_wait), bg = __ballot(began);
-#if BDPT_COOP_GROUPS
             if (!(P->fr.sched_flags & kSchedNoCoopGroups) && popc64(busy) >= 2 && popc64(busy) <= BDPT_COOP_MAX &&
                 (bg | wt) == busy) {
                 // 2-4 long walks: each walked by its own group of 32 or 16 lanes, all at once
@@ -780,20 +566,19 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                 qi.inv = mk(__shfl(ri.inv.x, sl), __shfl(ri.inv.y, sl), __shfl(ri.inv.z, sl));
                 qi.near = __shfl(ri.near, sl);
                 qi.fast = true;
-                const float guess = BDPT_GRAZE_IN_DIST ? -1.f : __shfl(L.h.dist, sl);
+                const float guess = __shfl(L.h.dist, sl);
                 const CoopStack cs{stack_mem + (threadIdx.x & ~63u), kBlock};
                 const int cap = kLdsStack * G, gbase = gi * cap;
                 const bool bounded = act && guess > 0.f;
                 float t = 0.f, u = 0.f, v = 0.f;
                 int r = -1;
                 bool ok = coop_closest_groups<SLACK>(tsc, q, qi, bounded ? 2.f * guess : q.max_t, act, cs, gbase, cap, G,
-                                                     t, r, u, v, coop_rl);
+                                                     t, r, u, v);
                 const bool again = bounded && ok && r < 0;  // nothing below the bound: the walk unbounded
                 if (__ballot(again)) {
                     float t2 = 0.f, u2 = 0.f, v2 = 0.f;
                     int r2 = -1;
-                    const bool ok2 = coop_closest_groups<SLACK>(tsc, q, qi, q.max_t, again, cs, gbase, cap, G, t2, r2, u2, v2,
-                                                                coop_rl);
+                    const bool ok2 = coop_closest_groups<SLACK>(tsc, q, qi, q.max_t, again, cs, gbase, cap, G, t2, r2, u2, v2);
                     if (again) t = t2, u = u2, v = v2, r = r2, ok = ok2;
                 }
                 // each walk's owner takes its group's result (group = the owner's rank among the busy lanes)
@@ -811,7 +596,6 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                     }
                 }
             } else
-#endif
             if (popc64(busy) <= BDPT_COOP_MAX && (bg | wt) == busy) {
                 const int b = __ffsll(static_cast<unsigned long long>(wt ? wt : bg)) - 1;
                 const int me = static_cast<int>(opaque_tid() & 63);
@@ -828,12 +612,6 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
 #if BDPT_CHAIN_RING_WAVE
                 uint32_t chain_g = 0;  // lane b's ring outputs generated, as the wave last left it (0: unknown)
 #endif
-#if BDPT_EXPRESS_CHAIN == 2
-                if (chain) {
-                    bounced = express_chain<SLACK>(L, b, ri, P->sc, P->fr, P->fb, tsc, stack_mem + (threadIdx.x & ~63u),
-                                                   coop_rl, t, r, u, v, ok);
-                } else
-#endif
                 for (;;) {
                     Ray q;
                     q.o = mk(lane_val(L.ray.o.x, b), lane_val(L.ray.o.y, b), lane_val(L.ray.o.z, b));
@@ -844,7 +622,7 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                     qi.near = lane_val(ri.near, b);
                     qi.fast = true;
                     // the lane's last hit distance (Hit::dist, shade_hit), the bound's guess
-                    const float guess = BDPT_GRAZE_IN_DIST ? -1.f : lane_val(L.h.dist, b);
+                    const float guess = lane_val(L.h.dist, b);
                     r = -1;
                     ok = true;
 #if BDPT_EXPRESS_PROBE
@@ -852,15 +630,13 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
 #endif
                     for (int pass = guess > 0.f ? 0 : 1; pass < 2 && r < 0 && ok; pass++) {
                         const float bound = pass == 0 ? 2.f * guess : q.max_t;
-                        ok = SLACK ? coop_closest<true, BDPT_COOP_BATCH>(tsc, q, qi, bound, cs, 64 * kLdsStack, t, r, u, v,
-                                                                         nullptr, coop_rl)
-                                   : coop_closest<false, BDPT_COOP_BATCH>(tsc, q, qi, bound, cs, 64 * kLdsStack, t, r, u, v,
-                                                                          nullptr, coop_rl);
+                        ok = SLACK ? coop_closest<true>(tsc, q, qi, bound, cs, 64 * kLdsStack, t, r, u, v)
+                                   : coop_closest<false>(tsc, q, qi, bound, cs, 64 * kLdsStack, t, r, u, v);
                     }
 #if BDPT_EXPRESS_PROBE
                     if (xp_lone) xp_walk += __builtin_amdgcn_s_memtime() - xw0;
 #endif
-                    if (BDPT_EXPRESS_CHAIN != 1 || !chain || !ok) break;
+                    if (!chain || !ok) break;
 #if BDPT_CHAIN_RING_WAVE
                     if (chain) {  // lane b's generator ring, refilled by the wave when its next bounce could reach the end
                         const uint32_t bn = static_cast<uint32_t>(lane_val(static_cast<int>(L.rng.n), b));
@@ -880,7 +656,6 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                             ++L.c.steps;
                             shade_hit(P->sc, r, u, v, t, L.ray.d, L.h);
                             const float dist2 = L.h.dist * L.h.dist;
-                            BDPT_DIST_TO_GRAZE
                             const float absCosIn = fabsf(L.h.wo.z);
 #if BDPT_DEEP_RNG && BDPT_RING_AHEAD
 #if BDPT_CHAIN_RING_WAVE
@@ -949,12 +724,10 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
 #endif
 #endif
         const uint64_t c0 = COUNT ? __builtin_amdgcn_s_memtime() : 0;
-#if BDPT_READY_HOIST
         // read once per shading step: in the walk loop its scalar load waited (lgkmcnt)
         // on the lane's LDS stack traffic every iteration
         const int steady_ready = P->fr.shade_ready > 0 ? P->fr.shade_ready : BDPT_SHADE_READY;
-#endif
-#if BDPT_HELP && BDPT_HELP_SREG
+#if BDPT_HELP
         // the ring's positions in scalar registers while the wave walks (pushes happen
         // only in the shading step; claims below write the head back)
         uint32_t qhead = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(*task_ctl(L.c).head)));
@@ -964,9 +737,7 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
 #if BDPT_HELP
             uint64_t tr = __ballot(tracing);
             const uint64_t ready = __ballot(has_res && !helping);  // helpers shade after their walk
-            if (popc64(ready) >= (BDPT_TAIL_SHADE == 1 && exhausted ? 1
-                                  : BDPT_TAIL_SHADE == 2 && exhausted ? max(1, (popc64(tr | ready) * BDPT_TAIL_FRAC) >> 3)
-                                                                      : steady_ready))
+            if (popc64(ready) >= (exhausted ? max(1, (popc64(tr | ready) * BDPT_TAIL_FRAC) >> 3) : steady_ready))
                 break;
             // Lanes that wait (a result kept, or no sample) claim the ring's oldest
             // tasks, one each, and walk their shadow rays with the walk code below.
@@ -987,30 +758,15 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                 } else {
                     ts = trav_begin(tsc, L.ray);
                     tracing = true;
-#if BDPT_ROOT_LDS
                     if (root_in_lds && !walk_begin_lds<COUNT, SLACK>(root_lds, L.ray, ri, true, ts, stk, cnt)) {
                         tracing = false;  // no child hit: unoccluded
                         hfin = true;
                     }
-#endif
                 }
             };
-#if BDPT_HELP_DEFER
-            if (hwait) {  // claimed in the previous iteration: its record has arrived meanwhile
-                hwait = false;
-                L.c.pend = mk(ts.best_t, ts.best_u, ts.best_v);
-                L.c.pend_px = static_cast<int>(ts.link);
-                help_begin(ri.near);
-            }
-#endif
-            const uint64_t hk0 = COUNT && BDPT_HELP_CLOCKS ? __builtin_amdgcn_s_memtime() : 0;
             {
                 const TaskCtl ctl = task_ctl(L.c);
-#if BDPT_HELP_SREG
                 const uint32_t head = qhead, tail = qtail;
-#else
-                const uint32_t head = *ctl.head, tail = *ctl.tail;
-#endif
                 // (a lane waiting on its own shadow ray, pushed by itself when the ring was
                 // full, keeps its pending contribution in L.c.pend: it does not help)
                 const bool cand = !helping && !tracing && (has_res ? !is_shadow_state(L.state) : L.state == ST_IDLE);
@@ -1023,75 +779,42 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                     const uint32_t n = min(static_cast<uint32_t>(popc64(cm)), tail - head);
                     const uint32_t rank = static_cast<uint32_t>(lanes_below(cm));
                     *ctl.head = head + n;
-#if BDPT_HELP_SREG
                     qhead = head + n;
-#endif
                     if (cand && rank < n) {
-#if !BDPT_HELP_HOIST
                         if (has_res) help_compact(L, res, rt, ru, rv, P->sc);  // frees L.ray
-#endif
                         const uint32_t slot = (head + rank) & (P->fr.task_cap - 1);
                         float4* const ring = task_ring(P->fr);
                         const uint32_t cap = P->fr.task_cap;
                         // the record (bdpt_path.hpp task_push): (P, meta) (end, c.x | c, -) (c.y, c.z)
                         const float4 a = gld4(task_vec(ring, cap, slot, 0)), b = gld4(task_vec(ring, cap, slot, 1));
                         const uint32_t meta = __float_as_uint(a.w);
-#if BDPT_HELP_LAZY_TAIL
-                        const float2 cyz = meta & kTaskSplat ? make_float2(b.y, b.z) : gld2(task_tail(ring, cap, slot));
-#else
                         const float2 ctl2 = gld2(task_tail(ring, cap, slot));
                         const float2 cyz = meta & kTaskSplat ? make_float2(b.y, b.z) : ctl2;
-#endif
                         const f3 c = meta & kTaskSplat ? mk(b.x, cyz.x, cyz.y) : mk(b.w, cyz.x, cyz.y);
                         const f3 rs = meta & kTaskSplat ? mk(P->fr.cam_o[0], P->fr.cam_o[1], P->fr.cam_o[2]) : xyz(a);
                         const f3 re = meta & kTaskSplat ? xyz(a) : xyz(b);
                         const float near = meta & kTaskNoCull ? kNoCullNear : kCullNear;
-#if BDPT_HELP_HOIST
-                        // the record's loads are in flight while the lane's own hit is shaded
-                        // (one exposed latency per claim round instead of two)
-                        if (has_res) help_compact(L, res, rt, ru, rv, P->sc);  // frees L.ray
-#endif
                         if (COUNT) cnt.q[3]++;  // (counting pass: claims)
                         // visibilityQuery's ray of the two points, by the pusher's own code (the same bits)
                         L.ray = shadow_ray(rs, re);
                         helping = true;
-#if BDPT_HELP_DEFER
-                        // the walk begins next iteration (the loads land meanwhile): the near
-                        // cull, contribution and pixel wait in the lane's idle walk registers
-                        ri.near = near;
-                        ts.best_t = c.x, ts.best_u = c.y, ts.best_v = c.z;
-                        ts.link = meta & ~kTaskNoCull;
-                        hwait = true;
-#else
                         // the contribution and pixel | splat bit into the lane's (free) pending-
                         // connection fields: the slot may be pushed over once claimed
                         L.c.pend = c;
                         L.c.pend_px = static_cast<int>(meta & ~kTaskNoCull);
                         help_begin(near);
-#endif
                     }
                 }
             }
-            if (COUNT && BDPT_HELP_CLOCKS && first_active_lane())  // (probe build: claim block clocks in stack_gt8)
-                cnt.c[16] += static_cast<uint32_t>(__builtin_amdgcn_s_memtime() - hk0);
             tr = __ballot(tracing);
-#if BDPT_HELP_DEFER
-            if (!tr && !__ballot(hfin) && !__ballot(hwait)) break;
-#else
             if (!tr && !__ballot(hfin)) break;
-#endif
 #else
             const uint64_t tr = __ballot(tracing);
             if (!tr) break;
             const uint64_t ready = __ballot(has_res);
             if (popc64(ready) >= (express ? 1
-                                    : BDPT_TAIL_SHADE == 1 && exhausted ? 1
-                                    : BDPT_TAIL_SHADE == 2 && exhausted ? max(1, (popc64(tr | ready) * BDPT_TAIL_FRAC) >> 3)
-#if BDPT_READY_HOIST
-                                                                        : steady_ready))
-#else
-                                                                        : (P->fr.shade_ready > 0 ? P->fr.shade_ready : BDPT_SHADE_READY)))
-#endif
+                                  : exhausted ? max(1, (popc64(tr | ready) * BDPT_TAIL_FRAC) >> 3)
+                                              : steady_ready))
                 break;
 #endif
 #if BDPT_TRAV_SPLIT
@@ -1102,11 +825,11 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
             const uint64_t lv = __ballot(tracing && at_leaf);
             const bool do_leaf = popc64(lv) * 4 >= popc64(tr & ~lv) * BDPT_TRAV_SPLIT;
             bool fin = tracing && at_leaf == do_leaf && trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt);
-            // BDPT_WALK_UNROLL more interior-node steps before the wave's ballots
+            // BDPT_WALK_UNROLL more interior-node steps before the wave's ballots, also after
+            // a leaf iteration, for lanes that popped to an interior node
 #pragma unroll
             for (int k = 0; k < BDPT_WALK_UNROLL; k++)
-                if ((BDPT_UNROLL_ANY || !do_leaf) && tracing && !fin && !(ts.link & kLeafBit))
-                    fin = trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt);
+                if (tracing && !fin && !(ts.link & kLeafBit)) fin = trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt);
             if (fin) {
 #else
             if (tracing && trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt)) {
@@ -1126,7 +849,6 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
 #endif
             }
 #if BDPT_HELP
-            const uint64_t hk1 = COUNT && BDPT_HELP_CLOCKS ? __builtin_amdgcn_s_memtime() : 0;
             if (hfin) {  // the task's shadow ray: unoccluded -> its contribution to the pixel
                 helping = false;
                 if (ts.best < 0) {
@@ -1140,8 +862,6 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
                     }
                 }
             }
-            if (COUNT && BDPT_HELP_CLOCKS && first_active_lane())  // (probe build: completion clocks in stack_gt12)
-                cnt.c[17] += static_cast<uint32_t>(__builtin_amdgcn_s_memtime() - hk1);
 #endif
         }
         const uint64_t c1 = COUNT ? __builtin_amdgcn_s_memtime() : 0;
@@ -1170,10 +890,7 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
 #if BDPT_HELP_BATCH
         // the connections of the eye vertices reached in this step, over the whole wave
         if (__ballot(shade_now)) {
-            const uint64_t hk2 = COUNT && BDPT_HELP_CLOCKS ? __builtin_amdgcn_s_memtime() : 0;
             conn_batch<COUNT>(L, shade_now && act2 == A_CONN && P->fr.strategy == 0, P->sc, P->fr, ls, cnt);
-            if (COUNT && BDPT_HELP_CLOCKS && first_active_lane())  // (probe build: batch clocks in stack_gt16)
-                cnt.c[18] += static_cast<uint32_t>(__builtin_amdgcn_s_memtime() - hk2);
             if (shade_now) advance<COUNT, 2>(L, act2, P->sc, P->fr, P->fb, ls, cnt);
         }
 #endif
@@ -1188,15 +905,12 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
             cnt.t_step = 0;
             if (lane0()) cnt.q[0] += tw, cnt.q[1]++, cnt.q[2] += tw >= 32u, cnt.q[3] += tw >= 64u;
         }
-#else
-        if (L.state != ST_IDLE) step<FULL, COUNT>(L, P->sc, P->fr, P->fb, ls, stk, cnt);
-#endif
     }
 #if BDPT_SEED_CHUNK && BDPT_EYE_SLOTS
     if (lane0())  // every sample of the wave has finished: the slots' sums to the framebuffer
         for (int k = 0; k < BDPT_EYE_SLOTS; k++) eye_slot_reset(kp.fb, k, -1);
 #endif
-    if (BDPT_DIAG && lane0() && kpp->fr.diag) gmax(kpp->fr.diag + kDiagEnd, __builtin_amdgcn_s_memrealtime());
+    if (lane0() && kpp->fr.diag) gmax(kpp->fr.diag + kDiagEnd, __builtin_amdgcn_s_memrealtime());
 #if BDPT_EXPRESS_PROBE
     if (lane0() && xp_iters) {  // into bdpt_stats.sched (a timed run writes nothing else there)
         gadd(kpp->counters + kCounters + 3, static_cast<unsigned long long>(xp_iters));
@@ -1222,23 +936,14 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void bdpt_frame_kernel(c
     }
 }
 
-
 #if BDPT_PARK
 // The continuation pass's chain kernel: one wave per parked sample (see park_lane).
-#ifndef BDPT_CHAIN_PROBE
-#define BDPT_CHAIN_PROBE 0
-#endif
-#ifndef BDPT_CHAIN_LDS_RING
-#define BDPT_CHAIN_LDS_RING 1  // the chain's MT19937 ring in LDS (each draw an LDS read instead of an HBM round trip)
-#endif
 constexpr int kChainStack = 2048;  // LDS entries of the wave's shared walk stack
-__global__ __launch_bounds__(64) void bdpt_chain_kernel(const KParams* __restrict__ kpp) {
+__global__ __launch_bounds__(64) void BDPT_NAME(bdpt_chain_kernel)(const KParams* __restrict__ kpp) {
     const KParams& kp = *kpp;
     __shared__ uint2 cstack[kChainStack];
     __shared__ LaneCold cold;
-#if BDPT_CHAIN_LDS_RING
     __shared__ uint32_t lring[kMtRingSlotWords];
-#endif
     scene_tables_to_lds(kp.sc);
     const uint32_t lane = threadIdx.x;
 #if BDPT_EYE_SLOTS
@@ -1251,18 +956,11 @@ __global__ __launch_bounds__(64) void bdpt_chain_kernel(const KParams* __restric
     const gbl_u32* const list = (const gbl_u32*)park_list(fr, kp.nslots);
     const uint32_t n = list[0];
     Counts cnt;  // (not a counting pass)
-    // BDPT_CHAIN_PROBE: bounces, walk rounds, and the longest walk's bounces and clocks into bdpt_stats.sched
-    uint64_t pc[4] = {0u, 0u, 0u, 0u};
-    uint32_t rounds32 = 0;
-    uint32_t* const probe_rounds = BDPT_CHAIN_PROBE ? &rounds32 : nullptr;
-    const uint64_t k0 = BDPT_CHAIN_PROBE ? __builtin_amdgcn_s_memtime() : 0;
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
         const uint32_t slot = list[1 + i];
         uint32_t* const rec = park_record(fr, slot);
         Lane L(cold);
         float guess = -1.f;  // the last hit distance of this chain (wave-uniform)
-        const uint64_t w0 = BDPT_CHAIN_PROBE ? __builtin_amdgcn_s_memtime() : 0, wb = pc[0];
-#if BDPT_CHAIN_LDS_RING
         // the slot's MT19937 ring (and generator cursor) in LDS while the chain draws from it
         gbl_u32* const hring = (gbl_u32*)(sc.mt_ring + static_cast<size_t>(slot) * kMtRingSlotWords);
         for (uint32_t k = lane; k < kMtRingSlotWords; k += 64) lring[k] = hring[k];
@@ -1273,14 +971,7 @@ __global__ __launch_bounds__(64) void bdpt_chain_kernel(const KParams* __restric
             park_restore(rec, L);
         }
         __syncthreads();
-#else
-        if (lane == 0) {
-            park_restore(rec, L);
-            g_scene_lds[3] = slot;  // the sample's MT19937 ring (mt_ring_slot, lane 0)
-        }
-#endif
         for (;;) {
-            const uint64_t c0 = BDPT_CHAIN_PROBE ? __builtin_amdgcn_s_memtime() : 0;
             // lane 0's query, walked by the wave
             Ray q;
             q.o = mk(lane_val(L.ray.o.x, 0), lane_val(L.ray.o.y, 0), lane_val(L.ray.o.z, 0));
@@ -1298,10 +989,9 @@ __global__ __launch_bounds__(64) void bdpt_chain_kernel(const KParams* __restric
             for (int pass = guess > 0.f ? 0 : 1; pass < 2 && r < 0 && ok; pass++) {
                 const float bound = pass == 0 ? 2.f * guess : q.max_t;
                 const CoopStack cs{cstack, 0};
-                ok = tsc.node_slack ? coop_closest<true>(tsc, q, ri, bound, cs, kChainStack, t, r, u, v, probe_rounds)
-                                    : coop_closest<false>(tsc, q, ri, bound, cs, kChainStack, t, r, u, v, probe_rounds);
+                ok = tsc.node_slack ? coop_closest<true>(tsc, q, ri, bound, cs, kChainStack, t, r, u, v)
+                                    : coop_closest<false>(tsc, q, ri, bound, cs, kChainStack, t, r, u, v);
             }
-            if (BDPT_CHAIN_PROBE) pc[0]++, pc[2] += __builtin_amdgcn_s_memtime() - c0;
             guess = r >= 0 ? t : -1.f;
             if (!ok) {
                 if (lane == 0 && fr.diag) gadd(fr.diag + kDiagErrors, 1ull);
@@ -1313,12 +1003,11 @@ __global__ __launch_bounds__(64) void bdpt_chain_kernel(const KParams* __restric
             if (!is_delta(b) || !is_zero(ld3(b.emission))) break;  // a vertex the megakernel shades
             int more = 0;
             if (lane == 0 && L.c.steps + 1 <= (1 << 30)) {
-                // the sweep's work at a delta, non-emitting vertex (express_walk's bounce): resolve(),
+                // the sweep's work at a delta, non-emitting vertex: resolve(),
                 // the vertex update (bdpt.h:193-209 / :73-136), ContinuePathRandomWalk, the loop test
                 ++L.c.steps;
                 shade_hit(sc, r, u, v, t, L.ray.d, L.h);
                 const float dist2 = L.h.dist * L.h.dist;
-                BDPT_DIST_TO_GRAZE
                 const float absCosIn = fabsf(L.h.wo.z);
 #if BDPT_RING_AHEAD
                 if (L.rng.n + BDPT_RING_AHEAD >= 227 && !mt_ring_ahead(L.rng) && fr.diag)
@@ -1342,21 +1031,10 @@ __global__ __launch_bounds__(64) void bdpt_chain_kernel(const KParams* __restric
         if (lane == 0) {
             park_save(rec, L);
             ((gbl_u32*)rec)[kParkStatus] = 2u;
-            if (BDPT_CHAIN_PROBE) {  // the longest walk: its bounces and clocks
-                gmax(kp.counters + kCounters + 3 + 2, static_cast<unsigned long long>(pc[0] - wb));
-                gmax(kp.counters + kCounters + 3 + 3, static_cast<unsigned long long>(__builtin_amdgcn_s_memtime() - w0));
-            }
         }
-#if BDPT_CHAIN_LDS_RING
         __syncthreads();
         for (uint32_t k = lane; k < kMtRingSlotWords; k += 64) hring[k] = lring[k];
-#endif
     }
-    if (BDPT_CHAIN_PROBE && lane == 0 && n > blockIdx.x) {
-        gadd(kp.counters + kCounters + 3, static_cast<unsigned long long>(pc[0]));
-        gadd(kp.counters + kCounters + 3 + 1, static_cast<unsigned long long>(rounds32));
-    }
-    (void)k0;
 }
 #endif
 #endif  // !BDPT_SAMPLER_STATE
@@ -1366,7 +1044,7 @@ __global__ __launch_bounds__(64) void bdpt_chain_kernel(const KParams* __restric
 // sample_state.hip): the sampler is the caller's std::mt19937 state, whose
 // address sc.mt_ring carries into the LDS header (mt_state_u32); splats go to
 // the list `fb` (splat_add). out = Li.xyz, draws taken.
-__global__ __launch_bounds__(64) void bdpt_sample_kernel(DevScene sc, DevFrame fr, float* __restrict__ fb,
+__global__ __launch_bounds__(64) void BDPT_NAME(bdpt_sample_kernel)(DevScene sc, DevFrame fr, float* __restrict__ fb,
                                                          float* __restrict__ lvbuf, uint2* __restrict__ gstack,
                                                          Ray ray, float* __restrict__ out) {
     __shared__ uint2 stack_mem[kLdsStack * 64];
@@ -1397,10 +1075,7 @@ __global__ __launch_bounds__(64) void bdpt_sample_kernel(DevScene sc, DevFrame f
 
 // ------------------------------------------------------------ host launchers
 #if !BDPT_SAMPLER_STATE
-size_t frame_params_bytes() { return sizeof(dev::KParams); }
-
-// `dparams` is a device buffer of frame_params_bytes() owned by the caller; it
-// is filled on `stream` before the launch (stream order protects reuse).
+namespace {
 hipError_t launch_frame(const dev::DevScene& sc, const dev::DevFrame& fr, float* fb, float* lvbuf, uint2* gstack,
                         uint32_t nslots, unsigned long long* work, unsigned long long* counters, int grid,
                         hipStream_t stream, void* dparams) {
@@ -1412,15 +1087,14 @@ hipError_t launch_frame(const dev::DevScene& sc, const dev::DevFrame& fr, float*
     const dim3 g(grid), b(dev::kBlock);
     const size_t lds = 4 * static_cast<size_t>(sc.lds_words);
     // FULL walks the reference's binary tree: SLACK does not apply
-    if (full && count) hipLaunchKernelGGL((dev::bdpt_frame_kernel<true, true, true>), g, b, lds, stream, kp);
-    else if (full) hipLaunchKernelGGL((dev::bdpt_frame_kernel<true, false, true>), g, b, lds, stream, kp);
-    else if (count && slack) hipLaunchKernelGGL((dev::bdpt_frame_kernel<false, true, true>), g, b, lds, stream, kp);
-    else if (count) hipLaunchKernelGGL((dev::bdpt_frame_kernel<false, true, false>), g, b, lds, stream, kp);
-    else if (slack) hipLaunchKernelGGL((dev::bdpt_frame_kernel<false, false, true>), g, b, lds, stream, kp);
-    else hipLaunchKernelGGL((dev::bdpt_frame_kernel<false, false, false>), g, b, lds, stream, kp);
+    if (full && count) hipLaunchKernelGGL((dev::BDPT_NAME(bdpt_frame_kernel)<true, true, true>), g, b, lds, stream, kp);
+    else if (full) hipLaunchKernelGGL((dev::BDPT_NAME(bdpt_frame_kernel)<true, false, true>), g, b, lds, stream, kp);
+    else if (count && slack) hipLaunchKernelGGL((dev::BDPT_NAME(bdpt_frame_kernel)<false, true, true>), g, b, lds, stream, kp);
+    else if (count) hipLaunchKernelGGL((dev::BDPT_NAME(bdpt_frame_kernel)<false, true, false>), g, b, lds, stream, kp);
+    else if (slack) hipLaunchKernelGGL((dev::BDPT_NAME(bdpt_frame_kernel)<false, false, true>), g, b, lds, stream, kp);
+    else hipLaunchKernelGGL((dev::BDPT_NAME(bdpt_frame_kernel)<false, false, false>), g, b, lds, stream, kp);
     return hipGetLastError();
 }
-
 
 #if BDPT_PARK
 // The Russian-roulette continuation pass's chain kernel (one wave per parked
@@ -1431,39 +1105,47 @@ hipError_t launch_chain(const dev::DevScene& sc, const dev::DevFrame& fr, float*
     const dev::KParams host{sc, fr, fb, lvbuf, gstack, nslots, work, counters};
     hipError_t e = hipMemcpyAsync(dparams, &host, sizeof(host), hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dev::bdpt_chain_kernel, dim3(grid), dim3(64), 4 * static_cast<size_t>(sc.lds_words), stream,
-                       static_cast<const dev::KParams*>(dparams));
-    return hipGetLastError();
-}
-#endif
-#endif  // !BDPT_SAMPLER_STATE
-
-#if BDPT_SAMPLER_STATE
-// sc.mt_ring = the device copy of the caller's std::mt19937 state (625 words);
-// splats = the splat list (header + records, see splat_add).
-hipError_t launch_sample(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf, uint2* gstack,
-                         const dev::Ray& ray, float* out, hipStream_t stream) {
-    hipLaunchKernelGGL(dev::bdpt_sample_kernel, dim3(1), dim3(64), 4 * static_cast<size_t>(sc.lds_words), stream, sc,
-                       fr, splats, lvbuf, gstack, ray, out);
+    hipLaunchKernelGGL(dev::BDPT_NAME(bdpt_chain_kernel), dim3(grid), dim3(64), 4 * static_cast<size_t>(sc.lds_words),
+                       stream, static_cast<const dev::KParams*>(dparams));
     return hipGetLastError();
 }
 #else
+constexpr FrameBuild::Launch launch_chain = nullptr;
+#endif
 
-// Resident 256-lane blocks per CU for the frame kernel (VGPR and LDS limited).
-int frame_kernel_blocks_per_cu(size_t dyn_lds) {
+int blocks_per_cu(size_t dyn_lds) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dev::bdpt_frame_kernel<false, false, false>, dev::kBlock,
-                                                     dyn_lds) !=
-            hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dev::BDPT_NAME(bdpt_frame_kernel)<false, false, false>,
+                                                     dev::kBlock, dyn_lds) != hipSuccess ||
         n <= 0)
         n = BDPT_WAVES_PER_EU;
     return n;
 }
+}  // namespace
 
-int frame_kernel_lds_stack() { return dev::kLdsStack; }
-int frame_kernel_block() { return dev::kBlock; }
-int light_vertex_fields() { return dev::kLvFields; }
+// The build without glossy lobes reports the default build's name (callers key their
+// schedules on it); FrameBuild::glossy tells the two apart. (Not const: a const object
+// with a constant initializer is emitted into the device code too.)
+FrameBuild BDPT_NAME(frame_build) = {
+    /* name */ BDPT_GLOSSY ? BDPT_STR(BDPT_NAME(bdpt_frame_kernel)) : "bdpt_frame_kernel",
+    /* glossy */ BDPT_GLOSSY,
+    /* launch_frame */ launch_frame,
+    /* launch_chain */ launch_chain,
+    /* blocks_per_cu */ blocks_per_cu,
+    /* light_vertex_fields */ dev::kLvFields,
+    /* block */ dev::kBlock,
+    /* lds_stack */ dev::kLdsStack,
+    /* params_bytes */ sizeof(dev::KParams)};
 
+#else
+// sc.mt_ring = the device copy of the caller's std::mt19937 state (625 words);
+// splats = the splat list (header + records, see splat_add).
+hipError_t BDPT_NAME(launch_sample)(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf,
+                                    uint2* gstack, const dev::Ray& ray, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(dev::BDPT_NAME(bdpt_sample_kernel), dim3(1), dim3(64), 4 * static_cast<size_t>(sc.lds_words),
+                       stream, sc, fr, splats, lvbuf, gstack, ray, out);
+    return hipGetLastError();
+}
 #endif  // BDPT_SAMPLER_STATE
 
 }  // namespace bdpt

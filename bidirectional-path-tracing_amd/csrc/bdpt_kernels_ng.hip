@@ -9,13 +9,5 @@
 // the default build. Chosen per render (bdpt_capi.cpp; BDPT_NG_BUILD=0/1); every
 // host-visible symbol gets an _ng name.
 #define BDPT_GLOSSY 0
-#define bdpt_frame_kernel bdpt_frame_kernel_ng
-#define bdpt_sample_kernel bdpt_sample_kernel_ng
-#define frame_params_bytes frame_params_bytes_ng
-#define launch_frame launch_frame_ng
-#define launch_sample launch_sample_ng
-#define frame_kernel_blocks_per_cu frame_kernel_blocks_per_cu_ng
-#define frame_kernel_lds_stack frame_kernel_lds_stack_ng
-#define frame_kernel_block frame_kernel_block_ng
-#define light_vertex_fields light_vertex_fields_ng
+#define BDPT_VARIANT _ng
 #include "bdpt_kernels.hip"

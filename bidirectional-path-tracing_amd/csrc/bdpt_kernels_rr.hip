@@ -7,15 +7,5 @@
 // bdpt_kernels.hip; every host-visible symbol gets an _rr name.
 #define BDPT_DEEP_RNG 1
 #define BDPT_RR 1
-#define bdpt_frame_kernel bdpt_frame_kernel_rr
-#define bdpt_sample_kernel bdpt_sample_kernel_rr
-#define frame_params_bytes frame_params_bytes_rr
-#define launch_frame launch_frame_rr
-#define launch_chain launch_chain_rr
-#define bdpt_chain_kernel bdpt_chain_kernel_rr
-#define launch_sample launch_sample_rr
-#define frame_kernel_blocks_per_cu frame_kernel_blocks_per_cu_rr
-#define frame_kernel_lds_stack frame_kernel_lds_stack_rr
-#define frame_kernel_block frame_kernel_block_rr
-#define light_vertex_fields light_vertex_fields_rr
+#define BDPT_VARIANT _rr
 #include "bdpt_kernels.hip"

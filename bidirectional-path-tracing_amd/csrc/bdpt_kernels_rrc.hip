@@ -11,15 +11,5 @@
 #define BDPT_DEEP_RNG 1
 #define BDPT_RR 1
 #define BDPT_EXPRESS_CHAIN 1
-#define bdpt_frame_kernel bdpt_frame_kernel_rrc
-#define bdpt_sample_kernel bdpt_sample_kernel_rrc
-#define frame_params_bytes frame_params_bytes_rrc
-#define launch_frame launch_frame_rrc
-#define launch_chain launch_chain_rrc
-#define bdpt_chain_kernel bdpt_chain_kernel_rrc
-#define launch_sample launch_sample_rrc
-#define frame_kernel_blocks_per_cu frame_kernel_blocks_per_cu_rrc
-#define frame_kernel_lds_stack frame_kernel_lds_stack_rrc
-#define frame_kernel_block frame_kernel_block_rrc
-#define light_vertex_fields light_vertex_fields_rrc
+#define BDPT_VARIANT _rrc
 #include "bdpt_kernels.hip"

@@ -14,7 +14,6 @@
 namespace bdpt {
 namespace dev {
 
-
 // Floats of a stored light vertex: p vcm n vc wo rr tp mat (64 B), and in the textured
 // builds a fifth float4 (tkd, tks, 0, 0): connectVertices evaluates the stored vertex's
 // BSDF again (bdpt.h:434-483), so its texels travel with it (80 B).
@@ -86,71 +85,45 @@ struct Vertex {  // PathVertex (bdpt.h:24-35); its Frame is rebuilt from n where
 #endif
 };
 
-#ifndef BDPT_LV_NT
-#define BDPT_LV_NT 0  // 1: light-vertex records use non-temporal loads / stores (keep L2 for the scene)
-#endif
-__device__ __forceinline__ void lv_st(float4* p, float4 x) {
-#if BDPT_LV_NT
-    __builtin_nontemporal_store(v4f_t{x.x, x.y, x.z, x.w}, (__attribute__((address_space(1))) v4f_t*)(p));
-#else
-    gst4(p, x);
-#endif
-}
-__device__ __forceinline__ float4 lv_ld(const float4* p) {
-#if BDPT_LV_NT
-    const v4f_t v = __builtin_nontemporal_load((const __attribute__((address_space(1))) v4f_t*)(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return gld4(p);
-#endif
-}
-#ifndef BDPT_PROBE_NO_LV_STORE
-#define BDPT_PROBE_NO_LV_STORE 0  // accounting probe only (a wrong image): light-vertex records not written
-#endif
 __device__ __forceinline__ void store_vertex(const LightStore& ls, int v, const Hit& h, f3 tp, float vcm, float vc,
                                              float rr) {
-    if (BDPT_PROBE_NO_LV_STORE) return;
     float4* q = ls.at(v);
-    lv_st(q, make_float4(h.p.x, h.p.y, h.p.z, vcm));
-    lv_st(q + 1, make_float4(h.n.x, h.n.y, h.n.z, vc));
-    lv_st(q + 2, make_float4(h.wo.x, h.wo.y, h.wo.z, rr));
-    lv_st(q + 3, make_float4(tp.x, tp.y, tp.z, __int_as_float(h.mat)));
+    gst4(q, make_float4(h.p.x, h.p.y, h.p.z, vcm));
+    gst4(q + 1, make_float4(h.n.x, h.n.y, h.n.z, vc));
+    gst4(q + 2, make_float4(h.wo.x, h.wo.y, h.wo.z, rr));
+    gst4(q + 3, make_float4(tp.x, tp.y, tp.z, __int_as_float(h.mat)));
 #if BDPT_TEXTURED
-    lv_st(q + 4, make_float4(__int_as_float(h.tkd), __int_as_float(h.tks), 0.f, 0.f));
+    gst4(q + 4, make_float4(__int_as_float(h.tkd), __int_as_float(h.tks), 0.f, 0.f));
 #endif
 }
 
 __device__ __forceinline__ Vertex load_vertex_at(const float4* q) {
-    const float4 a = lv_ld(q), b = lv_ld(q + 1), c = lv_ld(q + 2), d = lv_ld(q + 3);
+    const float4 a = gld4(q), b = gld4(q + 1), c = gld4(q + 2), d = gld4(q + 3);
     Vertex x;
     x.p = xyz(a), x.vcm = a.w;
     x.n = xyz(b), x.vc = b.w;
     x.wo = xyz(c), x.rr = c.w;
     x.tp = xyz(d), x.mat = __float_as_int(d.w);
 #if BDPT_TEXTURED
-    const float4 e = lv_ld(q + 4);
+    const float4 e = gld4(q + 4);
     x.tkd = __float_as_int(e.x), x.tks = __float_as_int(e.y);
 #endif
     return x;
 }
 __device__ __forceinline__ Vertex load_vertex(const LightStore& ls, int v) {
     const float4* q = ls.at(v);
-    const float4 a = lv_ld(q), b = lv_ld(q + 1), c = lv_ld(q + 2), d = lv_ld(q + 3);
+    const float4 a = gld4(q), b = gld4(q + 1), c = gld4(q + 2), d = gld4(q + 3);
     Vertex x;
     x.p = xyz(a), x.vcm = a.w;
     x.n = xyz(b), x.vc = b.w;
     x.wo = xyz(c), x.rr = c.w;  // rr: always 1 under NO_RR (bdpt.h:18), where x * rr == x is not formed
     x.tp = xyz(d), x.mat = __float_as_int(d.w);
 #if BDPT_TEXTURED
-    const float4 e = lv_ld(q + 4);
+    const float4 e = gld4(q + 4);
     x.tkd = __float_as_int(e.x), x.tks = __float_as_int(e.y);
 #endif
     return x;
 }
-
-#ifndef BDPT_CONN_EARLY_COS
-#define BDPT_CONN_EARLY_COS 3  // 1: connectVertices rejects on the cosines before building frames; 2: also connectToLight (+1.3 %); 3: also connectToCamera (+0.6 %)
-#endif
 
 // ContinuePathRandomWalk (bdpt.h:243-291): BSDF sample (2 draws), throughput,
 // vc / vcm recursion (Georgiev VCM Eqs. 52-54) and the next ray.
@@ -289,9 +262,6 @@ struct Lane {
 // The single-sample build returns the splats of its one sample as a list
 // instead (fb = header {count, capacity, 0, 0} then (pixel, r, g, b) records),
 // so the caller adds them to its own framebuffer in the reference's order.
-#ifndef BDPT_PROBE_NO_SPLAT
-#define BDPT_PROBE_NO_SPLAT 0
-#endif
 __device__ __forceinline__ void splat_add(float* __restrict__ fb, int pixel, f3 v) {
 #if BDPT_SAMPLER_STATE
     uint32_t* const hdr = reinterpret_cast<uint32_t*>(fb);
@@ -301,8 +271,6 @@ __device__ __forceinline__ void splat_add(float* __restrict__ fb, int pixel, f3 
         float* e = fb + 4 + 4 * static_cast<size_t>(k);
         e[0] = __int_as_float(pixel), e[1] = v.x, e[2] = v.y, e[3] = v.z;
     }
-#elif BDPT_PROBE_NO_SPLAT
-    (void)fb, (void)pixel, (void)v;  // accounting probe only (a wrong image): no camera-splat atomics
 #else
     float* px = fb + 3 * static_cast<size_t>(pixel);
     gadd(px + 0, v.x);
@@ -389,7 +357,6 @@ __device__ __forceinline__ TaskCtl task_ctl(const LaneCold& mine) {
 //   B float4 (end, c.x)    splat: (c, -)
 //   C float2 (c.y, c.z)    eye-side tasks only
 // 40 bytes stored and loaded for an eye-side task, 28 stored for a splat.
-#if BDPT_HELP_SOA
 __device__ __forceinline__ float4* task_ring(const DevFrame& fr) {
     const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x * 4 + (threadIdx.x >> 6))));
     return fr.tasks + static_cast<size_t>(wave) * (fr.task_cap / 2) * (kTaskBytes / 8);  // (task_cap is even: a power of two >= 64)
@@ -400,18 +367,6 @@ __device__ __forceinline__ float4* task_vec(float4* ring, uint32_t cap, uint32_t
 __device__ __forceinline__ float2* task_tail(float4* ring, uint32_t cap, uint32_t slot) {  // plane C
     return reinterpret_cast<float2*>(ring + 2 * static_cast<size_t>(cap)) + slot;
 }
-#else  // records of 3 float4 (plane C's float2 in the third), slot after slot
-__device__ __forceinline__ float4* task_ring(const DevFrame& fr) {
-    const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x * 4 + (threadIdx.x >> 6))));
-    return fr.tasks + static_cast<size_t>(wave) * fr.task_cap * (kTaskBytes / 16);
-}
-__device__ __forceinline__ float4* task_vec(float4* ring, uint32_t, uint32_t slot, int k) {
-    return ring + 3 * static_cast<size_t>(slot) + k;
-}
-__device__ __forceinline__ float2* task_tail(float4* ring, uint32_t, uint32_t slot) {
-    return reinterpret_cast<float2*>(ring + 3 * static_cast<size_t>(slot) + 2);
-}
-#endif
 // Called by the lanes that push (their exec mask is the set): true if this lane's
 // task went into the ring (false: the ring is full; the caller traces it itself).
 // start, end: the arguments of the task's shadow_ray (a splat's start is the camera).
@@ -546,17 +501,6 @@ __device__ __forceinline__ bool walk_continues(Lane& L, const DevFrame& fr) {
 // vertex (NEE, connectVertices): true = no near cull.
 __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
 
-// BDPT_GRAZE_IN_DIST 1: a vertex's near-cull threshold (graze_threshold) is
-// decoded once, in its vertex body, into Hit::dist (dead after that body), and
-// the queries leaving the vertex compare against it (cull_near_for).
-#ifndef BDPT_GRAZE_IN_DIST
-#define BDPT_GRAZE_IN_DIST 0
-#endif
-#if BDPT_GRAZE_IN_DIST
-#define BDPT_DIST_TO_GRAZE L.h.dist = graze_threshold(L.h.shape);
-#else
-#define BDPT_DIST_TO_GRAZE
-#endif
 #ifndef BDPT_SPLIT_CONTINUE
 #define BDPT_SPLIT_CONTINUE 0  // 1: the light subpath's continuation runs before the eye subpath's start, so a light walk that ends starts its eye walk in the same sweep (no ST_DEFER step); the eye continuation is its own body
 #endif
@@ -564,7 +508,6 @@ __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
 #define BDPT_BODY_LIGHT_VERTEX \
     BDPT_ACTION(26, act == A_LIGHT_VERTEX) {  /* bdpt.h:193-209 */ \
         const float dist2 = L.h.dist * L.h.dist; \
-        BDPT_DIST_TO_GRAZE \
         const float absCosIn = fabsf(L.h.wo.z); \
         L.c.vcm *= div_w(dist2, absCosIn); \
         L.c.vc *= rcp_w(absCosIn); \
@@ -582,12 +525,11 @@ __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
         if (xp < 0 || yp < 0 || xp >= fr.W || yp >= fr.H) break; \
         const float cosCamera = dot(fwd, e2l); \
         if (cosCamera <= 0.f) break; \
-        const bool early_cos_ = BDPT_CONN_EARLY_COS >= 3; /* reject on wi.z = dot(-e2l, n) (the frame z component, to_local) first */ \
-        if (early_cos_ && dot(-e2l, L.h.n) <= 0.f) break; \
-        const f3 wi = early_cos_ ? local_for(b, L.h.n, -e2l) : local_at(L.h.n, -e2l); \
+        if (dot(-e2l, L.h.n) <= 0.f) break; /* reject on wi.z = dot(-e2l, n) (the frame z component, to_local) first */ \
+        const f3 wi = local_for(b, L.h.n, -e2l); \
         const EvalPdfs ep = bsdf_eval_pdfs(b, wi, L.h.wo); \
         const f3 f = ep.f; \
-        if (is_zero(f) || (!early_cos_ && wi.z <= 0.f)) break; \
+        if (is_zero(f)) break; \
         const float d = div_w(fr.cam.vnear, cosCamera); \
         const float img2solid = div_w(d * d, cosCamera); \
         const float img2surf = img2solid * (wi.z * invD2); \
@@ -705,7 +647,6 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
     } BDPT_END;
     BDPT_ACTION(22, act == A_EYE_VERTEX) {  // bdpt.h:73-136
         const float dist2 = L.h.dist * L.h.dist;
-        BDPT_DIST_TO_GRAZE
         const float absCosIn = fabsf(L.h.wo.z);
         L.c.vcm *= div_w(dist2, absCosIn);
         L.c.vc *= rcp_w(absCosIn);
@@ -762,11 +703,7 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
         make_frame(e_n, fs, ft);
         L.ray = Ray{e_p, to_world(fs, ft, e_n, edir), kEpsilon, 3.402823466e+38f};
         L.h.n = e_n;  // the surface the first light ray leaves (cull_near_for); the walk's resolve overwrites L.h
-#ifndef BDPT_EMIT_GRAZE
-#define BDPT_EMIT_GRAZE 1  // 0: the emitter face's graze code is not used (A/B only)
-#endif
-        if (BDPT_EMIT_GRAZE) L.h.shape = e_graze;  // its graze code (the shape id is not read before the walk's resolve)
-        if (BDPT_GRAZE_IN_DIST) L.h.dist = graze_threshold(e_graze);
+        L.h.shape = e_graze;  // its graze code (the shape id is not read before the walk's resolve)
         L.c.tp = (ld3(e.radiance) * edir.z) * rcp_w(emissionPdf);
         L.c.vc = edir.z * rcp_w(emissionPdf);
         L.c.vcm = div_w(areaPdf, emissionPdf);
@@ -791,17 +728,10 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
         f3 dir = L.h.p - e_p;
         const float d2 = dot(dir, dir);
         dir = dir * rsqrt_w(d2);
-#if BDPT_CONN_EARLY_COS >= 2
         const float cosAtLight = dot(e_n, dir);
         const float cosAtEye = dot(-dir, L.h.n);  // = the frame's z component (to_local)
         if (cosAtLight <= 0.f || cosAtEye <= 0.f) break;
         const f3 wi = local_for(b, L.h.n, -dir);
-#else
-        const f3 wi = local_at(L.h.n, -dir);
-        const float cosAtLight = dot(e_n, dir);
-        const float cosAtEye = wi.z;
-        if (cosAtLight <= 0.f || cosAtEye <= 0.f) break;
-#endif
         const float pdf_w = div_w((e_pdf * e_pos_pdf) * d2, cosAtLight);
         const EvalPdfs ep = bsdf_eval_pdfs(b, wi, L.h.wo);
         const f3 Li = ((ep.f * rcp_w(pdf_w)) * L.c.tp) * ld3(e.radiance);
@@ -836,7 +766,6 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
             f3 dir = L.h.p - V.p;
             const float invD2 = rcp_w(dot(dir, dir));
             dir = dir * sqrt_w(invD2);
-#if BDPT_CONN_EARLY_COS >= 1
             // the frames' z components are dot(v, n) (to_local), so the
             // rejection test runs before the frames are built
             const float cosL = dot(dir, V.n), cosE = dot(-dir, L.h.n);
@@ -847,16 +776,6 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
             BDPT_VERTEX_BSDF(bl, sc, V.mat, V.tkd, V.tks);
             const f3 wiL = local_for(bl, V.n, dir);  // Frame(n) is a pure function of n
             const f3 wiE = local_for(be, L.h.n, -dir);
-#else
-            const f3 wiL = local_at(V.n, dir);  // Frame(n) is a pure function of n
-            const f3 wiE = local_at(L.h.n, -dir);
-            const float cosL = wiL.z, cosE = wiE.z;
-            if (cosL <= 0.f || cosE <= 0.f) {
-                L.c.ci++;
-                continue;
-            }
-            BDPT_VERTEX_BSDF(bl, sc, V.mat, V.tkd, V.tks);
-#endif
             const EvalPdfs eL = bsdf_eval_pdfs(bl, wiL, V.wo), eE = bsdf_eval_pdfs(be, wiE, L.h.wo);
             f3 Li = eL.f * eE.f;
             Li = Li * ((V.tp * L.c.tp) * invD2);
@@ -908,9 +827,6 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
 #undef BDPT_BODY_CONTINUE
 #undef BDPT_BODY_LIGHT_NEXT
 
-#ifndef BDPT_SCAN_BITS
-#define BDPT_SCAN_BITS 1  // conn_batch's prefix sum by ballots per bit of the counts (0: six __shfl_up steps)
-#endif
 #if BDPT_HELP && !BDPT_SAMPLER_STATE
 // connectVertices of every owner lane that reached A_CONN in this shading step
 // (bdpt.h:434-483, all its remaining light vertices), flattened over the wave:
@@ -928,7 +844,6 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
     const uint64_t om = __ballot(k > 0);
     if (!om) return;
     const int me = static_cast<int>(opaque_tid() & 63);
-#if BDPT_SCAN_BITS
     // exclusive prefix sum of k over the wave, one bit of k at a time: lanes below
     // with the bit set (mbcnt of a ballot) times its weight — no LDS round trips
     int excl = 0, total = 0;
@@ -937,15 +852,6 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
         excl += lanes_below(m) << b;
         total += popc64(m) << b;
     }
-#else
-    int incl = k;  // inclusive prefix sum of k over the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off);
-        if (me >= off) incl += t;
-    }
-    const int total = lane_val(incl, 63), excl = incl - k;
-#endif
     {
         const TaskCtl ctl = task_ctl(L.c);
         if (static_cast<uint32_t>(total) > fr.task_cap - (*ctl.tail - *ctl.head)) return;
@@ -993,9 +899,6 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
         const float eyeWeight = eyePathRev_a * (oc.vcm + eyePrevRev * oc.vc);
         const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
         const Ray sr = shadow_ray(hp, V.p);
-#if BDPT_GRAZE_IN_DIST
-#error "conn_batch: BDPT_GRAZE_IN_DIST keeps the threshold in Hit::dist"
-#endif
         task_push(L.c, fr, hp, V.p, graze_exempt(sr.d, hn, hshape), (Li * mis) * fr.inv_spp, oc.pixel, false, cnt);
     }
     if (k > 0) L.c.ci = L.c.nl;
@@ -1041,20 +944,12 @@ __device__ __forceinline__ bool is_shadow_state(uint32_t st) { return st == ST_S
 // first light-subpath ray, the emitter: A_START_LIGHT puts its normal and face
 // code in L.h) nearly parallel to its triangle's plane; camera queries keep it.
 __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d) {
-#if BDPT_GRAZE_IN_DIST
-    return fabsf(dot(d, L.h.n)) < L.h.dist;
-#else
     return graze_exempt(d, L.h.n, L.h.shape);
-#endif
 }
 __device__ __forceinline__ float cull_near_for(const Lane& L) {
     const uint32_t st = L.state;
     if (st == ST_PRIMARY || st == ST_SPLAT) return kCullNear;
-#if BDPT_GRAZE_IN_DIST
-    return fabsf(dot(L.ray.d, L.h.n)) < L.h.dist ? kNoCullNear : kCullNear;
-#else
     return graze_exempt(L.ray.d, L.h.n, L.h.shape) ? kNoCullNear : kCullNear;
-#endif
 }
 
 // Applies the result of the lane's pending query (closest hit: leaf-order

@@ -69,10 +69,7 @@ struct CameraConstants {
 // five plus v0 at slot 5, so shading a closest hit reads one cache line instead
 // of the 80-byte record (often split over two lines) and v0 from the tri array;
 // 5 = the host layout uploaded as is.
-#ifndef BDPT_SHADE_WIDE
-#define BDPT_SHADE_WIDE 1
-#endif
-constexpr int kShadeStride = BDPT_SHADE_WIDE ? 8 : 5;
+constexpr int kShadeStride = 8;
 constexpr int kShadeV0 = 5;  // slot of (v0, 0) in a wide record
 // Scenes with bitmap textures: slots 6, 7 of a wide record hold the corners' texture
 // coordinates (s0 t0 s1 t1) (s2 t2 0 0), zero otherwise (as before).

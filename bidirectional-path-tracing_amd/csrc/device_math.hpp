@@ -79,32 +79,15 @@ __device__ __forceinline__ float rcp_nr(float x) {
     const float r = __builtin_amdgcn_rcpf(x);
     return __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
 }
-#ifndef BDPT_FAST_DIV
-#define BDPT_FAST_DIV 0  // 1: rcp_cr / div_cr take the short sequences (measured: no gain in the shading code)
-#endif
 __device__ __forceinline__ float rcp_cr(float x) {
-    if (!BDPT_FAST_DIV) return 1.0f / x;
-    const float ax = __builtin_fabsf(x);
-    if (__builtin_expect(ax >= 0x1p-126f && ax < 0x1p126f, 1)) return rcp_nr(x);
     return 1.0f / x;
 }
 // The triangle test's 1 / det: |det| >= 1e-8 is known, so only the upper bound is checked.
-#ifndef BDPT_FAST_TRI_RCP
-#define BDPT_FAST_TRI_RCP 1
-#endif
 __device__ __forceinline__ float rcp_det(float det) {
-    if (!BDPT_FAST_TRI_RCP) return 1.0f / det;
     if (__builtin_expect(__builtin_fabsf(det) < 0x1p126f, 1)) return rcp_nr(det);
     return 1.0f / det;
 }
 __device__ __forceinline__ float div_cr(float a, float b) {
-    if (!BDPT_FAST_DIV) return a / b;
-    const float aa = __builtin_fabsf(a), ab = __builtin_fabsf(b);
-    if (__builtin_expect(aa >= 0x1p-60f && aa <= 0x1p60f && ab >= 0x1p-40f && ab <= 0x1p40f, 1)) {
-        const float r = rcp_nr(b);
-        const float q = a * r;
-        return __builtin_fmaf(__builtin_fmaf(-b, q, a), r, q);
-    }
     return a / b;
 }
 __device__ __forceinline__ f3 normalize(f3 v) { return v * rcp_cr(sqrt_cr(dot(v, v))); }

@@ -732,7 +732,7 @@ __global__ __launch_bounds__(256, PT_WAVES_PER_EU) void pt_frame_kernel(const Pt
             const uint64_t lv = __ballot(tracing && at_leaf);
             const bool do_leaf = popc64(lv) * 4 >= popc64(tr & ~lv) * PT_TRAV_SPLIT;
             bool fin = tracing && at_leaf == do_leaf && trav_step<COUNT, SLACK>(tsc, L.ray, ri, false, ts, stk, cnt);
-            // PT_WALK_UNROLL more node steps for lanes now at an interior node (bdpt_frame_kernel's BDPT_UNROLL_ANY)
+            // PT_WALK_UNROLL more node steps for lanes now at an interior node (also after a leaf iteration, as in bdpt_frame_kernel)
 #pragma unroll
             for (int k = 0; k < PT_WALK_UNROLL; k++)
                 if (tracing && !fin && !(ts.link & kLeafBit)) fin = trav_step<COUNT, SLACK>(tsc, L.ray, ri, false, ts, stk, cnt);

@@ -5,6 +5,5 @@
 #define BDPT_SAMPLER_STATE 1
 #define BDPT_RR 2  // as sample_state.hip (textured calls always pass rr_mode 0)
 #define BDPT_TEXTURED 1
-#define bdpt_sample_kernel bdpt_sample_kernel_tex
-#define launch_sample launch_sample_tex
+#define BDPT_VARIANT _tex
 #include "bdpt_kernels.hip"

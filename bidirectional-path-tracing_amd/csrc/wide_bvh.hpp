@@ -75,8 +75,8 @@ struct TriWideBvh {
 bool build_wide_bvh_tris(const std::vector<FlatNode>& flat, const std::vector<float4_t>& tri,
                          const std::vector<float4_t>& shade, float pad_rel, TriWideBvh& out, std::string& err);
 
-// Compressed 64-byte node records (4 float4) of the same tree, for the
-// BDPT_QNODES=1 kernels: each child box as 8-bit offsets on a per-node,
+// Compressed 64-byte node records (4 float4) of the same tree (uploaded as
+// DevScene::qnodes; no kernel reads them): each child box as 8-bit offsets on a per-node,
 // per-axis grid of 2^e steps from the node's box minimum, rounded outward, so
 // the decoded box contains the exact one (the difference is computed in
 // double; its rounding, ~2^-53 of a coordinate, is far inside kTriBoxPad).

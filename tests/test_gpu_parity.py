@@ -106,7 +106,7 @@ def test_gpu_far_camera_takes_the_slack_test_and_matches_oracle(name, dist):
 
 
 # coordinates ~250 diagonals from 0: the slack-free interior test (by one fma per
-# plane in the BDPT_SLAB_FMA builds); ~350: past kFmaCoordDiags, the slack test (bdpt_capi.cpp)
+# plane, slab_fma); ~350: past kFmaCoordDiags, the slack test (bdpt_capi.cpp)
 # (HardLight's 0.08-unit light keeps its area only up to ~100 diagonals: float
 # coordinates near 800 flatten its faces, and the loader then finds no emitter)
 @pytest.mark.parametrize("name,diags", [("caustic", 250.0), ("caustic", 350.0), ("hardlight", 100.0)])
