@@ -278,6 +278,8 @@ def lib():
         L.bdpt_bsdf_eval.argtypes = [vp, i64, vp, vp, vp, vp]
         L.bdpt_bsdf_pdf.argtypes = [vp, i64, vp, vp, vp, vp]
         L.bdpt_bsdf_sample.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+        L.bdpt_bsdf_eval_pdfs.argtypes = [vp, i32, i64, vp, vp, vp, vp]
+        L.bdpt_bsdf_local_for.argtypes = [vp, i32, i64, vp, vp, vp, vp]
         L.bdpt_bsdf_type.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(i32)]
         L.bdpt_intersect.argtypes = [vp, i64, vp, i32, vp]
         L.bdpt_splat_to_image_plane.argtypes = [vp, ctypes.POINTER(_FrameParams), i64, vp, vp]
@@ -819,6 +821,31 @@ class BDPTIntegrator:
                                       wi.ctypes.data, pdf.ctypes.data))
         return f, wi, pdf
 
+    def bsdf_eval_pdfs(self, mat, wo, wi, build: str = "exact"):
+        """What a connection evaluates at one end (bsdf_eval_pdfs of the frame kernels): (f * cos
+        (n, 3), pdf(wi, wo) (n,), pdf(wo, wi) (n,)) on local directions. build: "exact" (IEEE
+        weights), "fast" (the default frame kernels' arithmetic) or "ng" (the build without
+        glossy lobes; refused for a scene with a Mixture / Phong or null BSDF)."""
+        m, o, i = _ai32(mat), _af32(wo, 3), _af32(wi, 3)
+        if not (m.size == o.shape[0] == i.shape[0]):
+            raise ValueError("mat, wo and wi differ in length")
+        out = np.zeros((m.size, 5), np.float32)
+        _check(lib().bdpt_bsdf_eval_pdfs(self._h, KAT_BUILDS[build], m.size, m.ctypes.data, o.ctypes.data,
+                                         i.ctypes.data, out.ctypes.data))
+        return out[:, :3].copy(), out[:, 3].copy(), out[:, 4].copy()
+
+    def bsdf_local_for(self, mat, n, v, build: str = "exact") -> np.ndarray:
+        """The world directions v (n, 3) in the shading frames of the unit normals n (n, 3) as a
+        connection computes them for materials mat (local_for of the frame kernels): (n, 3);
+        x = y = 0 for a diffuse material."""
+        m, nn, vv = _ai32(mat), _af32(n, 3), _af32(v, 3)
+        if not (m.size == nn.shape[0] == vv.shape[0]):
+            raise ValueError("mat, n and v differ in length")
+        out = np.zeros((m.size, 3), np.float32)
+        _check(lib().bdpt_bsdf_local_for(self._h, KAT_BUILDS[build], m.size, m.ctypes.data, nn.ctypes.data,
+                                         vv.ctypes.data, out.ctypes.data))
+        return out
+
     def intersect(self, rays, occlusion: bool = False, origin_normals=None, origin_tris=None) -> np.ndarray:
         """AcceleratorBVH::intersect (accel.h:125-172) or the occlusion query of
         visibilityQuery (bvh.h:259-352) on rays (n, 8): a structured bdpt_hit array.
@@ -1151,12 +1178,21 @@ class MultiDeviceRenderer:
                     capped_samples=s.capped_samples, schedule_errors=s.schedule_errors)
 
 
+KAT_BUILDS = {"exact": 0, "fast": 1, "ng": 2}  # BDPT_KAT_*
+MATH_FNS = {"sinf": 0, "cosf": 1, "powf": 2, "sincos_s": 3, "sincos_c": 4,  # BDPT_MATH_*
+            "pow_w": 5, "rcp_w": 6, "div_w": 7, "sqrt_w": 8, "rsqrt_w": 9}
+
+
 def debug_math(fn: str, x: np.ndarray, y: np.ndarray | None = None, device: int = 0) -> np.ndarray:
     """The device sinf / cosf / powf (glibc restatements) on float32 inputs:
-    fn in {"sinf", "cosf", "powf", "sincos_s", "sincos_c"}."""
-    code = {"sinf": 0, "cosf": 1, "powf": 2, "sincos_s": 3, "sincos_c": 4}[fn]
+    fn in {"sinf", "cosf", "powf", "sincos_s", "sincos_c"}; and the fast weight
+    arithmetic of the default frame kernels: "pow_w" (x, y), "rcp_w", "div_w" (x / y),
+    "sqrt_w", "rsqrt_w"."""
+    code = MATH_FNS[fn]
     x = np.ascontiguousarray(x, np.float32)
     yy = None if y is None else np.ascontiguousarray(y, np.float32)
+    if fn in ("powf", "pow_w", "div_w") and (yy is None or yy.size != x.size):
+        raise ValueError(f"debug_math({fn!r}) needs y of x's size")
     out = np.empty_like(x)
     _check(lib().bdpt_debug_math(device, code, x.ctypes.data, None if yy is None else yy.ctypes.data,
                                  out.ctypes.data, x.size))

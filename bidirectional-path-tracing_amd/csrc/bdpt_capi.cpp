@@ -29,9 +29,15 @@ hipError_t launch_sample(const dev::DevScene& sc, const dev::DevFrame& fr, float
 hipError_t launch_pt_sample(const dev::DevScene& sc, const dev::DevFrame& fr, const int32_t settings[8],
                             float4* levels, uint32_t* ring, uint2* gstack, const dev::Ray& ray, float* out,
                             unsigned long long* counters, hipStream_t stream, void* dparams);
-// kat_kernels.hip: per-function entry points
+// kat_kernels.hip: per-function entry points; the BSDF kernel also as the fast-weight frame
+// kernels compile its functions (kat_kernels_fw.hip) and as the build without glossy lobes
+// does (kat_kernels_ng.hip)
 hipError_t launch_bsdf_kat(const dev::DevScene& sc, int mode, int64_t n, const int32_t* mat, const float* wo,
                            const float* x, float* out, hipStream_t st);
+hipError_t launch_bsdf_kat_fw(const dev::DevScene& sc, int mode, int64_t n, const int32_t* mat, const float* wo,
+                              const float* x, float* out, hipStream_t st);
+hipError_t launch_bsdf_kat_ng(const dev::DevScene& sc, int mode, int64_t n, const int32_t* mat, const float* wo,
+                              const float* x, float* out, hipStream_t st);
 hipError_t launch_fresnel_kat(int64_t n, const float* in, float* out, hipStream_t st);
 hipError_t launch_triangle_kat(int64_t n, const float* rays, const float* verts, float* out, hipStream_t st);
 hipError_t launch_intersect_kat(const dev::DevScene& sc, int64_t n, int occlusion, const float* rays, const float* nrm,
@@ -46,6 +52,8 @@ hipError_t launch_pt(const dev::DevScene& sc, const dev::DevFrame& fr, const int
                      float4* levels, uint32_t* ring, uint2* gstack, uint32_t nslots, unsigned long long* work,
                      unsigned long long* counters, int grid, hipStream_t stream, void* dparams);
 hipError_t launch_math_check(int32_t fn, const float* x, const float* y, float* out, int64_t n, hipStream_t st);
+// math_check_fw.hip: the same with BDPT_FAST_WEIGHTS 1 (the weight operations' hardware forms)
+hipError_t launch_math_check_fw(int32_t fn, const float* x, const float* y, float* out, int64_t n, hipStream_t st);
 // aov_kernels.hip: first-hit feature buffers and the a-trous filter
 hipError_t launch_aov(const dev::DevScene& sc, const dev::DevFrame& fr, const void* mats, float* aov, uint2* gstack,
                       uint32_t nslots, hipStream_t st);
@@ -886,6 +894,9 @@ static uint32_t node_slack_needed(const bdpt_ctx* c, const float* const* origins
     return 0u;
 }
 
+// A material table the BDPT_GLOSSY 0 code serves: diffuse, mirror and glass records only.
+static bool ng_table(const bdpt_ctx* c) { return !c->has_glossy && !c->has_null; }
+
 // The frame-kernel build of a render that textured_frame_check and render_bdpt's own
 // checks have accepted. The order of the decisions matters (a textured scene with
 // rr_depth 2 runs the textured build, not the short-subpath one). Read per render:
@@ -908,7 +919,7 @@ static const FrameBuild& pick_frame_build(const bdpt_ctx* c, const bdpt_frame_pa
     // Mixture / Phong lobes (bdpt_kernels_ng.hip: a vertex that is not delta is diffuse
     // there, so a null BSDF keeps the full build too)
     const char* ne = std::getenv("BDPT_NG_BUILD");
-    if (!c->has_glossy && !c->has_null && !(ne && *ne == '0')) return frame_build_ng;
+    if (ng_table(c) && !(ne && *ne == '0')) return frame_build_ng;
     return frame_build;
 }
 
@@ -1338,7 +1349,9 @@ int bdpt_render_direct_sample(bdpt_ctx* c, const bdpt_frame_params* p, const bdp
 }
 
 int bdpt_debug_math(int32_t device, int32_t fn, const float* x, const float* y, float* out, int64_t n) {
-    if (!x || !out || n < 0 || (fn == 2 && !y) || fn < 0 || fn > 4) return fail(BDPT_ERR_INVALID, "bad argument");
+    const bool two = fn == BDPT_MATH_POWF || fn == BDPT_MATH_POW_W || fn == BDPT_MATH_DIV_W;
+    if (!x || !out || n < 0 || (two && !y) || fn < 0 || fn > BDPT_MATH_RSQRT_W)
+        return fail(BDPT_ERR_INVALID, "bad argument");
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(BDPT_ERR_NO_DEVICE, "no HIP device");
     if (device < 0 || device >= count) return fail(BDPT_ERR_INVALID, "bad device");
@@ -1351,7 +1364,9 @@ int bdpt_debug_math(int32_t device, int32_t fn, const float* x, const float* y, 
     if (e == hipSuccess) e = hipMalloc(&dout, bytes);
     if (e == hipSuccess) e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dy, y ? y : x, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_math_check(fn, dx, dy, dout, n, nullptr);
+    if (e == hipSuccess)
+        e = fn >= BDPT_MATH_POW_W ? launch_math_check_fw(fn, dx, dy, dout, n, nullptr)
+                                  : launch_math_check(fn, dx, dy, dout, n, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
     for (float* p : {dx, dy, dout})
         if (p) (void)hipFree(p);
@@ -1626,14 +1641,20 @@ static int kat_in(bdpt_ctx* c, KatBuffers& kb, const void* src, size_t bytes, vo
     return BDPT_OK;
 }
 
+// build: BDPT_KAT_EXACT / _FAST / _NG, the compilation of the BSDF kernel to run
 static int bsdf_kat(bdpt_ctx* c, int mode, int64_t n, const int32_t* mat, const float* wo, const float* x,
-                    float* out, int out_per) {
+                    float* out, int out_per, int build = BDPT_KAT_EXACT) {
     if (!c || n < 0 || (n > 0 && (!mat || !wo || !x || !out))) return fail(BDPT_ERR_INVALID, "bad argument");
+    if (build < BDPT_KAT_EXACT || build > BDPT_KAT_NG) return fail(BDPT_ERR_INVALID, "bad build");
+    if (build == BDPT_KAT_NG && !ng_table(c))
+        return fail(BDPT_ERR_UNSUPPORTED, "the build without glossy lobes serves material tables of diffuse, mirror "
+                                          "and glass records only; this scene has a Mixture / Phong or null BSDF");
     for (int64_t i = 0; i < n; i++)
         if (mat[i] < 0 || mat[i] >= c->sc.nbsdf) return fail(BDPT_ERR_INVALID, "material index out of range");
     for (int64_t i = 0; c->textured && i < n; i++)
         if (c->mat_textured[mat[i]])
-            return fail(BDPT_ERR_UNSUPPORTED, "bdpt_bsdf_eval / pdf / sample of material " + std::to_string(mat[i]) +
+            return fail(BDPT_ERR_UNSUPPORTED, "bdpt_bsdf_eval / pdf / sample / eval_pdfs / local_for of material " +
+                                                  std::to_string(mat[i]) +
                                                   ": it reads a bitmap texture and these calls carry no hit (texture + "
                                                   "bdpt_bsdf_*)");
     if (n == 0) return BDPT_OK;
@@ -1646,8 +1667,10 @@ static int bsdf_kat(bdpt_ctx* c, int mode, int64_t n, const int32_t* mat, const 
     if ((rc = kat_in(c, kb, mat, 4 * N, &dm)) || (rc = kat_in(c, kb, wo, 12 * N, &dwo)) ||
         (rc = kat_in(c, kb, x, (mode == 2 ? 8 : 12) * N, &dx)) || (rc = kat_in(c, kb, nullptr, 4 * out_per * N, &dout)))
         return rc;
-    HIP_TRY(launch_bsdf_kat(c->sc, mode, n, static_cast<const int32_t*>(dm), static_cast<const float*>(dwo),
-                            static_cast<const float*>(dx), static_cast<float*>(dout), c->stream));
+    const auto launch = build == BDPT_KAT_FAST ? launch_bsdf_kat_fw : build == BDPT_KAT_NG ? launch_bsdf_kat_ng
+                                                                                            : launch_bsdf_kat;
+    HIP_TRY(launch(c->sc, mode, n, static_cast<const int32_t*>(dm), static_cast<const float*>(dwo),
+                   static_cast<const float*>(dx), static_cast<float*>(dout), c->stream));
     HIP_TRY(hipMemcpyAsync(out, dout, 4 * out_per * N, hipMemcpyDeviceToHost, c->stream));
     if ((rc = end_use(c, c->stream))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1675,6 +1698,16 @@ int bdpt_bsdf_sample(bdpt_ctx* c, int64_t n, const int32_t* mat, const float* wo
         pdf[i] = r[6];
     }
     return BDPT_OK;
+}
+
+int bdpt_bsdf_eval_pdfs(bdpt_ctx* c, int32_t build, int64_t n, const int32_t* mat, const float* wo, const float* wi,
+                        float* out) {
+    return bsdf_kat(c, 3, n, mat, wo, wi, out, 5, build);
+}
+
+int bdpt_bsdf_local_for(bdpt_ctx* c, int32_t build, int64_t n, const int32_t* mat, const float* nrm, const float* v,
+                        float* out) {
+    return bsdf_kat(c, 4, n, mat, nrm, v, out, 3, build);
 }
 
 int bdpt_bsdf_type(const bdpt_scene* s, int32_t mat, uint32_t* type, int32_t* kind) {

@@ -107,7 +107,14 @@ __device__ __forceinline__ f3 normalize(f3 v) { return v * rcp_cr(sqrt_cr(dot(v,
 #define BDPT_FAST_WEIGHTS 0
 #endif
 __device__ __forceinline__ float rcp_w(float x) { return BDPT_FAST_WEIGHTS ? __builtin_amdgcn_rcpf(x) : rcp_cr(x); }
-__device__ __forceinline__ float div_w(float a, float b) { return BDPT_FAST_WEIGHTS ? a * __builtin_amdgcn_rcpf(b) : div_cr(a, b); }
+// a * rcp(b) alone is NaN where a / b is not: 0 * inf for a zero a over a denormal b (whose
+// reciprocal overflows) and inf * 0 for an infinite a over |b| >= 2^126 (whose reciprocal, a
+// denormal, is flushed). v_div_fixup_f32 (quotient, denominator, numerator) returns IEEE's
+// signed 0 / inf / NaN when an operand is 0, inf or NaN and the quotient's own bits otherwise,
+// so every other result is that of the bare product (tests/test_gpu_kat_connection.py).
+__device__ __forceinline__ float div_w(float a, float b) {
+    return BDPT_FAST_WEIGHTS ? __builtin_amdgcn_div_fixupf(a * __builtin_amdgcn_rcpf(b), b, a) : div_cr(a, b);
+}
 __device__ __forceinline__ float sqrt_w(float x) { return BDPT_FAST_WEIGHTS ? __builtin_amdgcn_sqrtf(x) : sqrt_cr(x); }
 __device__ __forceinline__ float rsqrt_w(float x) { return BDPT_FAST_WEIGHTS ? __builtin_amdgcn_rsqf(x) : rcp_cr(sqrt_cr(x)); }
 __device__ __forceinline__ bool is_zero(f3 v) { return v.x == 0.f && v.y == 0.f && v.z == 0.f; }

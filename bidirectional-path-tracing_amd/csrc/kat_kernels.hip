@@ -4,10 +4,32 @@
 // GlassBSDF::FresnelDielectric (glass.h:40-53), rayTriangleIntersect
 // (core.h:379-400), AcceleratorBVH::intersect and the occlusion query
 // (accel.h:125-172, bvh.h:259-352) and BDPTIntegrator::splatToImagePlane
-// (bdpt.h:485-496). Each kernel runs exactly the device function the frame
-// kernels call, one element per lane, so the parity tests can pin every piece
+// (bdpt.h:485-496), one element per lane, so the parity tests can pin every piece
 // of the path against the reference's own functions.
+//
+// The BSDF kernel is compiled three times, because the frame kernels compile its
+// device functions three ways (bdpt_device.hpp, device_math.hpp):
+//   kat_kernels.hip     IEEE weights, BDPT_GLOSSY 1: the Russian-roulette and single-
+//                       sample builds' arithmetic (bit-exact to the reference)
+//   kat_kernels_fw.hip  BDPT_FAST_WEIGHTS 1: the default frame kernels' (pow_w on
+//                       v_log_f32 / v_exp_f32, 1-ulp rcp / sqrt / rsq)
+//   kat_kernels_ng.hip  BDPT_GLOSSY 0 (and fast weights): bdpt_kernels_ng.hip's
+// Modes 0-2 run bsdf_eval / bsdf_pdf / bsdf_sample, which the walks call; modes 3 and
+// 4 run bsdf_eval_pdfs and local_for, which every connection calls (connectToLight,
+// connectToCamera, connectVertices, bdpt_path.hpp) and which are separate code: the
+// fused one-powf form and the diffuse frame skip. Those callers never pass a delta
+// vertex (is_delta, bdpt_path.hpp), so mode 3 answers a delta record with zeros
+// without a call, in every build; a BDPT_GLOSSY 0 build's bsdf_eval_pdfs does not read
+// the kind. The other kernels and the host launchers are compiled once, here.
 #include <hip/hip_runtime.h>
+
+#ifndef KAT_VARIANT
+#define KAT_VARIANT
+#define KAT_SHARED 1  // this unit also holds the kernels and launchers that are built once
+#endif
+#define KAT_PASTE(a, b) a##b
+#define KAT_NAME_(a, b) KAT_PASTE(a, b)
+#define KAT_NAME(x) KAT_NAME_(x, KAT_VARIANT)  // x with the build's suffix
 
 #include "bdpt_path.hpp"
 
@@ -16,11 +38,14 @@ namespace dev {
 
 constexpr int kKatBlock = 64;
 
-// mode 0: eval (f * cos) -> out[3]; 1: pdf -> out[1]; 2: sample -> out f[3], wi[3], pdf
-__global__ __launch_bounds__(kKatBlock) void bsdf_kat_kernel(DevScene sc, int mode, int64_t n,
-                                                            const int32_t* __restrict__ mat,
-                                                            const float* __restrict__ wo, const float* __restrict__ x,
-                                                            float* __restrict__ out) {
+// mode 0: eval (f * cos) -> out[3]; 1: pdf -> out[1]; 2: sample -> out f[3], wi[3], pdf;
+// 3: eval_pdfs, x = wi -> out f[3], fwd, rev; 4: local_for, wo = the unit normal,
+// x = the world direction -> out[3]
+__global__ __launch_bounds__(kKatBlock) void KAT_NAME(bsdf_kat_kernel)(DevScene sc, int mode, int64_t n,
+                                                                      const int32_t* __restrict__ mat,
+                                                                      const float* __restrict__ wo,
+                                                                      const float* __restrict__ x,
+                                                                      float* __restrict__ out) {
     scene_tables_to_lds(sc);
     const int64_t i = static_cast<int64_t>(blockIdx.x) * kKatBlock + threadIdx.x;
     if (i >= n) return;
@@ -33,6 +58,14 @@ __global__ __launch_bounds__(kKatBlock) void bsdf_kat_kernel(DevScene sc, int mo
         out[3 * i] = f.x, out[3 * i + 1] = f.y, out[3 * i + 2] = f.z;
     } else if (mode == 1) {
         out[i] = bsdf_pdf(b, mk(x[3 * i], x[3 * i + 1], x[3 * i + 2]), o);
+    } else if (mode == 3) {
+        EvalPdfs e{mk(0.f, 0.f, 0.f), 0.f, 0.f};
+        if (!is_delta(b)) e = bsdf_eval_pdfs(b, mk(x[3 * i], x[3 * i + 1], x[3 * i + 2]), o);
+        float* r = out + 5 * i;
+        r[0] = e.f.x, r[1] = e.f.y, r[2] = e.f.z, r[3] = e.fwd, r[4] = e.rev;
+    } else if (mode == 4) {
+        const f3 l = local_for(b, o, mk(x[3 * i], x[3 * i + 1], x[3 * i + 2]));
+        out[3 * i] = l.x, out[3 * i + 1] = l.y, out[3 * i + 2] = l.z;
     } else {
         f3 wi;
         float pdf;
@@ -42,6 +75,7 @@ __global__ __launch_bounds__(kKatBlock) void bsdf_kat_kernel(DevScene sc, int mo
     }
 }
 
+#ifdef KAT_SHARED
 // in: (eta_i, eta_t, cos_i, cos_t) per element
 __global__ __launch_bounds__(kKatBlock) void fresnel_kat_kernel(int64_t n, const float* __restrict__ in,
                                                                float* __restrict__ out) {
@@ -133,17 +167,21 @@ __global__ __launch_bounds__(kKatBlock) void splat_kat_kernel(DevFrame fr, int64
     xy[2 * i] = x, xy[2 * i + 1] = y;
 }
 
+#endif  // KAT_SHARED
+
 }  // namespace dev
 
 static dim3 kat_grid(int64_t n) { return dim3(static_cast<unsigned>((n + dev::kKatBlock - 1) / dev::kKatBlock)); }
 
-hipError_t launch_bsdf_kat(const dev::DevScene& sc, int mode, int64_t n, const int32_t* mat, const float* wo,
-                           const float* x, float* out, hipStream_t st) {
+// launch_bsdf_kat (exact), launch_bsdf_kat_fw, launch_bsdf_kat_ng
+hipError_t KAT_NAME(launch_bsdf_kat)(const dev::DevScene& sc, int mode, int64_t n, const int32_t* mat, const float* wo,
+                                     const float* x, float* out, hipStream_t st) {
     if (n > 0)
-        hipLaunchKernelGGL(dev::bsdf_kat_kernel, kat_grid(n), dim3(dev::kKatBlock), 4 * static_cast<size_t>(sc.lds_words),
-                           st, sc, mode, n, mat, wo, x, out);
+        hipLaunchKernelGGL(dev::KAT_NAME(bsdf_kat_kernel), kat_grid(n), dim3(dev::kKatBlock),
+                           4 * static_cast<size_t>(sc.lds_words), st, sc, mode, n, mat, wo, x, out);
     return hipGetLastError();
 }
+#ifdef KAT_SHARED
 hipError_t launch_fresnel_kat(int64_t n, const float* in, float* out, hipStream_t st) {
     if (n > 0) hipLaunchKernelGGL(dev::fresnel_kat_kernel, kat_grid(n), dim3(dev::kKatBlock), 0, st, n, in, out);
     return hipGetLastError();
@@ -165,5 +203,6 @@ hipError_t launch_splat_kat(const dev::DevFrame& fr, int64_t n, const float* p, 
     if (n > 0) hipLaunchKernelGGL(dev::splat_kat_kernel, kat_grid(n), dim3(dev::kKatBlock), 0, st, fr, n, p, xy);
     return hipGetLastError();
 }
+#endif  // KAT_SHARED
 
 }  // namespace bdpt

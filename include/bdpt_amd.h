@@ -560,6 +560,30 @@ int bdpt_bsdf_sample(bdpt_ctx* ctx, int64_t n, const int32_t* mat, const float* 
 /* BSDF::getType() (core.h:311) of a scene material, and this build's kind
  * (1 diffuse, 2 mirror, 3 glass, 4 mixture, 5 phong, 0 the null BSDF of illum 5). */
 int bdpt_bsdf_type(const bdpt_scene* scene, int32_t mat, uint32_t* type, int32_t* kind);
+/* What a BDPT connection runs at each of its ends (connectToLight, connectToCamera,
+ * connectVertices, bdpt.h:374-483), as the frame kernels compile it. `build` picks the
+ * compilation: BDPT_KAT_EXACT the IEEE weight arithmetic of the Russian-roulette and
+ * single-sample kernels (bit-exact to the reference's eval / pdf), BDPT_KAT_FAST the default
+ * frame kernels' (Phong powers as exp2(n log2 z) on the hardware instructions, 1-ulp
+ * reciprocal / square root: the outputs that hold a Phong power differ from the reference
+ * by a few ulp, all others are the same bits), BDPT_KAT_NG the build without glossy lobes,
+ * which returns BDPT_ERR_UNSUPPORTED unless the scene's material table holds diffuse,
+ * mirror and glass records only (the check that picks that frame kernel). Materials that
+ * read a bitmap texture are refused as by bdpt_bsdf_eval.
+ * bdpt_bsdf_eval_pdfs: out = n x 5 (f[3], fwd, rev) = eval(wi, wo), pdf(wi, wo) and the
+ * pdf of the swapped pair, pdf(wo, wi), from one evaluation. A delta material (mirror,
+ * glass) gives zeros: connections skip such vertices. */
+#define BDPT_KAT_EXACT 0
+#define BDPT_KAT_FAST 1
+#define BDPT_KAT_NG 2
+int bdpt_bsdf_eval_pdfs(bdpt_ctx* ctx, int32_t build, int64_t n, const int32_t* mat, const float* wo,
+                        const float* wi, float* out);
+/* The world direction v[k] in the shading frame of the unit normal nrm[k], as a connection
+ * computes it for evaluating material mat[k] (Frame(n).toLocal(v), core.h:155-157): out = n x 3.
+ * For a diffuse material (every material in BDPT_KAT_NG) x and y are left 0, since
+ * DiffuseBSDF reads z only. */
+int bdpt_bsdf_local_for(bdpt_ctx* ctx, int32_t build, int64_t n, const int32_t* mat, const float* nrm,
+                        const float* v, float* out);
 
 /* A closest hit as AcceleratorBVH::intersect fills SurfaceInteraction (accel.h:125-172). */
 typedef struct {
@@ -603,7 +627,20 @@ int bdpt_debug_triangle(int32_t device, int64_t n, const float* rays, const floa
 /* The device restatements of glibc's transcendental functions the path uses
  * (std::sinf / cosf / powf in src/core/math.h:125-242, mixture.h:70), element-wise
  * on device `device`: fn 0 sinf(x), 1 cosf(x), 2 powf(x, y), 3 / 4 the sin / cos
- * of the fused sincos the warps call. Host arrays of n floats; synchronous. */
+ * of the fused sincos the warps call. fn 5-9: the weight arithmetic of the default frame
+ * kernels (its BDPT_FAST_WEIGHTS forms on the hardware's 1-ulp instructions): 5 pow_w(x, y)
+ * = exp2(y log2 x) (1 for y == 0), 6 rcp_w(x), 7 div_w(x, y) = x * rcp(y), 8 sqrt_w(x),
+ * 9 rsqrt_w(x). y is read by fn 2, 5 and 7. Host arrays of n floats; synchronous. */
+#define BDPT_MATH_SINF 0
+#define BDPT_MATH_COSF 1
+#define BDPT_MATH_POWF 2
+#define BDPT_MATH_SINCOS_S 3
+#define BDPT_MATH_SINCOS_C 4
+#define BDPT_MATH_POW_W 5
+#define BDPT_MATH_RCP_W 6
+#define BDPT_MATH_DIV_W 7
+#define BDPT_MATH_SQRT_W 8
+#define BDPT_MATH_RSQRT_W 9
 int bdpt_debug_math(int32_t device, int32_t fn, const float* x, const float* y, float* out, int64_t n);
 
 /* ---- scene configuration and image output (host only, no GPU needed) ---- */

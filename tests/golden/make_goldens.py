@@ -50,6 +50,8 @@ FRAMEBUFFERS = {
     "G10_caustic_pt_64x64_spp16": ("caustic", 64, 64, 16, 8, 1, "pt"),
     "G11_hardlight_lt_64x64_spp16": ("hardlight", 64, 64, 16, 2, 1, "lt"),
     "G12_hardlight_pt_64x64_spp16": ("hardlight", 64, 64, 16, 2, 1, "pt"),
+    # a Phong lobe with Ns in the thousands (tests/test_gpu_kat_connection.py)
+    "G13_hardlight_phong_ns4000_32x32_spp4": ("hardlight_phong_ns4000", 32, 32, 4, 5, 1),
 }
 
 # The reference's Russian-roulette branch (NO_RR = 0): name: (scene, W, H, spp, rrDepth, row_stride)
