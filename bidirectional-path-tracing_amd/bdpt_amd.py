@@ -878,39 +878,30 @@ class BDPTIntegrator:
         """(bdpt_path_params, bdpt_direct_params) of bdpt_render_window: None, None = BDPT."""
         return None, None
 
-    def _window_host(self, p: _FrameParams, window: SampleWindow) -> None:
-        pp, dp = self._integrator_params()
-        w = window.c()
-        _check(lib().bdpt_render_window_host(self._h, ctypes.byref(p), ctypes.byref(w), pp and ctypes.byref(pp),
-                                             dp and ctypes.byref(dp), self.rgb.ctypes.data))
-
-    def _window_device(self, p: _FrameParams, window: SampleWindow, fb_ptr: int, stream_ptr: int) -> None:
-        pp, dp = self._integrator_params()
-        w = window.c()
-        _check(lib().bdpt_render_window(self._h, ctypes.byref(p), ctypes.byref(w), pp and ctypes.byref(pp),
-                                        dp and ctypes.byref(dp), ctypes.c_void_p(fb_ptr),
-                                        ctypes.c_void_p(stream_ptr)))
-
     def render_frame(self, row_offset: int = 0, row_stride: int = 1, flags: int = 0,
                      window: SampleWindow | None = None) -> np.ndarray:
         """All pixels x spp of the (sharded) image into self.rgb (host copy); with a
-        window only its samples of every pixel (bdpt_render_window_host)."""
+        window only its samples of every pixel. bdpt_render_window_host with this
+        integrator's settings: without a window exactly bdpt_render[_path|_direct]_host."""
         if self.rgb is None:
             self.init()
         p = self.params(row_offset, row_stride, flags)
-        if window is not None:
-            self._window_host(p, window)
-            return self.rgb
-        _check(lib().bdpt_render_host(self._h, ctypes.byref(p), self.rgb.ctypes.data))
+        pp, dp = self._integrator_params()
+        w = window and window.c()
+        _check(lib().bdpt_render_window_host(self._h, ctypes.byref(p), w and ctypes.byref(w), pp and ctypes.byref(pp),
+                                             dp and ctypes.byref(dp), self.rgb.ctypes.data))
         return self.rgb
 
     def render_device(self, fb_ptr: int, stream_ptr: int = 0, row_offset: int = 0, row_stride: int = 1,
                       flags: int = 0, window: SampleWindow | None = None) -> None:
-        """Asynchronous render into a device framebuffer (e.g. a torch tensor's data_ptr())."""
+        """Asynchronous render into a device framebuffer (e.g. a torch tensor's data_ptr()):
+        bdpt_render_window, as render_frame calls its host form."""
         p = self.params(row_offset, row_stride, flags)
-        if window is not None:
-            return self._window_device(p, window, fb_ptr, stream_ptr)
-        _check(lib().bdpt_render(self._h, ctypes.byref(p), ctypes.c_void_p(fb_ptr), ctypes.c_void_p(stream_ptr)))
+        pp, dp = self._integrator_params()
+        w = window and window.c()
+        _check(lib().bdpt_render_window(self._h, ctypes.byref(p), w and ctypes.byref(w), pp and ctypes.byref(pp),
+                                        dp and ctypes.byref(dp), ctypes.c_void_p(fb_ptr),
+                                        ctypes.c_void_p(stream_ptr)))
 
     def render_progressive(self, batch: int):
         """Generator: renders the contiguous sample windows [0, batch), [batch, 2 batch), ...
@@ -1050,27 +1041,12 @@ class PathTracerIntegrator(BDPTIntegrator):
     def _integrator_params(self):
         return self.path.c(), None
 
-    def render_frame(self, row_offset: int = 0, row_stride: int = 1, flags: int = 0,
-                     window: SampleWindow | None = None) -> np.ndarray:
-        if self.rgb is None:
-            self.init()
-        p, pp = self.params(row_offset, row_stride, flags), self.path.c()
-        if window is not None:
-            self._window_host(p, window)
-            return self.rgb
-        _check(lib().bdpt_render_path_host(self._h, ctypes.byref(p), ctypes.byref(pp), self.rgb.ctypes.data))
-        return self.rgb
-
     def render_device(self, fb_ptr: int, stream_ptr: int = 0, row_offset: int = 0, row_stride: int = 1,
                       flags: int = 0, window: SampleWindow | None = None) -> None:
         """Asynchronous; call check_levels() after the stream is synchronised: a
         sample that outgrew the 512-level recursion stack makes the frame differ
         from the reference's (render_frame checks this itself)."""
-        p, pp = self.params(row_offset, row_stride, flags), self.path.c()
-        if window is not None:
-            return self._window_device(p, window, fb_ptr, stream_ptr)
-        _check(lib().bdpt_render_path(self._h, ctypes.byref(p), ctypes.byref(pp), ctypes.c_void_p(fb_ptr),
-                                      ctypes.c_void_p(stream_ptr)))
+        super().render_device(fb_ptr, stream_ptr, row_offset, row_stride, flags, window)
 
     def check_levels(self) -> None:
         """Raises BdptError if a sample of the last render_device call outgrew the
@@ -1103,25 +1079,6 @@ class DirectIntegrator(BDPTIntegrator):
 
     def _integrator_params(self):
         return None, self.direct.c()
-
-    def render_frame(self, row_offset: int = 0, row_stride: int = 1, flags: int = 0,
-                     window: SampleWindow | None = None) -> np.ndarray:
-        if self.rgb is None:
-            self.init()
-        p, d = self.params(row_offset, row_stride, flags), self.direct.c()
-        if window is not None:
-            self._window_host(p, window)
-            return self.rgb
-        _check(lib().bdpt_render_direct_host(self._h, ctypes.byref(p), ctypes.byref(d), self.rgb.ctypes.data))
-        return self.rgb
-
-    def render_device(self, fb_ptr: int, stream_ptr: int = 0, row_offset: int = 0, row_stride: int = 1,
-                      flags: int = 0, window: SampleWindow | None = None) -> None:
-        p, d = self.params(row_offset, row_stride, flags), self.direct.c()
-        if window is not None:
-            return self._window_device(p, window, fb_ptr, stream_ptr)
-        _check(lib().bdpt_render_direct(self._h, ctypes.byref(p), ctypes.byref(d), ctypes.c_void_p(fb_ptr),
-                                        ctypes.c_void_p(stream_ptr)))
 
 
 class MultiDeviceRenderer:

@@ -97,6 +97,40 @@ const char* debug_knob(const char* name) {
         if (e_ != hipSuccess) return fail(BDPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// The owner of one device allocation; every device pointer of this file lives in one.
+// reserve() only grows and keeps no contents. Before it frees a live allocation it waits for
+// the device: work in flight on any stream may still read the old memory. That wait is the
+// one growth policy here; growth happens on a first call or a larger frame, never per frame
+// in steady state. A reserve that fails leaves the buffer empty.
+template <class T>
+class DevBuf {
+   public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr, o.bytes_ = 0; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= bytes_) return hipSuccess;
+        hipError_t e = p_ ? hipDeviceSynchronize() : hipSuccess;
+        release();
+        if (e == hipSuccess) e = hipMalloc(&p_, bytes);
+        if (e != hipSuccess) p_ = nullptr;
+        else bytes_ = bytes;
+        return e;
+    }
+    T* get() const { return static_cast<T*>(p_); }
+    operator T*() const { return get(); }
+
+   private:
+    void release() {
+        if (p_) (void)hipFree(p_);  // (teardown is best effort: nobody can act on an error here)
+        p_ = nullptr, bytes_ = 0;
+    }
+    void* p_ = nullptr;
+    size_t bytes_ = 0;  // capacity
+};
+
 constexpr int kCounterWords = BDPT_NUM_COUNTERS + 3 + 4;  // sums, the counting pass's 3 maxima (Counts::m), the task histogram (Counts::q)
 constexpr uint32_t kTaskCap = 256;  // shadow-ray tasks per wave ring (a power of two; DevFrame::tasks)
 constexpr int kLazyRrDepth = 28;  // lazy MT19937 covers 10 + 8 * 27 = 226 < 227 draws
@@ -170,16 +204,34 @@ struct bdpt_scene {
     DeviceLayout layout;
 };
 
-struct bdpt_ctx {
+// The context's stream and events. A base of bdpt_ctx, so that they are destroyed after its
+// members: the buffers are freed first.
+struct CtxStream {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // cross-stream ordering of the context's buffers: the last call's stream and
+    // an event recorded on it after that call's work
+    hipEvent_t last_use = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool used = false;
+    CtxStream() = default;
+    CtxStream(const CtxStream&) = delete;
+    CtxStream& operator=(const CtxStream&) = delete;
+    ~CtxStream() {  // best effort, as every teardown
+        for (hipEvent_t e : {last_use, ev0, ev1})
+            if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+struct bdpt_ctx : CtxStream {
     const char* last_kernel = "";  // the frame kernel build the last render launched (bdpt_last_kernel)
     int last_kernel_glossy = 1;    // 0: that build has no Mixture / Phong lobes (bdpt_last_kernel_glossy)
     int device = 0;
     int cus = 0;
     int grid = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // scene arrays
-    std::vector<void*> allocs;
+    std::vector<DevBuf<void>> allocs;
     dev::DevScene sc{};
     int max_depth = 0;
     bool tri_tree = false;              // traversal boxes padded (wide_bvh.hpp kTriBoxPad)
@@ -189,59 +241,50 @@ struct bdpt_ctx {
     int64_t ntri = 0;  // triangles (shade records)
     uint32_t lds_words_base = 0;  // dynamic LDS words without the emitter faces / CDFs
     // work buffers
-    unsigned long long* work = nullptr;      // work counter
-    unsigned long long* counters = nullptr;  // kCounters
-    float* lv = nullptr;
-    size_t lv_floats = 0;
-    uint2* gstack = nullptr;  // traversal-stack overflow beyond the LDS part
+    DevBuf<unsigned long long> work;      // work counter
+    DevBuf<unsigned long long> counters;  // kCounters
+    DevBuf<float> lv;
+    DevBuf<uint2> gstack;  // traversal-stack overflow beyond the LDS part
     uint32_t nslots = 0;
-    float* tmp_fb = nullptr;
-    size_t tmp_fb_floats = 0;
-    float* sample_out = nullptr;
-    void* dparams = nullptr;  // kernel parameter block (filled in stream order per launch)
+    DevBuf<float> tmp_fb;  // the host entries' staging buffer (stage_host)
+    DevBuf<float> sample_out;
+    DevBuf<void> dparams;  // kernel parameter block (filled in stream order per launch)
     // path tracer (pt_kernels.hip): level stacks, generator rings, parameter block
     int pt_grid = 0;
     uint32_t pt_nslots = 0;
-    float4* pt_levels = nullptr;
-    size_t pt_levels_f4 = 0;
-    uint32_t* pt_ring = nullptr;
-    uint32_t* mt_ring = nullptr;  // BDPT megakernel: MT19937 continuation past 227 draws (rrDepth > 28, RR)
-    uint32_t* park = nullptr;     // Russian roulette: continuation records + parked-slot list (DevFrame::park)
-    float4* tasks = nullptr;      // per-wave shadow-ray task rings (DevFrame::tasks; read by BDPT_HELP builds)
+    DevBuf<float4> pt_levels;
+    DevBuf<uint32_t> pt_ring;
+    DevBuf<uint32_t> mt_ring;  // BDPT megakernel: MT19937 continuation past 227 draws (rrDepth > 28, RR)
+    DevBuf<uint32_t> park;     // Russian roulette: continuation records + parked-slot list (DevFrame::park)
+    DevBuf<float4> tasks;      // per-wave shadow-ray task rings (DevFrame::tasks; read by BDPT_HELP builds)
     uint32_t task_cap = 0;        // their capacity (tasks per wave, a power of two)
     bool textured = false;        // the scene has bitmap textures: bdpt_render runs bdpt_kernels_tex.hip
     std::vector<uint8_t> mat_textured;  // per material: it reads a map (bdpt_bsdf_* carry no hit to look one up)
     bool has_glass = false;       // a GlassBSDF material: Russian-roulette renders run bdpt_kernels_rrc.hip
     bool has_glossy = false;      // a Mixture / Phong record in the device table (after device_bsdfs)
     bool has_null = false;        // a null BSDF (illum 5): not delta, not diffuse
-    int32_t* row_order = nullptr;  // bdpt_set_row_order (device copy; DevFrame::row_order)
-    int32_t row_order_n = 0;       // its row count (0: top to bottom)
-    unsigned long long* row_cost = nullptr;  // counting renders: queries per local row (DevFrame::row_cost)
-    int32_t row_cost_cap = 0, row_cost_n = 0;  // its capacity; the rows of the last counting render
+    DevBuf<int32_t> row_order;  // bdpt_set_row_order (device copy; DevFrame::row_order)
+    int32_t row_order_n = 0;    // its row count (0: top to bottom)
+    DevBuf<unsigned long long> row_cost;  // counting renders: queries per local row (DevFrame::row_cost)
+    int32_t row_cost_n = 0;               // the rows of the last counting render
     unsigned long long work_init = 0;  // BDPT_SAMPLE_RANGE's first sample (host copy for the async upload)
-    uint32_t* capped = nullptr;   // samples that met the Russian-roulette bounds, per call
-    unsigned long long* diag = nullptr;  // the BDPT frame kernel's timeline (dev::kDiag*)
+    DevBuf<uint32_t> capped;            // samples that met the Russian-roulette bounds, per call
+    DevBuf<unsigned long long> diag;    // the BDPT frame kernel's timeline (dev::kDiag*)
     bool diag_pending = false;    // the last call was a BDPT frame render (diag is its)
     int wall_khz = 100000;        // s_memrealtime rate
-    void* pt_dparams = nullptr;
+    DevBuf<void> pt_dparams;
     // single-sample calls: the caller's std::mt19937 state and the splat list
-    uint32_t* mt_state = nullptr;  // BDPT_MT19937_WORDS
-    float* splat_list = nullptr;   // header (count, capacity) + capacity (pixel, r, g, b) records
+    DevBuf<uint32_t> mt_state;  // BDPT_MT19937_WORDS
+    DevBuf<float> splat_list;   // header (count, capacity) + capacity (pixel, r, g, b) records
     int32_t splat_cap = 0;
-    // cross-stream ordering of the context's buffers: the last call's stream and
-    // an event recorded on it after that call's work
-    hipEvent_t last_use = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool used = false;
     // feature buffers (bdpt_render_aov): per material (Kd, albedo mode) (Ks, 0) of the records as
     // ingested, and for a scene without maps a table of "no map" records for shade_hit's lookup
-    void* aov_mats = nullptr;
-    void* aov_no_tex = nullptr;
+    DevBuf<void> aov_mats;
+    DevBuf<float4> aov_no_tex;
     // filter (bdpt_denoise): packed guides (2 float4 per pixel) and the ping-pong images (float4
-    // per pixel each), allocated at first use and grown when a larger frame comes
-    void* dn_guide = nullptr;
-    void* dn_img[2] = {nullptr, nullptr};
-    size_t dn_pixels = 0;
+    // per pixel each), reserved together at first use and when a larger frame comes
+    DevBuf<void> dn_guide, dn_img[2];
+    size_t dn_pixels = 0;  // the frame all three hold (0 after a failed reserve)
     // stats of the last render
     bool pending_timing = false;
     bdpt_stats stats{};
@@ -258,6 +301,62 @@ static int end_use(bdpt_ctx* c, hipStream_t st) {
     HIP_TRY(hipEventRecord(c->last_use, st));
     c->last_stream = st;
     c->used = true;
+    return BDPT_OK;
+}
+
+// The timed part of a call (frame renders, feature buffers, the filter): its counters start at
+// zero, ev0 / ev1 bracket its launches for kernel_ms, and its stats replace the last call's.
+// diag_pending: the call was a BDPT frame render, the timeline in c->diag is its.
+static int begin_timed(bdpt_ctx* c, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(unsigned long long) * kCounterWords, st));
+    HIP_TRY(hipMemsetAsync(c->capped, 0, sizeof(uint32_t), st));
+    HIP_TRY(hipEventRecord(c->ev0, st));
+    return BDPT_OK;
+}
+static int end_timed(bdpt_ctx* c, hipStream_t st, int64_t samples, int64_t launches, bool diag_pending = false) {
+    HIP_TRY(hipEventRecord(c->ev1, st));
+    if (int rc = end_use(c, st)) return rc;
+    c->pending_timing = true;
+    c->diag_pending = diag_pending;
+    c->stats = bdpt_stats{};
+    c->stats.samples = samples;
+    c->stats.launches = launches;
+    return BDPT_OK;
+}
+
+// A scene array: the context owns it (allocs, counted in scene_bytes), dst is the pointer the kernels read.
+template <class P>
+static int upload(bdpt_ctx* c, const void* src, size_t bytes, P& dst) {
+    if (bytes == 0) bytes = 16;
+    DevBuf<void> b;
+    HIP_TRY(b.reserve(bytes));
+    if (src) HIP_TRY(hipMemcpy(b, src, bytes, hipMemcpyHostToDevice));
+    dst = static_cast<P>(b.get());
+    c->allocs.push_back(std::move(b));
+    c->scene_bytes += static_cast<int64_t>(bytes);
+    return BDPT_OK;
+}
+
+// The host form of a frame entry: the caller's n floats staged in tmp_fb, the device entry
+// run on them on the context's stream (run(device pointer)), the result copied back and
+// waited for. What an entry checks before and after stays with the entry.
+template <class Run>
+static int stage_host(bdpt_ctx* c, float* host, size_t n, Run run) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->tmp_fb.reserve(n * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(c->tmp_fb, host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (int rc = run(c->tmp_fb.get())) return rc;
+    HIP_TRY(hipMemcpyAsync(host, c->tmp_fb, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+// Host arrays in, device run, host arrays out (the per-function entry points): a device array
+// of the call, filled from src on the context's stream (src null: an output, left as allocated).
+template <class T>
+static int kat_in(bdpt_ctx* c, DevBuf<T>& b, const T* src, size_t bytes) {
+    HIP_TRY(b.reserve(std::max<size_t>(bytes, 16)));
+    if (src && bytes) HIP_TRY(hipMemcpyAsync(b, src, bytes, hipMemcpyHostToDevice, c->stream));
     return BDPT_OK;
 }
 
@@ -535,34 +634,11 @@ int bdpt_device_count(int32_t* count) {
     return BDPT_OK;
 }
 
-static int upload(bdpt_ctx* c, const void* src, size_t bytes, void** dst) {
-    if (bytes == 0) bytes = 16;
-    HIP_TRY(hipMalloc(dst, bytes));
-    c->allocs.push_back(*dst);
-    if (src) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    c->scene_bytes += static_cast<int64_t>(bytes);
-    return BDPT_OK;
-}
-
 int bdpt_ctx_destroy(bdpt_ctx* c) {
     if (!c) return BDPT_OK;
     (void)hipSetDevice(c->device);
     // Teardown is best effort: errors here cannot be acted on by the caller.
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void* p : c->allocs) (void)hipFree(p);
-    for (void* p : {static_cast<void*>(c->work), static_cast<void*>(c->counters), static_cast<void*>(c->lv),
-                    static_cast<void*>(c->gstack), static_cast<void*>(c->tmp_fb), static_cast<void*>(c->sample_out), c->dparams,
-                    static_cast<void*>(c->pt_levels), static_cast<void*>(c->pt_ring), c->pt_dparams,
-                    static_cast<void*>(c->mt_ring), static_cast<void*>(c->mt_state), static_cast<void*>(c->capped),
-                    static_cast<void*>(c->diag),
-                    static_cast<void*>(c->splat_list), static_cast<void*>(c->park), static_cast<void*>(c->tasks),
-                    static_cast<void*>(c->row_order), static_cast<void*>(c->row_cost), c->aov_mats, c->aov_no_tex,
-                    c->dn_guide, c->dn_img[0], c->dn_img[1]})
-        if (p) (void)hipFree(p);
-    if (c->last_use) (void)hipEventDestroy(c->last_use);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return BDPT_OK;
 }
@@ -583,61 +659,47 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     HIP_TRY(hipEventCreate(&c->ev1));
     HIP_TRY(hipEventCreateWithFlags(&c->last_use, hipEventDisableTiming));
     const DeviceLayout& L = s->layout;
-    void* p;
     int rc;
-    if ((rc = upload(c.get(), L.tri.data(), L.tri.size() * 16, &p))) return rc;
-    c->sc.tri = static_cast<const float4*>(p);
+    if ((rc = upload(c.get(), L.tri.data(), L.tri.size() * 16, c->sc.tri))) return rc;
     if (s->host.shape_first.size() >= (size_t(1) << 24))
         return fail(BDPT_ERR_UNSUPPORTED, "more than 2^24 shapes (the shading record packs the shape id in 24 bits)");
     c->ntri = static_cast<int64_t>(L.shade.size() / 5);
     {  // the device shade records (bdpt_types.h kShadeStride): the host five + v0, one line each
         const std::vector<float4_t> dev_shade = device_shade(L);
-        if ((rc = upload(c.get(), dev_shade.data(), dev_shade.size() * 16, &p))) return rc;
+        if ((rc = upload(c.get(), dev_shade.data(), dev_shade.size() * 16, c->sc.shade))) return rc;
     }
-    c->sc.shade = static_cast<const float4*>(p);
-    if ((rc = upload(c.get(), L.nodes.data(), L.nodes.size() * 16, &p))) return rc;
-    c->sc.nodes = static_cast<const float4*>(p);
-    if ((rc = upload(c.get(), L.wnodes.data(), L.wnodes.size() * 16, &p))) return rc;
-    c->sc.wnodes = static_cast<const float4*>(p);
+    if ((rc = upload(c.get(), L.nodes.data(), L.nodes.size() * 16, c->sc.nodes))) return rc;
+    if ((rc = upload(c.get(), L.wnodes.data(), L.wnodes.size() * 16, c->sc.wnodes))) return rc;
     c->sc.wroot_link = L.wroot_link;
     c->sc.qnodes = nullptr;
     c->sc.q_ok = 0u;
     if (L.q_ok) {
-        if ((rc = upload(c.get(), L.qnodes.data(), L.qnodes.size() * 16, &p))) return rc;
-        c->sc.qnodes = static_cast<const float4*>(p);
+        if ((rc = upload(c.get(), L.qnodes.data(), L.qnodes.size() * 16, c->sc.qnodes))) return rc;
         c->sc.q_ok = 1u;
     }
-    if ((rc = upload(c.get(), L.wtri.data(), L.wtri.size() * 16, &p))) return rc;
-    c->sc.wtri = static_cast<const float4*>(p);
-    if ((rc = upload(c.get(), L.lbox.data(), L.lbox.size() * 16, &p))) return rc;
-    c->sc.lbox = static_cast<const float4*>(p);
+    if ((rc = upload(c.get(), L.wtri.data(), L.wtri.size() * 16, c->sc.wtri))) return rc;
+    if ((rc = upload(c.get(), L.lbox.data(), L.lbox.size() * 16, c->sc.lbox))) return rc;
     {
         const std::vector<BsdfRecord> dev_bsdfs = device_bsdfs(L.bsdfs, L.mat_tex);
-        if ((rc = upload(c.get(), dev_bsdfs.data(), dev_bsdfs.size() * sizeof(BsdfRecord), &p))) return rc;
+        if ((rc = upload(c.get(), dev_bsdfs.data(), dev_bsdfs.size() * sizeof(BsdfRecord), c->sc.bsdf))) return rc;
         for (const BsdfRecord& b : dev_bsdfs) {
             c->has_glass = c->has_glass || b.kind == BSDF_GLASS;
             c->has_glossy = c->has_glossy || b.kind == BSDF_MIXTURE || b.kind == BSDF_PHONG;
             c->has_null = c->has_null || b.kind == BSDF_NULL;
         }
     }
-    c->sc.bsdf = static_cast<const BsdfRecord*>(p);
-    if ((rc = upload(c.get(), L.emitters.data(), L.emitters.size() * sizeof(EmitterRecord), &p))) return rc;
-    c->sc.emit = static_cast<const EmitterRecord*>(p);
+    if ((rc = upload(c.get(), L.emitters.data(), L.emitters.size() * sizeof(EmitterRecord), c->sc.emit))) return rc;
     {
         const std::vector<float4_t> dev_etri = device_emit_tri(L);
-        if ((rc = upload(c.get(), dev_etri.data(), dev_etri.size() * 16, &p))) return rc;
+        if ((rc = upload(c.get(), dev_etri.data(), dev_etri.size() * 16, c->sc.emit_tri))) return rc;
     }
-    c->sc.emit_tri = static_cast<const float4*>(p);
-    if ((rc = upload(c.get(), L.emit_cdf.data(), L.emit_cdf.size() * 4, &p))) return rc;
-    c->sc.emit_cdf = static_cast<const float*>(p);
-    if ((rc = upload(c.get(), L.shape_emitter.data(), L.shape_emitter.size() * 4, &p))) return rc;
-    c->sc.shape_emitter = static_cast<const int32_t*>(p);
+    if ((rc = upload(c.get(), L.emit_cdf.data(), L.emit_cdf.size() * 4, c->sc.emit_cdf))) return rc;
+    if ((rc = upload(c.get(), L.shape_emitter.data(), L.shape_emitter.size() * 4, c->sc.shape_emitter))) return rc;
     c->sc.tex_tab = nullptr;
     if (L.textured()) {  // map records + texel pool; the texture coordinates ride in the shade records
         if (kShadeStride < kShadeSt + 2)
             return fail(BDPT_ERR_UNSUPPORTED, "bitmap textures need the wide shade records");
-        if ((rc = upload(c.get(), L.tex_tab.data(), L.tex_tab.size() * 16, &p))) return rc;
-        c->sc.tex_tab = static_cast<const float4*>(p);
+        if ((rc = upload(c.get(), L.tex_tab.data(), L.tex_tab.size() * 16, c->sc.tex_tab))) return rc;
         c->textured = true;
         for (size_t m = 0; m < L.bsdfs.size(); m++) c->mat_textured.push_back(L.mat_tex[2 * m] >= 0 || L.mat_tex[2 * m + 1] >= 0);
     }
@@ -653,10 +715,10 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
             mats[2 * m + 1] = float4_t{b.ks[0], b.ks[1], b.ks[2], 0.f};
         }
         std::memset(no_tex.data(), 0xff, no_tex.size() * sizeof(float4_t));  // first texel -1: no map
-        HIP_TRY(hipMalloc(&c->aov_mats, mats.size() * 16));
+        HIP_TRY(c->aov_mats.reserve(mats.size() * 16));
         HIP_TRY(hipMemcpy(c->aov_mats, mats.data(), mats.size() * 16, hipMemcpyHostToDevice));
         if (!L.textured()) {
-            HIP_TRY(hipMalloc(&c->aov_no_tex, no_tex.size() * 16));
+            HIP_TRY(c->aov_no_tex.reserve(no_tex.size() * 16));
             HIP_TRY(hipMemcpy(c->aov_no_tex, no_tex.data(), no_tex.size() * 16, hipMemcpyHostToDevice));
         }
     }
@@ -719,18 +781,18 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
         }
     }
     c->max_depth = s->host.max_depth;
-    HIP_TRY(hipMalloc(&c->work, sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&c->counters, sizeof(unsigned long long) * kCounterWords));
-    HIP_TRY(hipMalloc(&c->diag, sizeof(unsigned long long) * dev::kDiagWords));
+    HIP_TRY(c->work.reserve(sizeof(unsigned long long)));
+    HIP_TRY(c->counters.reserve(sizeof(unsigned long long) * kCounterWords));
+    HIP_TRY(c->diag.reserve(sizeof(unsigned long long) * dev::kDiagWords));
     {
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) == hipSuccess && khz > 0)
             c->wall_khz = khz;
     }
-    HIP_TRY(hipMalloc(&c->sample_out, 16 * sizeof(float)));
-    HIP_TRY(hipMalloc(&c->capped, sizeof(uint32_t)));
+    HIP_TRY(c->sample_out.reserve(16 * sizeof(float)));
+    HIP_TRY(c->capped.reserve(sizeof(uint32_t)));
     HIP_TRY(hipMemset(c->capped, 0, sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&c->dparams, frame_build.params_bytes));
+    HIP_TRY(c->dparams.reserve(frame_build.params_bytes));
     // Persistent grid: exactly the resident blocks (no co-residency is assumed:
     // the work queue has no inter-block waits, extra blocks would just queue).
     const size_t dyn = 4 * static_cast<size_t>(c->sc.lds_words);
@@ -750,7 +812,7 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     const int lds_entries = frame_build.lds_stack;
     c->sc.gdepth = static_cast<uint32_t>(std::max(1, depth - lds_entries));  // per slot (DevScene::gdepth)
     const size_t spill_mega = static_cast<size_t>(c->sc.gdepth) * c->nslots;
-    HIP_TRY(hipMalloc(&c->gstack, sizeof(uint2) * std::max<size_t>(1, spill_mega)));
+    HIP_TRY(c->gstack.reserve(sizeof(uint2) * std::max<size_t>(1, spill_mega)));
     // shadow-ray task rings: their capacity here, their memory in ensure_tasks
     c->task_cap = kTaskCap;
     if (const char* e = std::getenv("BDPT_TASK_CAP")) {  // (sweeps) a power of two in [64, 4096]
@@ -761,17 +823,29 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     return BDPT_OK;
 }
 
-static int check_params(const bdpt_frame_params* p) {
+// The frame shape, for every frame entry (BDPT, path, direct, feature buffers). Two parts:
+// each entry reports a bad size first and a bad shard of rows after its own checks (BDPT,
+// feature buffers) or before them (path, direct), as it always has.
+static int check_frame_size(const bdpt_frame_params* p) {
     if (!p) return fail(BDPT_ERR_INVALID, "null params");
     if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(BDPT_ERR_INVALID, "width/height/spp must be > 0");
     if (static_cast<int64_t>(p->width) * p->height >= (1ll << 31))
         return fail(BDPT_ERR_INVALID, "image too large (W*H must fit int32, as in the reference)");
+    return BDPT_OK;
+}
+static int check_row_shard(const bdpt_frame_params* p) {
+    if (p->row_stride < 1 || p->row_offset < 0) return fail(BDPT_ERR_INVALID, "bad row shard");
+    return BDPT_OK;
+}
+
+static int check_params(const bdpt_frame_params* p) {
+    if (int rc = check_frame_size(p)) return rc;
     if (p->rr_depth < 1 || p->rr_depth > kMaxRrDepth)
         return fail(BDPT_ERR_UNSUPPORTED, "rr_depth must be in [1, 1024]");
     if (p->flags & ~(BDPT_FLAG_COUNT | BDPT_FLAG_FULL_TRAVERSAL))
         return fail(BDPT_ERR_UNSUPPORTED, "unknown flag (bit 2, the round-1 wavefront schedule, was removed)");
     if (p->strategy < 0 || p->strategy > 2) return fail(BDPT_ERR_INVALID, "unknown strategy");
-    if (p->row_stride < 1 || p->row_offset < 0) return fail(BDPT_ERR_INVALID, "bad row shard");
+    if (int rc = check_row_shard(p)) return rc;
     if (p->russian_roulette != BDPT_RR_NONE && p->russian_roulette != BDPT_RR_LUMINANCE)
         return fail(BDPT_ERR_INVALID, "unknown russian_roulette mode");
     return BDPT_OK;
@@ -820,13 +894,7 @@ static dev::DevFrame make_frame(const bdpt_frame_params* p, const bdpt_sample_wi
 
 static int ensure_lv(bdpt_ctx* c, int lv_max, uint32_t nslots) {
     const int fields = (c->textured ? frame_build_tex : frame_build).light_vertex_fields;
-    const size_t need = static_cast<size_t>(std::max(lv_max, 1)) * fields * nslots;
-    if (need > c->lv_floats) {
-        if (c->lv) HIP_TRY(hipFree(c->lv));
-        c->lv = nullptr;
-        HIP_TRY(hipMalloc(&c->lv, need * sizeof(float)));
-        c->lv_floats = need;
-    }
+    HIP_TRY(c->lv.reserve(static_cast<size_t>(std::max(lv_max, 1)) * fields * nslots * sizeof(float)));
     return BDPT_OK;
 }
 
@@ -834,8 +902,7 @@ static int ensure_lv(bdpt_ctx* c, int lv_max, uint32_t nslots) {
 // on 256 CUs). Only the frame kernels without Russian roulette (BDPT_HELP builds) use them,
 // so the first render that launches one allocates them; the context's destruction frees them.
 static int ensure_tasks(bdpt_ctx* c) {
-    if (!c->tasks)
-        HIP_TRY(hipMalloc(&c->tasks, static_cast<size_t>(dev::kTaskBytes) * c->task_cap * (c->nslots / 64)));
+    HIP_TRY(c->tasks.reserve(static_cast<size_t>(dev::kTaskBytes) * c->task_cap * (c->nslots / 64)));
     return BDPT_OK;
 }
 
@@ -961,7 +1028,7 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
     dev::DevScene sc = c->sc;
     sc.node_slack = node_slack_needed(c, eye, 1);
     if (p->rr_depth > kLazyRrDepth || rr) {  // draws past 226: the lanes' MT19937 rings
-        if (!c->mt_ring) HIP_TRY(hipMalloc(&c->mt_ring, sizeof(uint32_t) * kMtRingSlotWords * static_cast<size_t>(c->nslots)));
+        HIP_TRY(c->mt_ring.reserve(sizeof(uint32_t) * kMtRingSlotWords * static_cast<size_t>(c->nslots)));
         sc.mt_ring = c->mt_ring;
         sc.mt_ring_stride = 1;  // slot-major blocks of kMtRingSlotWords words (DevScene::mt_ring)
     }
@@ -979,25 +1046,16 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
             HIP_TRY(hipMemcpyAsync(c->work, &c->work_init, sizeof(unsigned long long), hipMemcpyHostToDevice, st));
         }
     }
-    HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(unsigned long long) * kCounterWords, st));
     if ((p->flags & BDPT_FLAG_COUNT) && fr.nrows > 0) {  // queries per local row (bdpt_get_row_costs)
-        if (c->row_cost_cap < fr.nrows) {
-            HIP_TRY(hipStreamSynchronize(st));
-            if (c->row_cost) HIP_TRY(hipFree(c->row_cost));
-            c->row_cost = nullptr;
-            c->row_cost_cap = 0;
-            HIP_TRY(hipMalloc(&c->row_cost, sizeof(unsigned long long) * fr.nrows));
-            c->row_cost_cap = fr.nrows;
-        }
+        HIP_TRY(c->row_cost.reserve(sizeof(unsigned long long) * fr.nrows));
         HIP_TRY(hipMemsetAsync(c->row_cost, 0, sizeof(unsigned long long) * fr.nrows, st));
         fr.row_cost = c->row_cost;
         c->row_cost_n = fr.nrows;
     }
-    HIP_TRY(hipMemsetAsync(c->capped, 0, sizeof(uint32_t), st));
     HIP_TRY(hipMemsetAsync(c->diag, 0, sizeof(unsigned long long) * dev::kDiagWords, st));
     HIP_TRY(hipMemsetAsync(c->diag + dev::kDiagStart, 0xff, sizeof(unsigned long long), st));
     fr.diag = c->diag;
-    HIP_TRY(hipEventRecord(c->ev0, st));
+    if ((rc = begin_timed(c, st))) return rc;
     int64_t launches = 0;
     if (fr.total_samples > 0) {
         const FrameBuild& b = pick_frame_build(c, p);
@@ -1011,7 +1069,7 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
         const bool park = park_depth > 0 && !(p->flags & BDPT_FLAG_COUNT);
         if (park) {
             const size_t words = static_cast<size_t>(c->nslots) * (kParkSlotWords + 1) + 1;
-            if (!c->park) HIP_TRY(hipMalloc(&c->park, words * sizeof(uint32_t)));
+            HIP_TRY(c->park.reserve(words * sizeof(uint32_t)));
             HIP_TRY(hipMemsetAsync(c->park, 0, words * sizeof(uint32_t), st));
             fr.park = c->park;
             fr.park_depth = park_depth;
@@ -1033,21 +1091,12 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
         c->last_kernel_glossy = b.glossy;
         launches += 1 + 2 * rounds;
     }
-    HIP_TRY(hipEventRecord(c->ev1, st));
-    if ((rc = end_use(c, st))) return rc;
-    c->pending_timing = true;
-    c->diag_pending = true;
-    c->stats = bdpt_stats{};
-    c->stats.samples = static_cast<int64_t>(fr.total_samples - range_lo);
-    c->stats.launches = launches;
-    return BDPT_OK;
+    return end_timed(c, st, static_cast<int64_t>(fr.total_samples - range_lo), launches, true);
 }
 
 int bdpt_render(bdpt_ctx* c, const bdpt_frame_params* p, float* fb, void* hip_stream) {
     return render_bdpt(c, p, nullptr, fb, hip_stream);
 }
-
-static int ensure_tmp_fb(bdpt_ctx* c, size_t floats);
 
 // PathTracerIntegrator (path.h) on the same substrate: pt_kernels.hip.
 constexpr int kPtMaxLevels = 512;  // recursion levels per lane under Russian roulette (P(> 512) ~ 0.95^507)
@@ -1061,8 +1110,7 @@ static int pt_frame_tables(const bdpt_ctx* c) {
 }
 
 static int ensure_pt(bdpt_ctx* c, int levels) {
-    if (!c->pt_dparams) {
-        HIP_TRY(hipMalloc(&c->pt_dparams, pt_params_bytes()));
+    if (!c->pt_nslots) {
         // Up to 4 resident 256-lane blocks per CU (4 waves/SIMD at 128 VGPRs;
         // measured 70 -> 119 Msamples/s from 2), within the BDPT grid (the
         // traversal-stack overflow buffer is sized for that many slots).
@@ -1072,15 +1120,10 @@ static int ensure_pt(bdpt_ctx* c, int levels) {
         const int cap = cap_env ? std::max(1, std::atoi(cap_env)) : 4;
         c->pt_grid = std::min(c->grid, c->cus * std::min(cap, pt_blocks_per_cu(4 * static_cast<size_t>(c->sc.lds_words))));
         c->pt_nslots = static_cast<uint32_t>(c->pt_grid) * 256u;
-        HIP_TRY(hipMalloc(&c->pt_ring, sizeof(uint32_t) * 624 * static_cast<size_t>(c->pt_nslots)));
     }
-    const size_t need = static_cast<size_t>(levels) * 5 * c->pt_nslots;
-    if (need > c->pt_levels_f4) {
-        if (c->pt_levels) HIP_TRY(hipFree(c->pt_levels));
-        c->pt_levels = nullptr;
-        HIP_TRY(hipMalloc(&c->pt_levels, need * sizeof(float4)));
-        c->pt_levels_f4 = need;
-    }
+    HIP_TRY(c->pt_dparams.reserve(pt_params_bytes()));
+    HIP_TRY(c->pt_ring.reserve(sizeof(uint32_t) * 624 * static_cast<size_t>(c->pt_nslots)));
+    HIP_TRY(c->pt_levels.reserve(sizeof(float4) * 5 * static_cast<size_t>(levels) * c->pt_nslots));
     return BDPT_OK;
 }
 
@@ -1097,44 +1140,80 @@ static dev::DevScene pt_scene(const bdpt_ctx* c, const bdpt_frame_params* p) {
     return sc;
 }
 
-static int render_path(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
-                       const bdpt_path_params* path, float* fb, void* hip_stream) {
-    if (!c || !fb || !path) return fail(BDPT_ERR_INVALID, "null argument");
-    if (int trc = textured_unsupported(c, "the path integrator (texture + bdpt_render_path)")) return trc;
-    if (!p) return fail(BDPT_ERR_INVALID, "null params");
-    if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(BDPT_ERR_INVALID, "width/height/spp must be > 0");
-    if (static_cast<int64_t>(p->width) * p->height >= (1ll << 31))
-        return fail(BDPT_ERR_INVALID, "image too large (W*H must fit int32, as in the reference)");
-    if (p->row_stride < 1 || p->row_offset < 0) return fail(BDPT_ERR_INVALID, "bad row shard");
+// The launch_pt settings block of a path tracer and the level-stack depth it needs: maxDepth
+// levels, or Russian roulette's (check_pt_levels).
+static int path_sample_settings(const bdpt_path_params* path, int32_t settings[8], int& levels) {
+    if (!path) return fail(BDPT_ERR_INVALID, "null argument");
     if (path->emitter_samples < 0 || path->bsdf_samples < 0) return fail(BDPT_ERR_INVALID, "negative sample counts");
-    if (int wrc = check_window(p, w)) return wrc;
-    // the recursion depth the settings allow: maxDepth levels, or Russian roulette
     const bool rr = path->is_explicit && path->max_depth == -1;
-    const int levels = rr ? kPtMaxLevels : std::max(path->max_depth, 0) + 2;
+    levels = rr ? kPtMaxLevels : std::max(path->max_depth, 0) + 2;
+    const int32_t s[8] = {path->is_explicit ? 1 : 0, path->max_depth, path->rr_depth, 0, path->emitter_samples,
+                          path->bsdf_samples, levels, 0};
+    std::memcpy(settings, s, sizeof(s));
+    std::memcpy(&settings[3], &path->rr_prob, 4);
+    return BDPT_OK;
+}
+static int check_pt_levels(int levels) {
     if (levels > kPtMaxLevels) return fail(BDPT_ERR_UNSUPPORTED, "maxDepth > 510 is not supported");
+    return BDPT_OK;
+}
+
+// DirectIntegrator (direct.h) on the path tracer's kernel: one level, no recursion.
+static int direct_sample_settings(const bdpt_direct_params* d, int32_t settings[8]) {
+    if (!d) return fail(BDPT_ERR_INVALID, "null argument");
+    if (d->sampling_strategy < BDPT_DIRECT_AREA || d->sampling_strategy > BDPT_DIRECT_MIS)
+        return fail(BDPT_ERR_INVALID, "Error: wrong strategy");  // direct.h:460
+    if (d->emitter_samples < 0 || d->bsdf_samples < 0) return fail(BDPT_ERR_INVALID, "negative sample counts");
+    const int32_t s[8] = {1, -1, 0, 0, d->emitter_samples, d->bsdf_samples, 1, d->sampling_strategy};
+    std::memcpy(settings, s, sizeof(s));
+    return BDPT_OK;
+}
+
+// The frame render of the path tracer and of the direct integrator (w null: every sample).
+// integrator: the entry's bdpt_path_params / bdpt_direct_params; settings_of(integrator, block,
+// levels): its checks and its settings block (path_sample_settings / direct_sample_settings),
+// which run where the two entries always ran them, after the row shard's check and before
+// the window's; what: how the entry refuses a scene with bitmap textures.
+static int render_pt_frame(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, const void* integrator,
+                           int (*settings_of)(const void*, int32_t*, int&), const char* what, float* fb,
+                           void* hip_stream) {
+    if (!c || !fb || !integrator) return fail(BDPT_ERR_INVALID, "null argument");
+    int rc, levels = 1;
+    int32_t settings[8];
+    if ((rc = textured_unsupported(c, what)) || (rc = check_frame_size(p)) || (rc = check_row_shard(p)) ||
+        (rc = settings_of(integrator, settings, levels)) || (rc = check_window(p, w)) || (rc = check_pt_levels(levels)))
+        return rc;
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
     if ((rc = pt_frame_tables(c)) || (rc = ensure_pt(c, levels))) return rc;
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     const dev::DevFrame fr = make_frame(p, w);
-    int32_t settings[8] = {path->is_explicit ? 1 : 0, path->max_depth, path->rr_depth, 0, path->emitter_samples,
-                           path->bsdf_samples, levels, 0};
-    std::memcpy(&settings[3], &path->rr_prob, 4);
     if ((rc = begin_use(c, st))) return rc;
     HIP_TRY(hipMemsetAsync(c->work, 0, sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(unsigned long long) * kCounterWords, st));
-    HIP_TRY(hipEventRecord(c->ev0, st));
+    if ((rc = begin_timed(c, st))) return rc;
     if (fr.total_samples > 0)
         HIP_TRY(launch_pt(pt_scene(c, p), fr, settings, fb, c->pt_levels, c->pt_ring, c->gstack, c->pt_nslots, c->work,
                           c->counters, c->pt_grid, st, c->pt_dparams));
-    HIP_TRY(hipEventRecord(c->ev1, st));
-    if ((rc = end_use(c, st))) return rc;
-    c->pending_timing = true;
-    c->diag_pending = false;
-    c->stats = bdpt_stats{};
-    c->stats.samples = static_cast<int64_t>(fr.total_samples);
-    c->stats.launches = fr.total_samples > 0 ? 1 : 0;
-    return BDPT_OK;
+    return end_timed(c, st, static_cast<int64_t>(fr.total_samples), fr.total_samples > 0 ? 1 : 0);
+}
+
+static int render_path(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                       const bdpt_path_params* path, float* fb, void* hip_stream) {
+    return render_pt_frame(
+        c, p, w, path,
+        [](const void* path, int32_t* settings, int& levels) {
+            return path_sample_settings(static_cast<const bdpt_path_params*>(path), settings, levels);
+        },
+        "the path integrator (texture + bdpt_render_path)", fb, hip_stream);
+}
+
+static int render_direct(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                         const bdpt_direct_params* d, float* fb, void* hip_stream) {
+    return render_pt_frame(
+        c, p, w, d,
+        [](const void* d, int32_t* settings, int&) {
+            return direct_sample_settings(static_cast<const bdpt_direct_params*>(d), settings);
+        },
+        "the direct integrator (texture + bdpt_render_direct)", fb, hip_stream);
 }
 
 int bdpt_render_path(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_params* path, float* fb,
@@ -1142,18 +1221,25 @@ int bdpt_render_path(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_pa
     return render_path(c, p, nullptr, path, fb, hip_stream);
 }
 
-static int render_path_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
-                            const bdpt_path_params* path, float* fb_host) {
+int bdpt_render_direct(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_direct_params* d, float* fb,
+                       void* hip_stream) {
+    return render_direct(c, p, nullptr, d, fb, hip_stream);
+}
+
+// What the path / direct host entries check before they stage the frame.
+static int pt_host_args(const bdpt_ctx* c, const bdpt_frame_params* p, const float* fb_host) {
     if (!c || !fb_host || !p) return fail(BDPT_ERR_INVALID, "null argument");
     if (p->width <= 0 || p->height <= 0) return fail(BDPT_ERR_INVALID, "width/height must be > 0");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n = static_cast<size_t>(p->width) * p->height * 3;
-    int rc;
-    if ((rc = ensure_tmp_fb(c, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->tmp_fb, fb_host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if ((rc = render_path(c, p, w, path, c->tmp_fb, c->stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(fb_host, c->tmp_fb, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+static int render_path_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                            const bdpt_path_params* path, float* fb_host) {
+    int rc = pt_host_args(c, p, fb_host);
+    if (rc) return rc;
+    if ((rc = stage_host(c, fb_host, static_cast<size_t>(p->width) * p->height * 3,
+                         [&](float* fb) { return render_path(c, p, w, path, fb, c->stream); })))
+        return rc;
     bdpt_stats st;
     if ((rc = bdpt_get_stats(c, &st))) return rc;
     if (st.counters[1] != 0)
@@ -1161,65 +1247,15 @@ static int render_path_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_
     return BDPT_OK;
 }
 
-int bdpt_render_path_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_params* path, float* fb_host) {
-    return render_path_host(c, p, nullptr, path, fb_host);
-}
-
-// DirectIntegrator (direct.h) on the path tracer's kernel: one level, no recursion.
-static int render_direct(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
-                         const bdpt_direct_params* d, float* fb, void* hip_stream) {
-    if (!c || !fb || !d) return fail(BDPT_ERR_INVALID, "null argument");
-    if (int trc = textured_unsupported(c, "the direct integrator (texture + bdpt_render_direct)")) return trc;
-    if (!p) return fail(BDPT_ERR_INVALID, "null params");
-    if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(BDPT_ERR_INVALID, "width/height/spp must be > 0");
-    if (static_cast<int64_t>(p->width) * p->height >= (1ll << 31))
-        return fail(BDPT_ERR_INVALID, "image too large (W*H must fit int32, as in the reference)");
-    if (p->row_stride < 1 || p->row_offset < 0) return fail(BDPT_ERR_INVALID, "bad row shard");
-    if (d->sampling_strategy < BDPT_DIRECT_AREA || d->sampling_strategy > BDPT_DIRECT_MIS)
-        return fail(BDPT_ERR_INVALID, "Error: wrong strategy");  // direct.h:460
-    if (d->emitter_samples < 0 || d->bsdf_samples < 0) return fail(BDPT_ERR_INVALID, "negative sample counts");
-    if (int wrc = check_window(p, w)) return wrc;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = pt_frame_tables(c)) || (rc = ensure_pt(c, 1))) return rc;
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    const dev::DevFrame fr = make_frame(p, w);
-    const int32_t settings[8] = {1, -1, 0, 0, d->emitter_samples, d->bsdf_samples, 1, d->sampling_strategy};
-    if ((rc = begin_use(c, st))) return rc;
-    HIP_TRY(hipMemsetAsync(c->work, 0, sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(unsigned long long) * kCounterWords, st));
-    HIP_TRY(hipEventRecord(c->ev0, st));
-    if (fr.total_samples > 0)
-        HIP_TRY(launch_pt(pt_scene(c, p), fr, settings, fb, c->pt_levels, c->pt_ring, c->gstack, c->pt_nslots, c->work,
-                          c->counters, c->pt_grid, st, c->pt_dparams));
-    HIP_TRY(hipEventRecord(c->ev1, st));
-    if ((rc = end_use(c, st))) return rc;
-    c->pending_timing = true;
-    c->diag_pending = false;
-    c->stats = bdpt_stats{};
-    c->stats.samples = static_cast<int64_t>(fr.total_samples);
-    c->stats.launches = fr.total_samples > 0 ? 1 : 0;
-    return BDPT_OK;
-}
-
-int bdpt_render_direct(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_direct_params* d, float* fb,
-                       void* hip_stream) {
-    return render_direct(c, p, nullptr, d, fb, hip_stream);
-}
-
 static int render_direct_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
                               const bdpt_direct_params* d, float* fb_host) {
-    if (!c || !fb_host || !p) return fail(BDPT_ERR_INVALID, "null argument");
-    if (p->width <= 0 || p->height <= 0) return fail(BDPT_ERR_INVALID, "width/height must be > 0");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n = static_cast<size_t>(p->width) * p->height * 3;
-    int rc;
-    if ((rc = ensure_tmp_fb(c, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->tmp_fb, fb_host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if ((rc = render_direct(c, p, w, d, c->tmp_fb, c->stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(fb_host, c->tmp_fb, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return BDPT_OK;
+    if (int rc = pt_host_args(c, p, fb_host)) return rc;
+    return stage_host(c, fb_host, static_cast<size_t>(p->width) * p->height * 3,
+                      [&](float* fb) { return render_direct(c, p, w, d, fb, c->stream); });
+}
+
+int bdpt_render_path_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_params* path, float* fb_host) {
+    return render_path_host(c, p, nullptr, path, fb_host);
 }
 
 int bdpt_render_direct_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_direct_params* d, float* fb_host) {
@@ -1227,11 +1263,10 @@ int bdpt_render_direct_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_
 }
 
 static int ensure_sample_buffers(bdpt_ctx* c, int32_t splat_cap) {
-    if (!c->mt_state) HIP_TRY(hipMalloc(&c->mt_state, sizeof(uint32_t) * BDPT_MT19937_WORDS));
+    HIP_TRY(c->mt_state.reserve(sizeof(uint32_t) * BDPT_MT19937_WORDS));
     if (splat_cap > c->splat_cap) {
-        if (c->splat_list) HIP_TRY(hipFree(c->splat_list));
-        c->splat_list = nullptr;
-        HIP_TRY(hipMalloc(&c->splat_list, sizeof(float) * 4 * (static_cast<size_t>(splat_cap) + 1)));
+        c->splat_cap = 0;
+        HIP_TRY(c->splat_list.reserve(sizeof(float) * 4 * (static_cast<size_t>(splat_cap) + 1)));
         c->splat_cap = splat_cap;
     }
     return BDPT_OK;
@@ -1280,34 +1315,11 @@ static int render_pt_sample(bdpt_ctx* c, const bdpt_frame_params* p, const int32
     return BDPT_OK;
 }
 
-static int path_sample_settings(const bdpt_path_params* path, int32_t settings[8], int& levels) {
-    if (!path) return fail(BDPT_ERR_INVALID, "null argument");
-    if (path->emitter_samples < 0 || path->bsdf_samples < 0) return fail(BDPT_ERR_INVALID, "negative sample counts");
-    const bool rr = path->is_explicit && path->max_depth == -1;
-    levels = rr ? kPtMaxLevels : std::max(path->max_depth, 0) + 2;
-    if (levels > kPtMaxLevels) return fail(BDPT_ERR_UNSUPPORTED, "maxDepth > 510 is not supported");
-    const int32_t s[8] = {path->is_explicit ? 1 : 0, path->max_depth, path->rr_depth, 0, path->emitter_samples,
-                          path->bsdf_samples, levels, 0};
-    std::memcpy(settings, s, sizeof(s));
-    std::memcpy(&settings[3], &path->rr_prob, 4);
-    return BDPT_OK;
-}
-
-static int direct_sample_settings(const bdpt_direct_params* d, int32_t settings[8]) {
-    if (!d) return fail(BDPT_ERR_INVALID, "null argument");
-    if (d->sampling_strategy < BDPT_DIRECT_AREA || d->sampling_strategy > BDPT_DIRECT_MIS)
-        return fail(BDPT_ERR_INVALID, "Error: wrong strategy");  // direct.h:460
-    if (d->emitter_samples < 0 || d->bsdf_samples < 0) return fail(BDPT_ERR_INVALID, "negative sample counts");
-    const int32_t s[8] = {1, -1, 0, 0, d->emitter_samples, d->bsdf_samples, 1, d->sampling_strategy};
-    std::memcpy(settings, s, sizeof(s));
-    return BDPT_OK;
-}
-
 int bdpt_render_path_sample_mt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_path_params* path,
                                const float ray[8], uint32_t state[BDPT_MT19937_WORDS], float Li[3]) {
     int32_t settings[8];
     int levels = 0, rc;
-    if ((rc = path_sample_settings(path, settings, levels))) return rc;
+    if ((rc = path_sample_settings(path, settings, levels)) || (rc = check_pt_levels(levels))) return rc;
     return render_pt_sample(c, p, settings, levels, ray, state, Li);
 }
 
@@ -1336,7 +1348,7 @@ int bdpt_render_path_sample(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_
                             const float ray[8], uint32_t seed, int32_t* draws, float Li[3]) {
     int32_t settings[8];
     int levels = 0, rc;
-    if ((rc = path_sample_settings(path, settings, levels))) return rc;
+    if ((rc = path_sample_settings(path, settings, levels)) || (rc = check_pt_levels(levels))) return rc;
     return pt_sample_seeded(c, p, settings, levels, ray, seed, draws, Li);
 }
 
@@ -1357,19 +1369,17 @@ int bdpt_debug_math(int32_t device, int32_t fn, const float* x, const float* y, 
     if (device < 0 || device >= count) return fail(BDPT_ERR_INVALID, "bad device");
     HIP_TRY(hipSetDevice(device));
     if (n == 0) return BDPT_OK;
-    float *dx = nullptr, *dy = nullptr, *dout = nullptr;
+    DevBuf<float> dx, dy, dout;
     const size_t bytes = sizeof(float) * static_cast<size_t>(n);
-    hipError_t e = hipMalloc(&dx, bytes);
-    if (e == hipSuccess) e = hipMalloc(&dy, bytes);
-    if (e == hipSuccess) e = hipMalloc(&dout, bytes);
+    hipError_t e = dx.reserve(bytes);
+    if (e == hipSuccess) e = dy.reserve(bytes);
+    if (e == hipSuccess) e = dout.reserve(bytes);
     if (e == hipSuccess) e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dy, y ? y : x, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess)
         e = fn >= BDPT_MATH_POW_W ? launch_math_check_fw(fn, dx, dy, dout, n, nullptr)
                                   : launch_math_check(fn, dx, dy, dout, n, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
-    for (float* p : {dx, dy, dout})
-        if (p) (void)hipFree(p);
     if (e != hipSuccess) return fail(BDPT_ERR_HIP, std::string("bdpt_debug_math: ") + hipGetErrorString(e));
     return BDPT_OK;
 }
@@ -1387,11 +1397,9 @@ int bdpt_set_row_order(bdpt_ctx* c, const int32_t* order, int32_t n) {
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());  // a render in flight may read the previous order
-    if (c->row_order) HIP_TRY(hipFree(c->row_order));
-    c->row_order = nullptr;
     c->row_order_n = 0;
     if (n == 0) return BDPT_OK;
-    HIP_TRY(hipMalloc(&c->row_order, sizeof(int32_t) * static_cast<size_t>(n)));
+    HIP_TRY(c->row_order.reserve(sizeof(int32_t) * static_cast<size_t>(n)));
     HIP_TRY(hipMemcpy(c->row_order, order, sizeof(int32_t) * static_cast<size_t>(n), hipMemcpyHostToDevice));
     c->row_order_n = n;
     return BDPT_OK;
@@ -1457,28 +1465,14 @@ int bdpt_synchronize(bdpt_ctx* c) {
     return BDPT_OK;
 }
 
-static int ensure_tmp_fb(bdpt_ctx* c, size_t floats) {
-    if (floats > c->tmp_fb_floats) {
-        if (c->tmp_fb) HIP_TRY(hipFree(c->tmp_fb));
-        c->tmp_fb = nullptr;
-        HIP_TRY(hipMalloc(&c->tmp_fb, floats * sizeof(float)));
-        c->tmp_fb_floats = floats;
-    }
-    return BDPT_OK;
-}
-
 static int render_bdpt_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* fb_host) {
     if (!c || !fb_host) return fail(BDPT_ERR_INVALID, "null argument");
     int rc = check_params(p);
     if (rc) return rc;
     if ((rc = check_window(p, w))) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n = static_cast<size_t>(p->width) * p->height * 3;
-    if ((rc = ensure_tmp_fb(c, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->tmp_fb, fb_host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if ((rc = render_bdpt(c, p, w, c->tmp_fb, c->stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(fb_host, c->tmp_fb, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = stage_host(c, fb_host, static_cast<size_t>(p->width) * p->height * 3,
+                         [&](float* fb) { return render_bdpt(c, p, w, fb, c->stream); })))
+        return rc;
     {
         bdpt_stats st;
         if ((rc = bdpt_get_stats(c, &st))) return rc;
@@ -1620,27 +1614,6 @@ int bdpt_render_sample(bdpt_ctx* c, const bdpt_frame_params* p, const float ray[
     return BDPT_OK;
 }
 
-static int ensure_kat(bdpt_ctx* c, size_t bytes, void** buf) {
-    HIP_TRY(hipMalloc(buf, std::max<size_t>(bytes, 16)));
-    return BDPT_OK;
-}
-
-// Host arrays in, device run, host arrays out (the per-function entry points).
-struct KatBuffers {
-    std::vector<void*> p;
-    ~KatBuffers() {
-        for (void* q : p) (void)hipFree(q);
-    }
-};
-
-static int kat_in(bdpt_ctx* c, KatBuffers& kb, const void* src, size_t bytes, void** dst) {
-    int rc;
-    if ((rc = ensure_kat(c, bytes, dst))) return rc;
-    kb.p.push_back(*dst);
-    if (src && bytes) HIP_TRY(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    return BDPT_OK;
-}
-
 // build: BDPT_KAT_EXACT / _FAST / _NG, the compilation of the BSDF kernel to run
 static int bsdf_kat(bdpt_ctx* c, int mode, int64_t n, const int32_t* mat, const float* wo, const float* x,
                     float* out, int out_per, int build = BDPT_KAT_EXACT) {
@@ -1661,16 +1634,15 @@ static int bsdf_kat(bdpt_ctx* c, int mode, int64_t n, const int32_t* mat, const 
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = begin_use(c, c->stream))) return rc;
-    KatBuffers kb;
-    void *dm, *dwo, *dx, *dout;
+    DevBuf<int32_t> dm;
+    DevBuf<float> dwo, dx, dout;
     const size_t N = static_cast<size_t>(n);
-    if ((rc = kat_in(c, kb, mat, 4 * N, &dm)) || (rc = kat_in(c, kb, wo, 12 * N, &dwo)) ||
-        (rc = kat_in(c, kb, x, (mode == 2 ? 8 : 12) * N, &dx)) || (rc = kat_in(c, kb, nullptr, 4 * out_per * N, &dout)))
+    if ((rc = kat_in(c, dm, mat, 4 * N)) || (rc = kat_in(c, dwo, wo, 12 * N)) ||
+        (rc = kat_in(c, dx, x, (mode == 2 ? 8 : 12) * N)) || (rc = kat_in<float>(c, dout, nullptr, 4 * out_per * N)))
         return rc;
     const auto launch = build == BDPT_KAT_FAST ? launch_bsdf_kat_fw : build == BDPT_KAT_NG ? launch_bsdf_kat_ng
                                                                                             : launch_bsdf_kat;
-    HIP_TRY(launch(c->sc, mode, n, static_cast<const int32_t*>(dm), static_cast<const float*>(dwo),
-                   static_cast<const float*>(dx), static_cast<float*>(dout), c->stream));
+    HIP_TRY(launch(c->sc, mode, n, dm, dwo, dx, dout, c->stream));
     HIP_TRY(hipMemcpyAsync(out, dout, 4 * out_per * N, hipMemcpyDeviceToHost, c->stream));
     if ((rc = end_use(c, c->stream))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1731,15 +1703,15 @@ int bdpt_intersect_from(bdpt_ctx* c, int64_t n, const float* rays, const float* 
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = begin_use(c, c->stream))) return rc;
-    KatBuffers kb;
-    void *dr, *dout, *dn = nullptr, *dt = nullptr;
+    DevBuf<float> dr, dout, dn;
+    DevBuf<int32_t> dt;
     const size_t N = static_cast<size_t>(n);
     if (origin_tris)
         for (size_t i = 0; i < N; i++)
             if (origin_tris[i] < -1 || origin_tris[i] >= c->ntri) return fail(BDPT_ERR_INVALID, "origin_tris out of range");
-    if ((rc = kat_in(c, kb, rays, 32 * N, &dr)) || (rc = kat_in(c, kb, nullptr, 80 * N, &dout))) return rc;
-    if (origin_normals && (rc = kat_in(c, kb, origin_normals, 12 * N, &dn))) return rc;
-    if (origin_normals && origin_tris && (rc = kat_in(c, kb, origin_tris, 4 * N, &dt))) return rc;
+    if ((rc = kat_in(c, dr, rays, 32 * N)) || (rc = kat_in<float>(c, dout, nullptr, 80 * N))) return rc;
+    if (origin_normals && (rc = kat_in(c, dn, origin_normals, 12 * N))) return rc;
+    if (origin_normals && origin_tris && (rc = kat_in(c, dt, origin_tris, 4 * N))) return rc;
     // The interior-box test the frame kernels would use for these origins: without
     // the ambiguity slack when every origin lies within 100 scene diagonals (as
     // for a frame whose camera does, node_slack_needed), with it otherwise.
@@ -1750,10 +1722,8 @@ int bdpt_intersect_from(bdpt_ctx* c, int64_t n, const float* rays, const float* 
     // the traversal-stack overflow columns serve c->nslots rays at a time
     for (int64_t b = 0; b < n; b += c->nslots) {
         const int64_t m = std::min<int64_t>(c->nslots, n - b);
-        HIP_TRY(launch_intersect_kat(sc, m, occlusion ? 1 : 0, static_cast<const float*>(dr) + 8 * b,
-                                     dn ? static_cast<const float*>(dn) + 3 * b : nullptr,
-                                     dt ? static_cast<const int32_t*>(dt) + b : nullptr, c->gstack, c->nslots,
-                                     static_cast<float*>(dout) + 20 * b, c->stream));
+        HIP_TRY(launch_intersect_kat(sc, m, occlusion ? 1 : 0, dr + 8 * b, dn ? dn + 3 * b : nullptr,
+                                     dt ? dt + b : nullptr, c->gstack, c->nslots, dout + 20 * b, c->stream));
     }
     HIP_TRY(hipMemcpyAsync(out, dout, 80 * N, hipMemcpyDeviceToHost, c->stream));
     if ((rc = end_use(c, c->stream))) return rc;
@@ -1763,31 +1733,9 @@ int bdpt_intersect_from(bdpt_ctx* c, int64_t n, const float* rays, const float* 
 
 // ---- first-hit feature buffers and the filter for preview frames (aov_kernels.hip) ----
 static int check_aov_params(const bdpt_frame_params* p) {
-    if (!p) return fail(BDPT_ERR_INVALID, "null params");
-    if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(BDPT_ERR_INVALID, "width/height/spp must be > 0");
-    if (static_cast<int64_t>(p->width) * p->height >= (1ll << 31))
-        return fail(BDPT_ERR_INVALID, "image too large (W*H must fit int32, as in the reference)");
+    if (int rc = check_frame_size(p)) return rc;
     if (p->flags != 0) return fail(BDPT_ERR_UNSUPPORTED, "bdpt_render_aov: flags must be 0 (no counting pass or full traversal)");
-    if (p->row_stride < 1 || p->row_offset < 0) return fail(BDPT_ERR_INVALID, "bad row shard");
-    return BDPT_OK;
-}
-
-// Events and stats of a call that is not a frame render: kernel_ms, samples, launches.
-static int begin_timed(bdpt_ctx* c, hipStream_t st) {
-    HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(unsigned long long) * kCounterWords, st));
-    HIP_TRY(hipMemsetAsync(c->capped, 0, sizeof(uint32_t), st));
-    HIP_TRY(hipEventRecord(c->ev0, st));
-    return BDPT_OK;
-}
-static int end_timed(bdpt_ctx* c, hipStream_t st, int64_t samples, int64_t launches) {
-    HIP_TRY(hipEventRecord(c->ev1, st));
-    if (int rc = end_use(c, st)) return rc;
-    c->pending_timing = true;
-    c->diag_pending = false;
-    c->stats = bdpt_stats{};
-    c->stats.samples = samples;
-    c->stats.launches = launches;
-    return BDPT_OK;
+    return check_row_shard(p);
 }
 
 int bdpt_render_aov(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* aov,
@@ -1814,14 +1762,8 @@ int bdpt_render_aov_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sam
     int rc = check_aov_params(p);
     if (rc) return rc;
     if ((rc = check_window(p, w))) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n = static_cast<size_t>(p->width) * p->height * 8;
-    if ((rc = ensure_tmp_fb(c, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->tmp_fb, aov_host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if ((rc = bdpt_render_aov(c, p, w, c->tmp_fb, c->stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(aov_host, c->tmp_fb, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return BDPT_OK;
+    return stage_host(c, aov_host, static_cast<size_t>(p->width) * p->height * 8,
+                      [&](float* aov) { return bdpt_render_aov(c, p, w, aov, c->stream); });
 }
 
 static int check_denoise(int32_t width, int32_t height, const float* color, const float* aov, const float* out,
@@ -1855,16 +1797,11 @@ int bdpt_denoise(bdpt_ctx* c, int32_t width, int32_t height, const float* color,
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     const size_t px = static_cast<size_t>(width) * height;
     if ((rc = begin_use(c, st))) return rc;
-    if (d->iterations > 0 && px > c->dn_pixels) {  // the stream's earlier work may still read the old buffers
-        HIP_TRY(hipStreamSynchronize(st));
-        for (void** q : {&c->dn_guide, &c->dn_img[0], &c->dn_img[1]}) {
-            if (*q) HIP_TRY(hipFree(*q));
-            *q = nullptr;
-        }
+    if (d->iterations > 0 && px > c->dn_pixels) {
         c->dn_pixels = 0;
-        HIP_TRY(hipMalloc(&c->dn_guide, px * 32));
-        HIP_TRY(hipMalloc(&c->dn_img[0], px * 16));
-        HIP_TRY(hipMalloc(&c->dn_img[1], px * 16));
+        HIP_TRY(c->dn_guide.reserve(px * 32));
+        HIP_TRY(c->dn_img[0].reserve(px * 16));
+        HIP_TRY(c->dn_img[1].reserve(px * 16));
         c->dn_pixels = px;
     }
     if ((rc = begin_timed(c, st))) return rc;
@@ -1890,7 +1827,7 @@ int bdpt_denoise_host(bdpt_ctx* c, int32_t width, int32_t height, const float* c
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t px = static_cast<size_t>(width) * height;
-    if ((rc = ensure_tmp_fb(c, px * 14))) return rc;
+    HIP_TRY(c->tmp_fb.reserve(px * 14 * sizeof(float)));
     float *dc = c->tmp_fb, *da = c->tmp_fb + px * 3, *dout = c->tmp_fb + px * 11;  // color, aov (16-byte aligned or not: scalar loads), out
     HIP_TRY(hipMemcpyAsync(dc, color, px * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(da, aov, px * 8 * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -1907,11 +1844,11 @@ int bdpt_splat_to_image_plane(bdpt_ctx* c, const bdpt_frame_params* p, int64_t n
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = begin_use(c, c->stream))) return rc;
-    KatBuffers kb;
-    void *dp, *dxy;
+    DevBuf<float> dp;
+    DevBuf<int32_t> dxy;
     const size_t N = static_cast<size_t>(n);
-    if ((rc = kat_in(c, kb, pts, 12 * N, &dp)) || (rc = kat_in(c, kb, nullptr, 8 * N, &dxy))) return rc;
-    HIP_TRY(launch_splat_kat(make_frame(p), n, static_cast<const float*>(dp), static_cast<int32_t*>(dxy), c->stream));
+    if ((rc = kat_in(c, dp, pts, 12 * N)) || (rc = kat_in<int32_t>(c, dxy, nullptr, 8 * N))) return rc;
+    HIP_TRY(launch_splat_kat(make_frame(p), n, dp, dxy, c->stream));
     HIP_TRY(hipMemcpyAsync(xy, dxy, 8 * N, hipMemcpyDeviceToHost, c->stream));
     if ((rc = end_use(c, c->stream))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1926,16 +1863,14 @@ static int device_kat(int32_t device, size_t in_bytes, const float* in, size_t i
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(BDPT_ERR_NO_DEVICE, "no HIP device");
     if (device < 0 || device >= count) return fail(BDPT_ERR_INVALID, "bad device");
     HIP_TRY(hipSetDevice(device));
-    float *a = nullptr, *b = nullptr, *o = nullptr;
-    hipError_t e = hipMalloc(&a, std::max<size_t>(in_bytes, 16));
-    if (e == hipSuccess) e = hipMalloc(&b, std::max<size_t>(in2_bytes, 16));
-    if (e == hipSuccess) e = hipMalloc(&o, std::max<size_t>(out_bytes, 16));
+    DevBuf<float> a, b, o;
+    hipError_t e = a.reserve(std::max<size_t>(in_bytes, 16));
+    if (e == hipSuccess) e = b.reserve(std::max<size_t>(in2_bytes, 16));
+    if (e == hipSuccess) e = o.reserve(std::max<size_t>(out_bytes, 16));
     if (e == hipSuccess) e = hipMemcpy(a, in, in_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess && in2) e = hipMemcpy(b, in2, in2_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = launch(a, b, o);
     if (e == hipSuccess) e = hipMemcpy(out, o, out_bytes, hipMemcpyDeviceToHost);
-    for (float* q : {a, b, o})
-        if (q) (void)hipFree(q);
     if (e != hipSuccess) return fail(BDPT_ERR_HIP, std::string("device diagnostic: ") + hipGetErrorString(e));
     return BDPT_OK;
 }
