@@ -283,6 +283,8 @@ def lib():
         L.bdpt_bsdf_type.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(i32)]
         L.bdpt_intersect.argtypes = [vp, i64, vp, i32, vp]
         L.bdpt_splat_to_image_plane.argtypes = [vp, ctypes.POINTER(_FrameParams), i64, vp, vp]
+        L.bdpt_debug_sampling.argtypes = [vp, ctypes.POINTER(_FrameParams), i32, i32, i32, i64, vp, vp,
+                                          ctypes.POINTER(i32)]
         L.bdpt_debug_fresnel.argtypes = [i32, i64, vp, vp]
         L.bdpt_debug_triangle.argtypes = [i32, i64, vp, vp, vp]
         L.bdpt_get_stats.argtypes = [vp, ctypes.POINTER(_Stats)]
@@ -874,6 +876,27 @@ class BDPTIntegrator:
         _check(lib().bdpt_splat_to_image_plane(self._h, ctypes.byref(p), q.shape[0], q.ctypes.data, out.ctypes.data))
         return out
 
+    def debug_sampling(self, fn: str, records, build: str = "exact", placement: str = "ctx") -> np.ndarray:
+        """bdpt_debug_sampling: one of SAMPLING_FNS on records (n, words in) of 32-bit words
+        (uint32; floats and ints by their bits), through the frame kernels' device functions:
+        uint32 (n, words out). "camera" uses this integrator's camera, width, height and spp.
+        build: "exact" or "fast"; placement ("ctx", "hbm", "lds"): where "cdf" and "emitter"
+        read the emitter faces and CDFs."""
+        code, nin, nout = SAMPLING_FNS[fn]
+        rec = np.ascontiguousarray(records, np.uint32).reshape(-1, nin)
+        out = np.zeros((rec.shape[0], nout), np.uint32)
+        p = self.params()
+        _check(lib().bdpt_debug_sampling(self._h, ctypes.byref(p), KAT_BUILDS[build], code,
+                                         EMITTER_PLACEMENTS[placement], rec.shape[0], rec.ctypes.data,
+                                         out.ctypes.data, None))
+        return out
+
+    def emitter_placement(self) -> str:
+        """Where this context's frames read the emitter faces and CDFs: "lds" or "hbm"."""
+        got = ctypes.c_int32(-1)
+        _check(lib().bdpt_debug_sampling(self._h, None, 0, 0, 0, 0, None, None, ctypes.byref(got)))
+        return {v: k for k, v in EMITTER_PLACEMENTS.items()}[got.value]
+
     def _integrator_params(self):
         """(bdpt_path_params, bdpt_direct_params) of bdpt_render_window: None, None = BDPT."""
         return None, None
@@ -1136,6 +1159,11 @@ class MultiDeviceRenderer:
 
 
 KAT_BUILDS = {"exact": 0, "fast": 1, "ng": 2}  # BDPT_KAT_*
+# BDPT_SAMPLING_*: code, words in, words out per element
+SAMPLING_FNS = {"canonical": (0, 1, 1), "hemisphere": (1, 2, 3), "triangle": (2, 2, 2), "sphere": (3, 2, 3),
+                "solid_angle": (4, 9, 4), "ray_sphere": (5, 12, 1), "cdf": (6, 2, 1), "emitter": (7, 4, 10),
+                "camera": (8, 3, 3)}
+EMITTER_PLACEMENTS = {"ctx": 0, "hbm": 1, "lds": 2}  # BDPT_EMITTERS_*
 MATH_FNS = {"sinf": 0, "cosf": 1, "powf": 2, "sincos_s": 3, "sincos_c": 4,  # BDPT_MATH_*
             "pow_w": 5, "rcp_w": 6, "div_w": 7, "sqrt_w": 8, "rsqrt_w": 9}
 

@@ -43,6 +43,11 @@ hipError_t launch_triangle_kat(int64_t n, const float* rays, const float* verts,
 hipError_t launch_intersect_kat(const dev::DevScene& sc, int64_t n, int occlusion, const float* rays, const float* nrm,
                                 const int32_t* otri, uint2* gstack, uint32_t nslots, float* out, hipStream_t st);
 hipError_t launch_splat_kat(const dev::DevFrame& fr, int64_t n, const float* p, int32_t* xy, hipStream_t st);
+// kat_sampling.hip: the sampling side per function, and with the fast weights (kat_sampling_fw.hip)
+hipError_t launch_sampling_kat(const dev::DevScene& sc, const dev::DevFrame& fr, int fn, int nin, int nout, int64_t n,
+                               const uint32_t* in, uint32_t* out, hipStream_t st);
+hipError_t launch_sampling_kat_fw(const dev::DevScene& sc, const dev::DevFrame& fr, int fn, int nin, int nout,
+                                  int64_t n, const uint32_t* in, uint32_t* out, hipStream_t st);
 // sample_state_tex.hip: the single-sample kernel for scenes with bitmap textures
 hipError_t launch_sample_tex(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf,
                              uint2* gstack, const dev::Ray& ray, float* out, hipStream_t stream);
@@ -349,6 +354,16 @@ static int stage_host(bdpt_ctx* c, float* host, size_t n, Run run) {
     HIP_TRY(hipMemcpyAsync(host, c->tmp_fb, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BDPT_OK;
+}
+
+// The LDS tables with the emitter faces (5 float4 each) and CDFs appended to `base` words:
+// their word offsets, and the total (16-byte rounded parts; bdpt_device.hpp scene_tables_to_lds).
+constexpr uint32_t kLdsBudget = 24u * 1024u;  // bytes of dynamic LDS the scene tables may take
+static uint32_t emitter_lds_layout(const dev::DevScene& sc, uint32_t base, uint32_t& etri, uint32_t& ecdf) {
+    auto up4 = [](uint32_t w) { return (w + 3u) & ~3u; };
+    etri = base;
+    ecdf = up4(etri + 20u * static_cast<uint32_t>(sc.n_etri));
+    return up4(ecdf + static_cast<uint32_t>(sc.n_ecdf));
 }
 
 // Host arrays in, device run, host arrays out (the per-function entry points): a device array
@@ -745,7 +760,7 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     c->sc.nshapes = static_cast<int32_t>(L.shape_emitter.size());
     {  // LDS table layout (bdpt_device.hpp scene_tables_to_lds), 16-byte aligned parts
         auto up4 = [](uint32_t w) { return (w + 3u) & ~3u; };
-        constexpr uint32_t kBudget = 24u * 1024u;
+        constexpr uint32_t kBudget = kLdsBudget;
         const uint32_t nb = static_cast<uint32_t>(L.bsdfs.size() * sizeof(BsdfRecord) / 4);
         const uint32_t ne = static_cast<uint32_t>(L.emitters.size() * sizeof(EmitterRecord) / 4);
         // BSDF records in LDS unless they do not fit with the emitter records (then
@@ -768,8 +783,8 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
         c->sc.n_etri = static_cast<int32_t>(L.emit_tri.size() / 5);
         c->sc.n_ecdf = static_cast<int32_t>(L.emit_cdf.size());
         c->lds_words_base = c->sc.lds_words;
-        const uint32_t etri = c->sc.lds_words, ecdf = up4(etri + 20u * static_cast<uint32_t>(c->sc.n_etri));
-        const uint32_t with = up4(ecdf + static_cast<uint32_t>(c->sc.n_ecdf));
+        uint32_t etri, ecdf;
+        const uint32_t with = emitter_lds_layout(c->sc, c->lds_words_base, etri, ecdf);
         auto blocks = [&](uint32_t words) {
             const size_t bytes = 4 * static_cast<size_t>(words);
             return (hbm ? frame_build_hbm : frame_build).blocks_per_cu(bytes);
@@ -1850,6 +1865,52 @@ int bdpt_splat_to_image_plane(bdpt_ctx* c, const bdpt_frame_params* p, int64_t n
     if ((rc = kat_in(c, dp, pts, 12 * N)) || (rc = kat_in<int32_t>(c, dxy, nullptr, 8 * N))) return rc;
     HIP_TRY(launch_splat_kat(make_frame(p), n, dp, dxy, c->stream));
     HIP_TRY(hipMemcpyAsync(xy, dxy, 8 * N, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = end_use(c, c->stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+int bdpt_debug_sampling(bdpt_ctx* c, const bdpt_frame_params* p, int32_t build, int32_t fn, int32_t placement,
+                        int64_t n, const void* in, void* out, int32_t* ctx_placement) {
+    static const int kIn[] = {1, 2, 2, 2, 9, 12, 2, 4, 3}, kOut[] = {1, 3, 2, 3, 4, 1, 1, 10, 3};
+    if (!c || n < 0 || (n > 0 && (!in || !out))) return fail(BDPT_ERR_INVALID, "bad argument");
+    if (ctx_placement) *ctx_placement = c->sc.lds_etri_off != dev::kNoLds ? BDPT_EMITTERS_LDS : BDPT_EMITTERS_HBM;
+    if (build != BDPT_KAT_EXACT && build != BDPT_KAT_FAST)
+        return fail(BDPT_ERR_INVALID, "bdpt_debug_sampling: build must be BDPT_KAT_EXACT or BDPT_KAT_FAST");
+    if (fn < BDPT_SAMPLING_CANONICAL || fn > BDPT_SAMPLING_CAMERA) return fail(BDPT_ERR_INVALID, "bad function code");
+    if (placement < BDPT_EMITTERS_CTX || placement > BDPT_EMITTERS_LDS) return fail(BDPT_ERR_INVALID, "bad placement");
+    dev::DevFrame fr{};
+    if (fn == BDPT_SAMPLING_CAMERA) {
+        if (int rc = check_frame_size(p)) return rc;
+        if (int rc = check_row_shard(p)) return rc;
+        fr = make_frame(p);
+    }
+    dev::DevScene sc = c->sc;
+    if (placement == BDPT_EMITTERS_HBM) {
+        sc.lds_etri_off = sc.lds_ecdf_off = dev::kNoLds;
+        sc.lds_words = c->lds_words_base;
+    } else if (placement == BDPT_EMITTERS_LDS) {
+        const uint32_t with = emitter_lds_layout(sc, c->lds_words_base, sc.lds_etri_off, sc.lds_ecdf_off);
+        if (with * 4ull > kLdsBudget)
+            return fail(BDPT_ERR_UNSUPPORTED, "bdpt_debug_sampling: the emitter faces and CDFs (" +
+                                                  std::to_string(with * 4ull) + " bytes with the other tables) "
+                                                  "exceed the 24 KiB LDS budget");
+        sc.lds_words = with;
+    }
+    const uint32_t* win = static_cast<const uint32_t*>(in);
+    if (fn == BDPT_SAMPLING_CDF)
+        for (int64_t i = 0; i < n; i++)
+            if (win[2 * i] >= static_cast<uint32_t>(c->sc.nemit)) return fail(BDPT_ERR_INVALID, "emitter index out of range");
+    if (n == 0) return BDPT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = begin_use(c, c->stream))) return rc;
+    DevBuf<uint32_t> din, dout;
+    const size_t N = static_cast<size_t>(n), bi = 4 * N * kIn[fn], bo = 4 * N * kOut[fn];
+    if ((rc = kat_in(c, din, win, bi)) || (rc = kat_in<uint32_t>(c, dout, nullptr, bo))) return rc;
+    const auto launch = build == BDPT_KAT_FAST ? launch_sampling_kat_fw : launch_sampling_kat;
+    HIP_TRY(launch(sc, fr, fn, kIn[fn], kOut[fn], n, din, dout, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, dout, bo, hipMemcpyDeviceToHost, c->stream));
     if ((rc = end_use(c, c->stream))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BDPT_OK;

@@ -496,7 +496,12 @@ __device__ BDPT_NOINLINE uint32_t mt_u32_long(LazyMT& r) {
 #endif  // BDPT_RING_AHEAD
 #endif  // BDPT_DEEP_RNG
 
-// generate_canonical<float, 24> (libstdc++ 11 random.tcc:3348-3380).
+// generate_canonical<float, 24> (libstdc++ 11 random.tcc:3348-3380) of one 32-bit draw: the
+// draws >= 0xFFFFFF80 round to 1.0f in the division and are moved to the float below 1.
+__device__ __forceinline__ float canonical_f32(uint32_t u) {
+    const float f = static_cast<float>(u) / 4294967296.0f;
+    return f >= 1.0f ? 0x1.fffffep-1f : f;
+}
 __device__ __forceinline__ float next1(LazyMT& r) {
 #if BDPT_SAMPLER_STATE
     const uint32_t u = mt_state_u32();
@@ -506,8 +511,7 @@ __device__ __forceinline__ float next1(LazyMT& r) {
 #else
     const uint32_t u = mt_next_u32(r);
 #endif
-    float f = static_cast<float>(u) / 4294967296.0f;
-    return f >= 1.0f ? 0x1.fffffep-1f : f;
+    return canonical_f32(u);
 }
 struct F2 {
     float x, y;

@@ -172,7 +172,8 @@ __device__ __forceinline__ void splat_pixel(const CameraConstants& c, f3 p, int&
 }
 
 // Camera ray of Renderer::render (renderer.cpp:162-192); 2 jitter draws if spp > 1.
-__device__ __forceinline__ f3 camera_dir(const DevFrame& fr, int pixel, LazyMT& rng) {
+template <class Rng>
+__device__ __forceinline__ f3 camera_dir(const DevFrame& fr, int pixel, Rng& rng) {
     const CameraConstants& c = fr.cam;
     const int j = pixel % fr.W, i = pixel / fr.W;
     const float y = (1.f - (static_cast<float>(i) + 0.5f) * c.invH) * 2.f - 1.f;

@@ -618,6 +618,51 @@ int bdpt_intersect_from(bdpt_ctx* ctx, int64_t n, const float* rays, const float
 int bdpt_splat_to_image_plane(bdpt_ctx* ctx, const bdpt_frame_params* params, int64_t n, const float* p,
                               int32_t* xy);
 
+/* The sampling side of the path, per function: n elements of host words in (32-bit: floats,
+ * ints and raw generator outputs), host words out, through the frame kernels' own device
+ * functions. A draw enters as the std::mt19937 output word it is converted from
+ * (std::generate_canonical<float, 24>: word / 2^32 in float, moved to the float below 1 where
+ * that rounds to 1, i.e. for words >= 0xFFFFFF80). fn, words in -> words out per element:
+ *   BDPT_SAMPLING_CANONICAL    word -> Sampler::next() (math.h:70)
+ *   BDPT_SAMPLING_HEMISPHERE   u[2] -> Warp::squareToUniformHemisphere (math.h:136-144), d[3]
+ *   BDPT_SAMPLING_TRIANGLE     u[2] -> Warp::squareToUniformTriangle (math.h:229-234), uv[2]
+ *   BDPT_SAMPLING_SPHERE       u[2] -> Warp::squareToUniformSphere (math.h:119-127), d[3]
+ *   BDPT_SAMPLING_SOLID_ANGLE  u[2], p[3], center[3], radius -> sampleSphereBySolidAngle
+ *                              (direct.h:111-141): wi[3], pdf
+ *   BDPT_SAMPLING_RAY_SPHERE   ray[8] (o d min_t max_t), center[3], radius -> raySphereIntersect's
+ *                              result (direct.h:37-69), int
+ *   BDPT_SAMPLING_CDF          emitter (int), u -> Distribution1D::sample of that emitter's face
+ *                              areas (math.h:107-111), int
+ *   BDPT_SAMPLING_EMITTER      4 words -> selectEmitter + sampleEmitterPosition
+ *                              (integrator.cpp:46-51, :73-100): id (int), emitter pdf, face (int:
+ *                              BDPT_SAMPLING_CDF of word 1), pos[3], n[3], position pdf
+ *   BDPT_SAMPLING_CAMERA       pixel (int), 2 words -> the camera ray's direction
+ *                              (renderer.cpp:165-195) for the camera, width, height and spp of
+ *                              params (the words are read when spp > 1), d[3]
+ * params is read by BDPT_SAMPLING_CAMERA only and may be NULL otherwise. build is
+ * BDPT_KAT_EXACT (every output has the reference's bits) or BDPT_KAT_FAST (the default frame
+ * kernels' weight arithmetic: the position pdf is the 1-ulp reciprocal of the area, all else
+ * the same bits). placement picks where BDPT_SAMPLING_CDF and _EMITTER read the emitter faces
+ * and CDFs, which are two bodies of code: BDPT_EMITTERS_CTX as the context's frames do,
+ * BDPT_EMITTERS_HBM from global memory, BDPT_EMITTERS_LDS from a copy in LDS
+ * (BDPT_ERR_UNSUPPORTED when they do not fit the 24 KiB the scene tables may take).
+ * *ctx_placement (may be NULL) receives BDPT_EMITTERS_HBM or _LDS: what the context's frames
+ * run (LDS when the copy fits and costs no resident block). Synchronous. */
+#define BDPT_SAMPLING_CANONICAL 0
+#define BDPT_SAMPLING_HEMISPHERE 1
+#define BDPT_SAMPLING_TRIANGLE 2
+#define BDPT_SAMPLING_SPHERE 3
+#define BDPT_SAMPLING_SOLID_ANGLE 4
+#define BDPT_SAMPLING_RAY_SPHERE 5
+#define BDPT_SAMPLING_CDF 6
+#define BDPT_SAMPLING_EMITTER 7
+#define BDPT_SAMPLING_CAMERA 8
+#define BDPT_EMITTERS_CTX 0
+#define BDPT_EMITTERS_HBM 1
+#define BDPT_EMITTERS_LDS 2
+int bdpt_debug_sampling(bdpt_ctx* ctx, const bdpt_frame_params* params, int32_t build, int32_t fn,
+                        int32_t placement, int64_t n, const void* in, void* out, int32_t* ctx_placement);
+
 /* ---- diagnostics ---- */
 /* GlassBSDF::FresnelDielectric (glass.h:40-53): in = n x (eta_i, eta_t, cos_i, cos_t). */
 int bdpt_debug_fresnel(int32_t device, int64_t n, const float* in, float* out);

@@ -383,6 +383,32 @@ inline float i2f(int i) {
     return x;
 }
 
+// The inverse of std::mt19937's output tempering (y ^= y >> 11; y ^= (y << 7) & 0x9d2c5680;
+// y ^= (y << 15) & 0xefc60000; y ^= y >> 18).
+inline uint32_t untemper(uint32_t y) {
+    y ^= y >> 18;
+    y ^= (y << 15) & 0xefc60000u;
+    uint32_t t = y;
+    for (int i = 0; i < 4; i++) t = y ^ ((t << 7) & 0x9d2c5680u);
+    y = t;
+    t = y;
+    for (int i = 0; i < 2; i++) t = y ^ (t >> 11);
+    return t;
+}
+
+// A Sampler whose next k <= 624 outputs are exactly the words w (as floats' bits): state
+// word i is untemper(w[i]) and the position 0, so no twist falls in between; loaded
+// through operator>> as cmdSampleState loads its states.
+Sampler samplerOfWords(const float* w, int k) {
+    std::ostringstream os;
+    for (int i = 0; i < 624; i++) os << (i < k ? untemper((uint32_t)f2i(w[i])) : 0u) << ' ';
+    os << 0;
+    Sampler sampler(0);
+    std::istringstream is(os.str());
+    is >> sampler.g;
+    return sampler;
+}
+
 // Per-function known-answer outputs of the reference's own functions on
 // records read from a float32 file (test fixtures, tests/golden/make_kat_goldens.py):
 //   bsdf      in (mat, wo[3], wi[3], u[2])  out (eval[3], pdf, sample f[3], wi[3], pdf, type, null)
@@ -393,6 +419,16 @@ inline float i2f(int i) {
 //             wo[3], -1, occluded)   AcceleratorBVH::intersect (accel.h:125-172) and the any-hit
 //             query visibilityQuery makes (bvh.h:259-352, occlusion = true)
 //   splat     in p[3]  out (x, y) as int bits   BDPTIntegrator::splatToImagePlane (bdpt.h:485-496)
+// The sampling side; a draw enters as the std::mt19937 output word it comes from (samplerOfWords):
+//   canonical in word  out Sampler::next() (math.h:70)
+//   warp      in u[2]  out (hemisphere[3], its pdf, triangle[2], sphere[3], its pdf)
+//             Warp::squareToUniformHemisphere / Triangle / Sphere and the pdfs (math.h:119-151, :229-234)
+//   emitter   in 4 words  out (id, emitterPdf, primID as int bits, pos[3], n[3], areaPdf)
+//             selectEmitter(sampler.next(), pdf), then sampleEmitterPosition (integrator.cpp:46-51, :73-100)
+//   camera    in (pixel, 2 words, spp)  out the ray direction[3]   cameraRay above, for the command line's W H
+//   sphere    in (u[2], p[3], center[3], radius, ray[8])  out (pos[3], ne[3], wiW[3], pdf of
+//             sampleSphereByArea, wiW[3], pdf of sampleSphereBySolidAngle, hit, t of
+//             raySphereIntersect(ray, center, radius))   direct.h:37-69, :96-141
 int cmdKat(int argc, char** argv) {
     if (argc < 8) return 2;
     const std::string toml = argv[2], kind = argv[5];
@@ -471,6 +507,57 @@ int cmdKat(int argc, char** argv) {
             bi->splatToImagePlane(v3f(in[r], in[r + 1], in[r + 2]), x, y);
             out.push_back(i2f(x));
             out.push_back(i2f(y));
+        }
+    } else if (kind == "canonical") {
+        for (size_t r = 0; r < in.size(); r++) {
+            Sampler sampler = samplerOfWords(&in[r], 1);
+            out.push_back(sampler.next());
+        }
+    } else if (kind == "warp") {
+        for (size_t r = 0; r + 2 <= in.size(); r += 2) {
+            const p2f u(in[r], in[r + 1]);
+            const v3f h = Warp::squareToUniformHemisphere(u);
+            const v2f t = Warp::squareToUniformTriangle(u);
+            const v3f sp = Warp::squareToUniformSphere(u);
+            const float o[10] = {h.x, h.y, h.z, Warp::squareToUniformHemispherePdf(h), t.x, t.y, sp.x, sp.y, sp.z,
+                                 Warp::squareToUniformSpherePdf()};
+            out.insert(out.end(), o, o + 10);
+        }
+    } else if (kind == "emitter") {
+        for (size_t r = 0; r + 4 <= in.size(); r += 4) {
+            Sampler sampler = samplerOfWords(&in[r], 4);
+            float emitterPdf = 0.f, areaPdf = 0.f;
+            const size_t id = s.integ->selectEmitter(sampler.next(), emitterPdf);
+            v3f n(0.f), pos(0.f);
+            size_t primID = 0;
+            s.integ->sampleEmitterPosition(sampler, s.integ->getEmitterByID((int)id), n, pos, areaPdf, &primID);
+            const float o[10] = {i2f((int)id), emitterPdf, i2f((int)primID), pos.x, pos.y, pos.z, n.x, n.y, n.z, areaPdf};
+            out.insert(out.end(), o, o + 10);
+        }
+    } else if (kind == "camera") {
+        const Cam cam = makeCam(s.cfg, W, H);
+        for (size_t r = 0; r + 4 <= in.size(); r += 4) {
+            Sampler sampler = samplerOfWords(&in[r + 1], 2);
+            const Ray ray = cameraRay(s.cfg, cam, W, f2i(in[r + 3]), f2i(in[r]), sampler);
+            out.push_back(ray.d.x), out.push_back(ray.d.y), out.push_back(ray.d.z);
+        }
+    } else if (kind == "sphere") {
+        const DirectIntegrator di(sc);
+        for (size_t r = 0; r + 17 <= in.size(); r += 17) {
+            const p2f u(in[r], in[r + 1]);
+            const p3f p(in[r + 2], in[r + 3], in[r + 4]);
+            const v3f c(in[r + 5], in[r + 6], in[r + 7]);
+            const float rad = in[r + 8];
+            const Ray ray(v3f(in[r + 9], in[r + 10], in[r + 11]), v3f(in[r + 12], in[r + 13], in[r + 14]), in[r + 15],
+                          in[r + 16]);
+            v3f pos(0.f), ne(0.f), wa(0.f), ws(0.f);
+            float pa = 0.f, ps = 0.f, t = 0.f;
+            di.sampleSphereByArea(u, p, c, rad, pos, ne, wa, pa);
+            di.sampleSphereBySolidAngle(u, p, c, rad, ws, ps);
+            const bool hit = tr_driver_raySphereIntersect(ray, c, rad, t);
+            const float o[16] = {pos.x, pos.y, pos.z, ne.x, ne.y, ne.z, wa.x, wa.y, wa.z, pa, ws.x, ws.y, ws.z, ps,
+                                 hit ? 1.f : 0.f, hit ? t : 0.f};
+            out.insert(out.end(), o, o + 16);
         }
     } else {
         fprintf(stderr, "unknown kat kind\n");

@@ -52,6 +52,9 @@ FRAMEBUFFERS = {
     "G12_hardlight_pt_64x64_spp16": ("hardlight", 64, 64, 16, 2, 1, "pt"),
     # a Phong lobe with Ns in the thousands (tests/test_gpu_kat_connection.py)
     "G13_hardlight_phong_ns4000_32x32_spp4": ("hardlight_phong_ns4000", 32, 32, 4, 5, 1),
+    # five emitters, one with 33 faces over 10^7 : 1 in area, one with a zero-area face
+    # (tests/test_gpu_kat_sampling.py)
+    "G14_emit_edges_32x32_spp4": ("emit_edges", 32, 32, 4, 5, 1),
 }
 
 # The reference's Russian-roulette branch (NO_RR = 0): name: (scene, W, H, spp, rrDepth, row_stride)
