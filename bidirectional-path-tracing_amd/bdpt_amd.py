@@ -13,6 +13,8 @@ Mirrors the reference's plugin surface for the BDPT path
     .rgb                               Integrator::rgb      (W x H x 3 float32, accumulated)
     .render_aov(...) / .aov            first-hit albedo, normal, depth, coverage (bdpt_render_aov; no counterpart)
     .denoise(samples_done=...)         edge-avoiding a-trous filter of a low-spp frame (bdpt_denoise; no counterpart)
+    .render_layers(n) / .compose_layers(layers, mask)
+                                       the BDPT frame split by path length (bdpt_render_layers; no counterpart)
   Sampler(seed)                        Sampler              src/core/math.h:63-76 (seed + draw count)
   Ray(o, d, min_t, max_t)              Ray                  src/core/core.h:117-122
   load_toml(path) -> SceneConfig       loadTOML             src/main.cpp:22-116
@@ -209,7 +211,7 @@ class _Stats(ctypes.Structure):
 
 # Sources that make up the frame kernels' code objects: their hash stamps the
 # profiles (PMC passes) so bench.py only reuses a measurement of the same kernel.
-KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
+KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_kernels_layers.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
                   "csrc/powf_restated.inc", "csrc/bdpt_types.h", "Makefile")
 
 
@@ -302,6 +304,9 @@ def lib():
         L.bdpt_render_aov_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), vp]
         L.bdpt_denoise.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.POINTER(_DenoiseParams), vp]
         L.bdpt_denoise_host.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.POINTER(_DenoiseParams)]
+        L.bdpt_render_layers.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp, vp]
+        L.bdpt_render_layers_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp]
+        L.bdpt_layers_compose.argtypes = [vp, vp, i32, i32, i32, ctypes.c_uint64, vp, vp]
         L.bdpt_synchronize.argtypes = [vp]
         L.bdpt_config_load_toml.argtypes = [ctypes.c_char_p, ctypes.POINTER(_Config)]
         L.bdpt_render_path.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_PathParams), vp, vp]
@@ -734,6 +739,23 @@ def camera_constants(cam: Camera, width: int, height: int) -> np.ndarray:
     return out
 
 
+def layers_longest_path(rr_depth: int, strategy: int = STRATEGY_BDPT) -> int:
+    """The longest full path (camera -> ... -> emitter, in edges) a frame without Russian roulette
+    holds, from the subpath loops' `depth < rrDepth` (bdpt.h:68, :188): both subpaths have vertices at
+    depths 1 .. rr_depth - 1. Layer k - 1 of render_layers is the last that can be non-zero; 0: the
+    frame is black.
+      BDPT           connectVertices joins two deepest vertices: (D - 1) + (D - 1) + 1 = 2 D - 1 (0 at D = 1)
+      PATH_TRACING   connectToLight at the deepest eye vertex: (D - 1) + 1 = D                  (0 at D = 1)
+      LIGHT_TRACING  connectToCamera at the deepest light vertex: D; the camera ray's own emitter hit
+                     (1 edge) is added whatever D is: max(1, D)"""
+    D = int(rr_depth)
+    if strategy == STRATEGY_LIGHT_TRACING:
+        return max(1, D)
+    if D <= 1:
+        return 0
+    return D if strategy == STRATEGY_PATH_TRACING else 2 * D - 1
+
+
 class BDPTIntegrator:
     """GPU BDPT integrator with the reference's Integrator interface."""
 
@@ -972,6 +994,73 @@ class BDPTIntegrator:
         w = window.c() if window is not None else None
         _check(lib().bdpt_render_aov(self._h, ctypes.byref(p), w and ctypes.byref(w), ctypes.c_void_p(aov_ptr),
                                      ctypes.c_void_p(stream_ptr)))
+
+    def render_layers(self, n_layers: int, window: SampleWindow | None = None, row_offset: int = 0,
+                      row_stride: int = 1, flags: int = 0) -> np.ndarray:
+        """bdpt_render_layers_host: the BDPT frame split by path length, a new (n_layers, H, W, 3)
+        array. Layer l holds the contributions of paths camera -> ... -> emitter with l + 1 edges
+        (0: emitters seen directly, 1: direct light, ...), the last layer everything longer; the
+        layers sum to render_frame()'s frame."""
+        H, W = self.config.height, self.config.width
+        p = self.params(row_offset, row_stride, flags)
+        w = window.c() if window is not None else None
+        n_layers = int(n_layers)
+        # a count or size the library refuses (before it touches the buffer) is not allocated here
+        ok = 1 <= n_layers <= 64 and n_layers * W * H < 1 << 30
+        out = np.zeros((n_layers, H, W, 3) if ok else (1,), np.float32)
+        _check(lib().bdpt_render_layers_host(self._h, ctypes.byref(p), w and ctypes.byref(w), n_layers,
+                                             out.ctypes.data))
+        return out
+
+    def render_layers_device(self, n_layers: int, fb_ptr: int, stream_ptr: int = 0,
+                             window: SampleWindow | None = None, row_offset: int = 0, row_stride: int = 1) -> None:
+        """bdpt_render_layers: asynchronous, ADDED to a device buffer of n_layers * H * W * 3 floats."""
+        p = self.params(row_offset, row_stride, 0)
+        w = window.c() if window is not None else None
+        _check(lib().bdpt_render_layers(self._h, ctypes.byref(p), w and ctypes.byref(w), int(n_layers),
+                                        ctypes.c_void_p(fb_ptr), ctypes.c_void_p(stream_ptr)))
+
+    @staticmethod
+    def layer_mask(mask_or_iterable) -> int:
+        """A 64-bit layer mask from an int (taken as is) or an iterable of layer indices."""
+        if isinstance(mask_or_iterable, (int, np.integer)):
+            m = int(mask_or_iterable)
+            if m < 0 or m >= 1 << 64:
+                raise ValueError("layer mask: an int mask must fit 64 bits")
+            return m
+        m = 0
+        for l in mask_or_iterable:
+            if not 0 <= int(l) < 64:
+                raise ValueError(f"layer mask: layer {l} is outside 0..63")
+            m |= 1 << int(l)
+        return m
+
+    def compose_layers(self, layers, mask_or_iterable) -> np.ndarray:
+        """bdpt_layers_compose on the device: the (H, W, 3) float32 sum of the layers the mask
+        names (an int bit mask or an iterable of layer indices), added in ascending layer order.
+        The layers go to the device and the sum comes back (a viewer that keeps the planes on
+        the device calls compose_layers_device)."""
+        import torch
+
+        a = np.ascontiguousarray(layers, np.float32)
+        if a.ndim != 4 or a.shape[3] != 3:
+            raise BdptError(f"compose_layers: layers must be (n_layers, H, W, 3), got {a.shape}")
+        n, H, W = a.shape[:3]
+        mask = self.layer_mask(mask_or_iterable)
+        dev = torch.device("cuda", self.device)
+        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+        d_out = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.compose_layers_device(d_in.data_ptr(), n, W, H, mask, d_out.data_ptr())
+        self.synchronize()
+        return d_out.cpu().numpy()
+
+    def compose_layers_device(self, layers_ptr: int, n_layers: int, width: int, height: int, mask: int, out_ptr: int,
+                              stream_ptr: int = 0) -> None:
+        """bdpt_layers_compose: asynchronous, on device buffers."""
+        _check(lib().bdpt_layers_compose(self._h, ctypes.c_void_p(layers_ptr), int(n_layers), int(width), int(height),
+                                         ctypes.c_uint64(mask), ctypes.c_void_p(out_ptr),
+                                         ctypes.c_void_p(stream_ptr)))
 
     def denoise(self, rgb=None, aov=None, samples_done: int | None = None, **params) -> np.ndarray:
         """bdpt_denoise_host of rgb (default self.rgb) guided by aov (default self.aov): a new

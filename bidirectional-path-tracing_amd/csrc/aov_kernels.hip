@@ -167,7 +167,32 @@ __global__ __launch_bounds__(kDnX* kDnY) void denoise_iter_kernel(int W, int H, 
     }
 }
 
+// ------------------------------------------------------------ path-length layers
+// out[i] = the sum over the layers l in `mask` of layers[l * n + i] (n = W * H * 3 floats per
+// plane, bdpt_render_layers), float32 additions in ascending layer order starting from the
+// lowest layer's value: no atomics, so the same bits every run and the bits of that sequential
+// sum on the host. Grid-stride over the floats; a wave reads 256 consecutive bytes of each
+// plane. mask != 0 with no bit at or above the plane count (bdpt_layers_compose checks).
+__global__ __launch_bounds__(256) void layers_compose_kernel(const float* __restrict__ layers, size_t n, uint64_t mask,
+                                                             float* __restrict__ out) {
+    const int first = __ffsll(static_cast<unsigned long long>(mask)) - 1;
+    const uint64_t rest = mask & (mask - 1);
+    for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * 256) {
+        float acc = gld1(layers + static_cast<size_t>(first) * n + i);
+        for (uint64_t m = rest; m; m &= m - 1)  // (wave-uniform)
+            acc += gld1(layers + static_cast<size_t>(__ffsll(static_cast<unsigned long long>(m)) - 1) * n + i);
+        gst1(out + i, acc);
+    }
+}
+
 }  // namespace dev
+
+hipError_t launch_layers_compose(const float* layers, size_t n, uint64_t mask, float* out, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((n + 255) / 256, 4096));
+    hipLaunchKernelGGL(dev::layers_compose_kernel, dim3(blocks), dim3(256), 0, st, layers, n, mask, out);
+    return hipGetLastError();
+}
 
 // tiles of the shard; the grid never exceeds the lane slots the overflow columns serve
 hipError_t launch_aov(const dev::DevScene& sc, const dev::DevFrame& fr, const void* mats, float* aov, uint2* gstack,

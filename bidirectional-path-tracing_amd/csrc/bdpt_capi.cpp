@@ -22,7 +22,7 @@
 namespace bdpt {
 // The builds of the BDPT frame kernel (bdpt_kernels_<x>.hip; FrameBuild: bdpt_device.hpp)
 extern FrameBuild frame_build, frame_build_tex, frame_build_rr, frame_build_rrc, frame_build_deep,
-    frame_build_hbm, frame_build_split, frame_build_ng;
+    frame_build_hbm, frame_build_split, frame_build_ng, frame_build_layers;
 // sample_state.hip: the single-sample kernels (the caller's std::mt19937 state at sc.mt_ring)
 hipError_t launch_sample(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf, uint2* gstack,
                          const dev::Ray& ray, float* out, hipStream_t stream);
@@ -67,6 +67,8 @@ hipError_t launch_denoise_prepare(int W, int H, const float* color, const float*
 hipError_t launch_denoise_scale(size_t n, const float* color, float norm, float* out, hipStream_t st);
 hipError_t launch_denoise_iter(int W, int H, int step, float inv_c, float inv_n, float sigma_z, int demodulate,
                                const void* guide, const void* src, void* dst, float* out, bool last, hipStream_t st);
+// aov_kernels.hip: a masked sum of path-length layers (planes of n floats)
+hipError_t launch_layers_compose(const float* layers, size_t n, uint64_t mask, float* out, hipStream_t st);
 }  // namespace bdpt
 
 using namespace bdpt;
@@ -1005,18 +1007,45 @@ static const FrameBuild& pick_frame_build(const bdpt_ctx* c, const bdpt_frame_pa
     return frame_build;
 }
 
-// bdpt_render and the BDPT form of bdpt_render_window (w null: every sample).
+// Path-length layers (bdpt_render_layers): what the one build that writes
+// them (bdpt_kernels_layers.hip) serves. Called after check_params, before any launch.
+constexpr int kMaxLayers = 64;  // a layer mask is one 64-bit word (bdpt_layers_compose)
+static int check_layers(const bdpt_ctx* c, const bdpt_frame_params* p, int n_layers) {
+    if (n_layers < 1 || n_layers > kMaxLayers)
+        return fail(BDPT_ERR_INVALID, "bdpt_render_layers: n_layers must be in [1, 64]");
+    // a contribution's plane and pixel travel as one index in the task record's 30-bit pixel field
+    if (static_cast<int64_t>(n_layers) * p->width * p->height >= (int64_t{1} << 30))
+        return fail(BDPT_ERR_INVALID, "bdpt_render_layers: n_layers * W * H must be below 2^30 (the shadow-ray task "
+                                      "record's pixel field)");
+    const char* what = p->flags != 0                              ? "with flags (a counting pass or full traversal)"
+                       : p->russian_roulette != BDPT_RR_NONE      ? "with Russian roulette"
+                       : p->rr_depth > kLazyRrDepth               ? "with rr_depth > 28"
+                       : c->textured                              ? "for a scene with bitmap textures"
+                       : c->sc.lds_bsdf_off == dev::kNoLds        ? "with the BSDF records in HBM (too many materials "
+                                                                    "for the LDS table)"
+                                                                  : nullptr;
+    if (what) return fail(BDPT_ERR_UNSUPPORTED, std::string("path-length layers are not built ") + what);
+    return BDPT_OK;
+}
+
+// bdpt_render and the BDPT form of bdpt_render_window (w null: every sample); n_layers other
+// than kNoLayers: bdpt_render_layers (fb is n_layers planes, the layers build; check_layers
+// refuses a bad count).
+constexpr int kNoLayers = -1;
 static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* fb,
-                       void* hip_stream) {
+                       void* hip_stream, int n_layers = kNoLayers) {
     if (!c || !fb) return fail(BDPT_ERR_INVALID, "null argument");
     int rc = check_params(p);
     if (rc) return rc;
     if ((rc = check_window(p, w))) return rc;
+    const bool layered = n_layers != kNoLayers;
+    if (layered && (rc = check_layers(c, p, n_layers))) return rc;
     if ((rc = textured_frame_check(c, p))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     dev::DevFrame fr = make_frame(p, w);
     fr.capped = c->capped;
+    fr.n_layers = layered ? n_layers : 0;
     if (!fr.rr_mode && fr.total_samples > 0 && (rc = ensure_tasks(c))) return rc;
     fr.tasks = c->tasks;
     fr.task_cap = c->task_cap;
@@ -1073,7 +1102,7 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
     if ((rc = begin_timed(c, st))) return rc;
     int64_t launches = 0;
     if (fr.total_samples > 0) {
-        const FrameBuild& b = pick_frame_build(c, p);
+        const FrameBuild& b = layered ? frame_build_layers : pick_frame_build(c, p);
         c->last_kernel_glossy = 1;  // (until the launches below have succeeded)
         // Never more resident blocks than the slots allocated. c->grid is the default build's
         // blocks_per_cu of these LDS bytes (the HBM build's on an HBM table; bdpt_ctx_create),
@@ -1111,6 +1140,29 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
 
 int bdpt_render(bdpt_ctx* c, const bdpt_frame_params* p, float* fb, void* hip_stream) {
     return render_bdpt(c, p, nullptr, fb, hip_stream);
+}
+
+int bdpt_render_layers(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_layers,
+                       float* fb_layers, void* hip_stream) {
+    return render_bdpt(c, p, w, fb_layers, hip_stream, n_layers == kNoLayers ? 0 : n_layers);  // (both: a bad count)
+}
+
+int bdpt_layers_compose(bdpt_ctx* c, const float* fb_layers, int32_t n_layers, int32_t width, int32_t height,
+                        uint64_t mask, float* out, void* hip_stream) {
+    if (!c || !fb_layers || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    if (n_layers < 1 || n_layers > kMaxLayers)
+        return fail(BDPT_ERR_INVALID, "bdpt_layers_compose: n_layers must be in [1, 64]");
+    if (width <= 0 || height <= 0 || static_cast<int64_t>(n_layers) * width * height >= (int64_t{1} << 30))
+        return fail(BDPT_ERR_INVALID, "bdpt_layers_compose: width/height must be > 0 and n_layers * W * H below 2^30");
+    if (mask == 0) return fail(BDPT_ERR_INVALID, "bdpt_layers_compose: empty layer mask");
+    if (n_layers < 64 && (mask >> n_layers) != 0)
+        return fail(BDPT_ERR_INVALID, "bdpt_layers_compose: the mask has bits at or above n_layers");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if (int rc = begin_use(c, st)) return rc;
+    if (int rc = begin_timed(c, st)) return rc;
+    HIP_TRY(launch_layers_compose(fb_layers, static_cast<size_t>(width) * height * 3, mask, out, st));
+    return end_timed(c, st, 0, 1);
 }
 
 // PathTracerIntegrator (path.h) on the same substrate: pt_kernels.hip.
@@ -1480,13 +1532,16 @@ int bdpt_synchronize(bdpt_ctx* c) {
     return BDPT_OK;
 }
 
-static int render_bdpt_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* fb_host) {
+static int render_bdpt_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* fb_host,
+                            int n_layers = kNoLayers) {
     if (!c || !fb_host) return fail(BDPT_ERR_INVALID, "null argument");
     int rc = check_params(p);
     if (rc) return rc;
     if ((rc = check_window(p, w))) return rc;
-    if ((rc = stage_host(c, fb_host, static_cast<size_t>(p->width) * p->height * 3,
-                         [&](float* fb) { return render_bdpt(c, p, w, fb, c->stream); })))
+    const bool layered = n_layers != kNoLayers;
+    if (layered && (rc = check_layers(c, p, n_layers))) return rc;  // before the planes are staged
+    if ((rc = stage_host(c, fb_host, static_cast<size_t>(p->width) * p->height * 3 * (layered ? n_layers : 1),
+                         [&](float* fb) { return render_bdpt(c, p, w, fb, c->stream, n_layers); })))
         return rc;
     {
         bdpt_stats st;
@@ -1505,6 +1560,11 @@ static int render_bdpt_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_
 
 int bdpt_render_host(bdpt_ctx* c, const bdpt_frame_params* p, float* fb_host) {
     return render_bdpt_host(c, p, nullptr, fb_host);
+}
+
+int bdpt_render_layers_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_layers,
+                            float* fb_layers_host) {
+    return render_bdpt_host(c, p, w, fb_layers_host, n_layers == kNoLayers ? 0 : n_layers);  // (both: a bad count)
 }
 
 // Sample windows: the three integrators' frame entries with a window (null: the whole

@@ -209,6 +209,10 @@ struct DevFrame {
     // i * win_stride, 0 <= i < win_count, are rendered (the whole frame: 0, 1, spp); seeds,
     // inv_spp and camera_dir's spp == 1 rule keep the frame's full spp
     int32_t win_first, win_stride, win_count;
+    // path-length layers (bdpt_render_layers, the bdpt_kernels_layers.hip build): the framebuffer
+    // is n_layers consecutive W x H x 3 planes and a contribution of a path with k edges goes to
+    // plane min(k - 1, n_layers - 1). 0 and unread in every other build.
+    int32_t n_layers;
 };
 enum : uint32_t { kParkOn = 1u, kParkResume = 2u };
 enum : uint32_t { kSchedNoCoopGroups = 1u };

@@ -55,6 +55,38 @@ __device__ __forceinline__ float rr_probability(const DevFrame& fr, int depth, f
     return dot(tp, mk(0.212671f, 0.715160f, 0.072169f)) < 0.01f ? 0.5f : 1.f;  // getLuminance (math.h:56-58)
 }
 
+// Path-length layers (BDPT_LAYERS 1: bdpt_kernels_layers.hip). A contribution
+// belongs to a full path camera -> ... -> emitter of k edges; the framebuffer is
+// DevFrame::n_layers consecutive W x H x 3 planes and the contribution's destination is
+// "pixel" plane * W * H + pixel with plane = min(k - 1, n_layers - 1). That index travels
+// wherever a pixel does (the task record's 30-bit field, pend_px, eye_add / splat_add), so
+// tasks, helpers and the ring-full fallback need nothing else. k at the four sites, from the
+// subpath depths (the vertex's edges from its subpath's start):
+//   eye walk hits an emitter (s = 0)   k = depth_eye
+//   connectToLight (s = 1)             k = depth_eye + 1
+//   connectVertices (s >= 2, t >= 2)   k = depth_eye + depth_light + 1
+//   connectToCamera (t = 1)            k = depth_light + 1
+// A stored light vertex's depth is not its index in the store (delta vertices are walked
+// but not stored), so the record carries it in its rr word, which these NO_RR = 1 builds
+// never read (BDPT_LV_TAG). Every line of this compiles out with BDPT_LAYERS 0.
+#ifndef BDPT_LAYERS
+#define BDPT_LAYERS 0
+#endif
+#if BDPT_LAYERS
+#if BDPT_RR || (defined(BDPT_SAMPLER_STATE) && BDPT_SAMPLER_STATE)
+#error "BDPT_LAYERS: the frame kernel without Russian roulette only"
+#endif
+__device__ __forceinline__ int layer_index(const DevFrame& fr, int k, int pixel) {
+    const int plane = max(0, min(k - 1, fr.n_layers - 1));
+    return plane * (fr.W * fr.H) + pixel;  // < 2^30 (bdpt_render_layers checks n_layers * W * H)
+}
+#define BDPT_LAYER_PX(fr, k, pixel) layer_index(fr, k, pixel)
+#define BDPT_LV_TAG(rr, depth) __int_as_float(depth)
+#else
+#define BDPT_LAYER_PX(fr, k, pixel) (pixel)
+#define BDPT_LV_TAG(rr, depth) (rr)
+#endif
+
 // Light-vertex scratch, one contiguous record per lane: vertex v of slot s is
 // the four float4 at lv[(s * maxv + v) * 4 + q] — (p, vcm) (n, vc) (wo, rr)
 // (tp, mat). A lane reads or writes a whole 64-byte vertex from one cache
@@ -405,6 +437,9 @@ __device__ __forceinline__ bool task_push(const LaneCold&, const DevFrame&, f3, 
 constexpr bool kTasks = BDPT_HELP && !BDPT_SAMPLER_STATE;
 
 // An eye-estimate addition for the pixel: the wave's slot when it holds the pixel, else the framebuffer.
+// BDPT_LAYERS: `pixel` is a layered index (layer_index). A plane-0 index equals the plain pixel
+// and uses the slot as before (the slot's flush, eye_slot_reset, writes plane 0); an index of
+// another plane matches no slot (slots hold pixels < W * H) and goes to the framebuffer.
 __device__ __forceinline__ void eye_add(float* __restrict__ fb, int pixel, f3 add) {
 #if BDPT_EYE_SLOTS && !BDPT_SAMPLER_STATE
     float4* const s = wave_eye_slots();
@@ -425,6 +460,25 @@ __device__ __forceinline__ void eye_add(float* __restrict__ fb, int pixel, f3 ad
     gadd(px + 2, add.z);
 }
 
+#if BDPT_LAYERS
+// A term the default build sums in L.c.Li (the s = 0 emission, a connection the owner traced
+// itself): to the plane `px` names at once, scaled as finish() scales the sample's sum.
+__device__ __forceinline__ void layer_add(const DevFrame& fr, float* __restrict__ fb, int px, f3 c) {
+    if (c.x != 0.f || c.y != 0.f || c.z != 0.f) eye_add(fb, px, c * fr.inv_spp);
+}
+#endif
+
+// The unoccluded connection the lane traced itself (ST_NEE / ST_CONN; with tasks: the ring was
+// full): into the sample's sum, or (layers) to its plane (pend_px) at once.
+__device__ __forceinline__ void add_pending(Lane& L, const DevFrame& fr, float* __restrict__ fb) {
+#if BDPT_LAYERS
+    layer_add(fr, fb, L.c.pend_px, L.c.pend);
+#else
+    (void)fr, (void)fb;
+    L.c.Li = L.c.Li + L.c.pend;
+#endif
+}
+
 template <bool COUNT>
 __device__ __forceinline__ void finish(Lane& L, const DevFrame& fr, float* __restrict__ fb, Counts& cnt) {
     if (COUNT) {
@@ -435,11 +489,13 @@ __device__ __forceinline__ void finish(Lane& L, const DevFrame& fr, float* __res
             gadd(fr.row_cost + (L.c.pixel / fr.W - fr.row_offset) / fr.row_stride,
                  static_cast<unsigned long long>(L.c.steps));
     }
+#if !BDPT_LAYERS  // (layers: every contribution was added to its plane where it was formed; no per-sample sum)
     // rgb[p] += acc * (1 / spp) (renderer.cpp:202), one sample at a time.
     if (!(fr.flags & kFlagNoEyeAccum) && (L.c.Li.x != 0.f || L.c.Li.y != 0.f || L.c.Li.z != 0.f)) {
         const float inv_spp = fr.inv_spp;  // 1.f / spp
         eye_add(fb, L.c.pixel, L.c.Li * inv_spp);
     }
+#endif
     L.state = ST_IDLE;
 }
 
@@ -545,7 +601,7 @@ __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
         const float lightWeight = div_w(reversePdf_a, nlight) * (L.c.vcm + prevRev * L.c.vc); \
         const float mis = rcp_w(lightWeight + 1.f + 0.f); \
         const f3 pend_ = (fr.strategy == 0) ? rad * mis : rad; \
-        const int px_ = yp * fr.W + xp; \
+        const int px_ = BDPT_LAYER_PX(fr, L.c.depth + 1, yp * fr.W + xp);  /* t = 1: k = depth_light + 1 */ \
         /* a helper walks it and forms its ray from the camera and L.h.p (act: A_LIGHT_CONTINUE) */ \
         if (kTasks && task_push(L.c, fr, cam_o, L.h.p, false, pend_, px_, true, cnt)) break; \
         L.c.pend = pend_; \
@@ -563,7 +619,7 @@ __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
         const float rrp = rr_on(fr) ? L.c.rr : 1.f; \
         /* the store is full: the vertex would be pushed only if the walk continues (bdpt.h:211-215) */ \
         const bool full = rr_on(fr) && light && !delta && L.c.nl >= fr.lv_max; \
-        if (light && !delta && !full) store_vertex(ls, L.c.nl, L.h, L.c.tp, L.c.vcm, L.c.vc, rrp);  /* the pre-walk state */ \
+        if (light && !delta && !full) store_vertex(ls, L.c.nl, L.h, L.c.tp, L.c.vcm, L.c.vc, BDPT_LV_TAG(rrp, L.c.depth));  /* the pre-walk state */ \
         const bool more = continue_walk(b, L.h, L.rng, L.c.tp, L.c.depth, L.c.vc, L.c.vcm, L.ray, rrp); \
         if (full && more) {  /* it would be stored: flag the sample, end the light walk */ \
             gadd(fr.capped, 1u); \
@@ -622,6 +678,9 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
         if (fr.strategy == 1) {  // LIGHT_TRACING: Li = Le at the primary hit (bdpt.h:231)
             const int mat = __float_as_int(gld4(sc.shade + kShadeStride * static_cast<size_t>(L.c.prim_tri)).w);
             L.c.Li = ld3(bsdf_of(sc, mat).emission);
+#if BDPT_LAYERS  // the camera ray's own emitter hit: k = 1
+            layer_add(fr, fb, BDPT_LAYER_PX(fr, 1, L.c.pixel), L.c.Li);
+#endif
             act = A_FINISH;
             break;
         }
@@ -655,6 +714,9 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
         const f3 emission = ld3(b.emission);  // getEmission = materials[matID].emission
         if (!is_zero(emission)) {
             const int eid = shape_emitter_of(sc, shape_id(L.h.shape));
+#if BDPT_LAYERS  // L.c.Li is zero here (nothing sums in it): after the block it holds this term alone
+            L.c.Li = mk(0.f, 0.f, 0.f);
+#endif
             if (eid >= 0) {  // (the reference asserts otherwise, integrator.cpp:56)
                 const EmitterRecord& e = emitter_of(sc, eid);
                 const float emitterPdf = sc.inv_nemit;  // 1.f / nemit
@@ -673,6 +735,9 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
                     L.c.Li = L.c.Li + emission;
                 }
             }
+#if BDPT_LAYERS  // s = 0: k = depth_eye
+            layer_add(fr, fb, BDPT_LAYER_PX(fr, L.c.depth, L.c.pixel), L.c.Li);
+#endif
             act = A_FINISH;
             break;
         }
@@ -745,8 +810,12 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
         const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
         const f3 pend = (fr.strategy == 0) ? Li * mis : Li;
         const Ray sr = shadow_ray(L.h.p, e_p);
-        if (kTasks && task_push(L.c, fr, L.h.p, e_p, vertex_nocull(L, sr.d), pend * fr.inv_spp, L.c.pixel, false, cnt))
+        const int px = BDPT_LAYER_PX(fr, L.c.depth + 1, L.c.pixel);  // s = 1: k = depth_eye + 1
+        if (kTasks && task_push(L.c, fr, L.h.p, e_p, vertex_nocull(L, sr.d), pend * fr.inv_spp, px, false, cnt))
             break;  // a helper walks it (act: A_CONN)
+#if BDPT_LAYERS
+        L.c.pend_px = px;  // the ring is full: the owner traces it, resolve() adds it to this plane
+#endif
         L.c.pend = pend;
         L.ray = sr;
         L.state = ST_NEE;
@@ -791,10 +860,15 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
             const float eyeWeight = eyePathRev_a * (L.c.vcm + eyePrevRev * L.c.vc);
             const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
             const Ray sr = shadow_ray(L.h.p, V.p);
-            if (kTasks && task_push(L.c, fr, L.h.p, V.p, vertex_nocull(L, sr.d), (Li * mis) * fr.inv_spp, L.c.pixel, false, cnt)) {
+            // s >= 2, t >= 2: k = depth_eye + depth_light + 1 (the stored vertex's depth: BDPT_LV_TAG)
+            const int px = BDPT_LAYER_PX(fr, L.c.depth + __float_as_int(V.rr) + 1, L.c.pixel);
+            if (kTasks && task_push(L.c, fr, L.h.p, V.p, vertex_nocull(L, sr.d), (Li * mis) * fr.inv_spp, px, false, cnt)) {
                 L.c.ci++;  // a helper walks it; the next light vertex now
                 continue;
             }
+#if BDPT_LAYERS
+            L.c.pend_px = px;  // the ring is full: the owner traces it, resolve() adds it to this plane
+#endif
             L.c.pend = Li * mis;
             L.ray = sr;
             L.state = ST_CONN;
@@ -900,7 +974,8 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
         const float eyeWeight = eyePathRev_a * (oc.vcm + eyePrevRev * oc.vc);
         const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
         const Ray sr = shadow_ray(hp, V.p);
-        task_push(L.c, fr, hp, V.p, graze_exempt(sr.d, hn, hshape), (Li * mis) * fr.inv_spp, oc.pixel, false, cnt);
+        task_push(L.c, fr, hp, V.p, graze_exempt(sr.d, hn, hshape), (Li * mis) * fr.inv_spp,
+                  BDPT_LAYER_PX(fr, oc.depth + __float_as_int(V.rr) + 1, oc.pixel), false, cnt);
     }
     if (k > 0) L.c.ci = L.c.nl;
 }
@@ -988,11 +1063,11 @@ __device__ __forceinline__ uint32_t resolve(Lane& L, int res, float t, float u, 
             break;
         case ST_EYE: act = hit ? A_EYE_VERTEX : A_FINISH; break;
         case ST_NEE:
-            if (!hit) L.c.Li = L.c.Li + L.c.pend;
+            if (!hit) add_pending(L, fr, fb);
             act = A_CONN;
             break;
         case ST_CONN:
-            if (!hit) L.c.Li = L.c.Li + L.c.pend;
+            if (!hit) add_pending(L, fr, fb);
             L.c.ci++;
             act = A_CONN;
             break;

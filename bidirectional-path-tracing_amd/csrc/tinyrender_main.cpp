@@ -22,6 +22,10 @@
 // the main EXR is the same bytes with or without them. Both combine with --sample-window
 // (the filter's norm is spp / count); with several devices the first one renders the
 // feature buffers and filters the reduced frame.
+// --layers N (1..64, a bdpt scene) also writes <out stem>.L00.exr ... .L<N-1>.exr, the frame split
+// by path length (bdpt_render_layers_host: layer l holds the paths of l + 1 edges, the last one
+// everything longer; a second render, so the main EXR is the same bytes with or without it). A
+// malformed N is refused before any device is used; with several devices the first renders them.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -76,7 +80,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Syntax: %s <scene.toml> [nogui] [--width W --height H --spp N --rr D --device K "
                              "--out FILE.exr --seed S --gpus N --devices a,b,... --shard samples|rows "
-                             "--sample-window F:S:C --aov --denoise[=ITER]]\n", argv[0]);
+                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string toml = argv[1];
@@ -89,6 +93,7 @@ int main(int argc, char** argv) {
     bdpt_sample_window window = {0, 1, 0};
     bool want_aov = false, want_denoise = false;
     int denoise_iterations = BDPT_DENOISE_ITERATIONS;
+    int layers = 0;  // --layers N (0: none)
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -141,6 +146,15 @@ int main(int argc, char** argv) {
             }
             want_denoise = true;
             denoise_iterations = static_cast<int>(n);
+        } else if (a == "--layers") {
+            const char* v = next("--layers");
+            char* end = nullptr;
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 1 || n > 64) {
+                std::fprintf(stderr, "--layers %s: the layer count must be an integer in [1, 64]\n", v);
+                return EXIT_FAILURE;
+            }
+            layers = static_cast<int>(n);
         } else if (a == "--gpus") {
             const int n = std::atoi(next("--gpus"));
             devices.clear();
@@ -185,6 +199,10 @@ int main(int argc, char** argv) {
     const bool direct = std::strcmp(cfg.integrator, "direct") == 0;
     if (!path && !direct && std::strcmp(cfg.integrator, "bdpt") != 0) {
         std::fprintf(stderr, "integrator type \"%s\" is not part of the MI355X BDPT path\n", cfg.integrator);
+        return EXIT_FAILURE;
+    }
+    if (layers && (path || direct)) {
+        std::fprintf(stderr, "--layers splits a bdpt frame (integrator type \"%s\" has no layers)\n", cfg.integrator);
         return EXIT_FAILURE;
     }
     if (W > 0) cfg.width = W;
@@ -287,6 +305,22 @@ int main(int argc, char** argv) {
             std::printf("Saved EXR image to %s\n", side.c_str());
         }
         if (fctx != ctx) bdpt_ctx_destroy(fctx);
+    }
+    if (layers) {
+        bdpt_ctx* lctx = ctx;  // several devices: the first renders the layers
+        if (!lctx && bdpt_ctx_create(scene, devices[0], &lctx) != BDPT_OK) return die("bdpt_ctx_create (layers)");
+        const size_t plane = static_cast<size_t>(cfg.width) * cfg.height * 3;
+        std::vector<float> planes(plane * layers, 0.f);
+        if (bdpt_render_layers_host(lctx, &p, win, layers, planes.data()) != BDPT_OK) return die("bdpt_render_layers_host");
+        for (int l = 0; l < layers; l++) {
+            char suffix[16];
+            std::snprintf(suffix, sizeof suffix, ".L%02d", l);
+            const std::string side = side_path(exr, suffix);
+            if (bdpt_save_exr(planes.data() + plane * l, cfg.width, cfg.height, side.c_str()) != BDPT_OK)
+                return die("saveEXR");
+            std::printf("Saved EXR image to %s\n", side.c_str());
+        }
+        if (lctx != ctx) bdpt_ctx_destroy(lctx);
     }
     if (multi) bdpt_multi_destroy(multi);
     if (ctx) bdpt_ctx_destroy(ctx);

@@ -502,6 +502,34 @@ int bdpt_denoise(bdpt_ctx* ctx, int32_t width, int32_t height, const float* colo
 int bdpt_denoise_host(bdpt_ctx* ctx, int32_t width, int32_t height, const float* color_host, const float* aov_host,
                       float* out_host, const bdpt_denoise_params* params);
 
+/* ---- path-length layers: one BDPT frame split by bounce count ---- */
+/* (new) Not in the reference. Every contribution the BDPT frame kernel forms belongs to a full path
+ * camera -> ... -> emitter of k edges (k = 1: the camera ray hits an emitter; k = 2: direct light).
+ * bdpt_render_layers renders what bdpt_render_window (path = direct = NULL) renders - the same paths,
+ * the same contribution values - but ADDS each contribution to plane min(k - 1, n_layers - 1) of
+ * fb_layers, n_layers consecutive width * height * 3 planes, so the last plane collects every longer
+ * path and the planes sum to bdpt_render's frame (up to the order of the float additions; with
+ * n_layers = 1 the plane is the frame). All four kinds are layered: eye-walk emitter hits,
+ * connectToLight, connectVertices and connectToCamera's splats. The longest k a frame holds is
+ * 2 rr_depth - 1 for BDPT_STRATEGY_BDPT and rr_depth for PATH_TRACING (both: nothing at rr_depth 1),
+ * and max(1, rr_depth) for LIGHT_TRACING.
+ * window NULL = the whole frame; row shards and bdpt_set_row_order work as in bdpt_render.
+ * BDPT_ERR_INVALID: n_layers outside 1..64, or n_layers * width * height >= 2^30. BDPT_ERR_UNSUPPORTED
+ * (the message says "layers"), before any launch: flags != 0, Russian roulette, rr_depth > 28, a scene
+ * with bitmap textures, BSDF records in HBM. bdpt_last_kernel afterwards: "bdpt_frame_kernel_layers".
+ * Asynchronous on `hip_stream` like bdpt_render; the host form stages the caller's
+ * n_layers * width * height * 3 floats as bdpt_render_host stages its frame and is synchronous. */
+int bdpt_render_layers(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                       int32_t n_layers, float* fb_layers_device, void* hip_stream);
+int bdpt_render_layers_host(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                            int32_t n_layers, float* fb_layers_host);
+/* (new) out[p] = the sum of the planes l with bit l of `mask` set, float32 additions in ascending
+ * layer order starting from the lowest plane's value (no atomics: the bits of that sequential sum).
+ * Device pointers; out is width * height * 3 floats and must not overlap the planes. BDPT_ERR_INVALID: an empty mask, a bit at or above n_layers, n_layers
+ * outside 1..64 or n_layers * width * height >= 2^30. Asynchronous on `hip_stream`. */
+int bdpt_layers_compose(bdpt_ctx* ctx, const float* fb_layers_device, int32_t n_layers, int32_t width,
+                        int32_t height, uint64_t mask, float* out_device, void* hip_stream);
+
 /* ---- several HIP devices in one process ---- */
 /* The reference fans the offline loop out over host threads (parallel_for,
  * src/core/parallelfor.h:25-65, renderer.cpp:157); here every device gets one

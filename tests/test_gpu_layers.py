@@ -1,0 +1,365 @@
+"""Path-length layers (bdpt_render_layers): one BDPT frame split by the edge
+count k of each contribution's full path camera -> ... -> emitter, layer min(k - 1, n - 1).
+
+The layers must add up to the reference's frame (the goldens, at the project's bound: per-pixel
+relative L2 <= 1e-4, tests/test_gpu_parity.py's metric), the layer index must be right in
+absolute terms (scenes/kat/layers_open.obj, where no path of more than two edges carries
+energy), the depth bound of DESIGN.md must be tight, row shards and sample windows must commute
+with the split, the ring-full fallback must be layered like the tasks, bdpt_layers_compose must
+be the sequential float32 sum, and what the build does not serve must be refused.
+
+Frames are at most 64 x 64 x 16 spp (one 64-pixel row at 64 spp for the windows). A layered
+render is made once per (case, n_layers) and shared."""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import bdpt_amd
+import variants
+from conftest import REPO, gpu_available, load_golden
+from test_config_exr import decode_exr
+from test_gpu_parity import TOL, rel_l2
+
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a HIP device")]
+
+STRATEGY = {"bdpt": bdpt_amd.STRATEGY_BDPT, "lt": bdpt_amd.STRATEGY_LIGHT_TRACING, "pt": bdpt_amd.STRATEGY_PATH_TRACING}
+with open(os.path.join(REPO, "tests", "golden", "manifest.json")) as _f:
+    FRAMES = json.load(_f)["framebuffers"]
+
+
+def smallest(strategy):
+    """The smallest golden (by samples; the manifest's order breaks ties) of the strategy that
+    fits 64 x 64 x 16 spp in one shard. synth1m is left out: building its million triangles
+    takes longer than every render here together."""
+    fit = [(m["samples"], i, n) for i, (n, m) in enumerate(FRAMES.items())
+           if m.get("strategy", "bdpt") == strategy and m["width"] <= 64 and m["height"] <= 64 and m["spp"] <= 16
+           and m["row_stride"] == 1 and m["scene"] != "synth1m"]
+    return min(fit)[2]
+
+
+BDPT_CASE, LT_CASE, PT_CASE, CBOX_CASE = smallest("bdpt"), smallest("lt"), smallest("pt"), "G1_cbox_low_64x64_spp4"
+RING_CASE = "G2_caustic_64x64_spp16"  # glass (delta light vertices) and, at BDPT_TASK_CAP=64, refused pushes
+SUM_CASES = [BDPT_CASE, LT_CASE, PT_CASE, CBOX_CASE, RING_CASE]
+
+_scenes, _layers = {}, {}
+
+
+def scene(path):
+    if path not in _scenes:
+        _scenes[path] = bdpt_amd.Scene(path)
+    return _scenes[path]
+
+
+def golden_integrator(name, **kw):
+    m = FRAMES[name]
+    args = dict(camera=bdpt_amd.Camera(**variants.SCENES[m["scene"]]["camera"]), width=m["width"], height=m["height"],
+                spp=m["spp"], rr_depth=m["rr_depth"], strategy=STRATEGY[m.get("strategy", "bdpt")])
+    args.update(kw)
+    it = bdpt_amd.BDPTIntegrator(scene(variants.obj_path(m["scene"])), bdpt_amd.Config(**args))
+    it.init()
+    return it
+
+
+def bound_of(name):
+    m = FRAMES[name]
+    return bdpt_amd.layers_longest_path(m["rr_depth"], STRATEGY[m.get("strategy", "bdpt")])
+
+
+def layers_of(name, n_layers):
+    """The layered render of a golden's frame, made once (read-only: callers do not write to it)."""
+    key = (name, n_layers)
+    if key not in _layers:
+        it = golden_integrator(name)
+        out = it.render_layers(n_layers)
+        st = it.stats()
+        assert st["kernel"] == "bdpt_frame_kernel_layers", st["kernel"]
+        assert st["schedule_errors"] == 0 and st["samples"] == FRAMES[name]["samples"]
+        assert out.shape == (n_layers, FRAMES[name]["height"], FRAMES[name]["width"], 3) and out.dtype == np.float32
+        assert np.isfinite(out).all()
+        out.setflags(write=False)
+        _layers[key] = out
+    return _layers[key]
+
+
+def layer_sum(layers):
+    return layers.astype(np.float64).sum(axis=0)
+
+
+def worst_per_layer(a, b):
+    return max(rel_l2(a[l], b[l]).max() for l in range(a.shape[0]))
+
+
+# ---------------------------------------------------------------- 1. the layers add up
+@pytest.mark.parametrize("which", ["bound+1", "3", "1"])
+@pytest.mark.parametrize("name", SUM_CASES)
+def test_gpu_layers_sum_to_the_reference_frame(name, which):
+    n = {"bound+1": bound_of(name) + 1, "3": 3, "1": 1}[which]
+    layers = layers_of(name, n)
+    ref = load_golden(name)
+    total = layers[0] if n == 1 else layer_sum(layers)  # n = 1: the layer itself is the frame
+    worst = rel_l2(np.asarray(total), ref).max()
+    print(f"{name} n_layers {n}: max per-pixel rel L2 of the layer sum {worst:.3g}; layer means "
+          f"{[float(f'{x:.3g}') for x in layers.reshape(n, -1).mean(axis=1)]}")
+    assert worst <= TOL, f"max per-pixel rel L2 {worst:.3g}"
+    if which == "bound+1":
+        # one layer per admitted length and one more: the extra (overflow) layer stays empty
+        assert not layers[-1].any()
+    if which == "3" and bound_of(name) > 3:
+        # the overflow bucket is in use: layers 0 and 1 are the long render's, the last its rest
+        full = layers_of(name, bound_of(name) + 1)
+        assert rel_l2(layers[0], full[0]).max() <= TOL and rel_l2(layers[1], full[1]).max() <= TOL
+        assert rel_l2(layers[2], layer_sum(full[2:])).max() <= TOL
+
+
+# ------------------------------------------------- 2. the layer index in absolute terms
+OPEN_OBJ = os.path.join(REPO, "scenes", "kat", "layers_open.obj")
+OPEN_CAMERA = dict(eye=(0.0, 0.6, 3.0), at=(0.0, 0.6, 0.0), up=(0.0, 1.0, 0.0), fov=45.0)
+OPEN_W = OPEN_H = 48
+
+
+def open_integrator(spp, strategy=bdpt_amd.STRATEGY_BDPT):
+    cfg = bdpt_amd.Config(camera=bdpt_amd.Camera(**OPEN_CAMERA), width=OPEN_W, height=OPEN_H, spp=spp, rr_depth=5,
+                          strategy=strategy)
+    it = bdpt_amd.BDPTIntegrator(scene(OPEN_OBJ), cfg)
+    it.init()
+    return it
+
+
+def dilate(mask):
+    """The mask and the 8 neighbours of each of its pixels."""
+    p = np.pad(mask, 1)
+    out = np.zeros_like(mask)
+    for dy in range(3):
+        for dx in range(3):
+            out |= p[dy:dy + mask.shape[0], dx:dx + mask.shape[1]]
+    return out
+
+
+@pytest.fixture(scope="module")
+def open_first_hits():
+    """Per pixel, what the frame's own spp = 1 camera ray hits first: (emitter mask, floor mask)."""
+    it = open_integrator(1)
+    px = np.arange(OPEN_W * OPEN_H, dtype=np.uint32)
+    rec = np.stack([px, np.zeros_like(px), np.zeros_like(px)], axis=1)
+    d = it.debug_sampling("camera", rec).view(np.float32)
+    rays = np.zeros((px.size, 8), np.float32)
+    rays[:, 0:3] = OPEN_CAMERA["eye"]
+    rays[:, 3:6] = d
+    rays[:, 6], rays[:, 7] = 1.0, 1000.0  # the camera ray's range (renderer.cpp)
+    hit = it.intersect(rays)
+    got = hit["hit"] == 1
+    y = hit["p"][:, 1]  # the emitter quad lies at y = 1.3, the floor at y = 0
+    emitter = (got & (y > 0.5)).reshape(OPEN_H, OPEN_W)
+    floor = (got & (y <= 0.5)).reshape(OPEN_H, OPEN_W)
+    assert emitter.sum() >= 4 and floor.sum() >= 100 and not (emitter & floor).any()  # the camera sees both
+    assert not dilate(emitter)[floor].any()  # and they are apart in the image
+    return emitter, floor
+
+
+@pytest.mark.parametrize("strategy", ["bdpt", "lt", "pt"])
+@pytest.mark.parametrize("spp", [1, 8])
+def test_gpu_layer_index_is_absolute_on_the_open_scene(open_first_hits, spp, strategy):
+    """Camera -> emitter is one edge, camera -> floor -> emitter two, and nothing longer carries
+    energy (the emitter's Kd is 0, the floor is flat). An off-by-one in any of the four k formulas
+    moves energy into a layer that must be empty, or out of one that must not be. BDPT reaches
+    all four sites; light tracing alone pins connectToCamera, path tracing connectToLight."""
+    emitter, floor = open_first_hits
+    it = open_integrator(spp, STRATEGY[strategy])
+    layers = it.render_layers(6)
+    assert it.stats()["kernel"] == "bdpt_frame_kernel_layers"
+    lit = [layers[l].any(axis=2) for l in range(6)]
+    print(f"{strategy} spp {spp}: non-zero pixels per layer {[int(m.sum()) for m in lit]}")
+    for l in range(2, 6):
+        assert not layers[l].any(), f"layer {l} holds energy: no path of {l + 1} edges exists"
+    assert lit[0].any() and not (lit[0] & ~dilate(emitter)).any()
+    assert lit[1].any() and not (lit[1] & ~dilate(floor)).any()
+    if spp == 1:  # no jitter: layer 0 is exactly the pixels whose ray hits the emitter, at its radiance (Ke)
+        assert np.array_equal(lit[0], emitter)
+        assert np.allclose(layers[0][emitter], np.float32([17.0, 12.0, 4.0]), rtol=1e-6)
+    # and the layers are the plain frame
+    ref = open_integrator(spp, STRATEGY[strategy]).render_frame()
+    assert rel_l2(layer_sum(layers), ref).max() <= TOL
+
+
+# ------------------------------------------------------------ 3. the depth bound is tight
+@pytest.mark.parametrize("rr", [1, 2, 3])
+def test_gpu_depth_bound_is_tight(rr):
+    """cbox_low 48 x 48 x 8, strategy 0: the longest admitted path has 2 rr - 1 edges (none at
+    rr_depth 1, where neither subpath has a vertex: the frame is black)."""
+    bound = bdpt_amd.layers_longest_path(rr, bdpt_amd.STRATEGY_BDPT)
+    assert bound == (0 if rr == 1 else 2 * rr - 1)
+    cfg = bdpt_amd.Config(camera=bdpt_amd.Camera(**variants.SCENES["cbox_low"]["camera"]), width=48, height=48, spp=8,
+                          rr_depth=rr)
+    it = bdpt_amd.BDPTIntegrator(scene(variants.obj_path("cbox_low")), cfg)
+    it.init()
+    layers = it.render_layers(bound + 3)
+    print(f"rr_depth {rr}: layer means {[float(f'{x:.3g}') for x in layers.reshape(bound + 3, -1).mean(axis=1)]}")
+    for l in range(bound, bound + 3):
+        assert not layers[l].any(), f"rr_depth {rr}: layer {l} (paths of {l + 1} edges) is not empty"
+    if bound:
+        assert layers[bound - 1].any(), f"rr_depth {rr}: the layer at the bound ({bound} edges) is empty"
+
+
+# ------------------------------------------------------- 4. decompositions commute
+def test_gpu_row_shards_sum_to_the_full_layers():
+    n = bound_of(CBOX_CASE) + 1
+    full = layers_of(CBOX_CASE, n)
+    parts = [golden_integrator(CBOX_CASE).render_layers(n, row_offset=o, row_stride=2) for o in (0, 1)]
+    worst = worst_per_layer(parts[0] + parts[1], full)
+    print(f"two interleaved row shards: worst per-layer per-pixel rel L2 {worst:.3g}")
+    assert worst <= 1e-4
+
+
+def test_gpu_sample_windows_sum_to_the_full_layers():
+    """40 + 24 of 64 spp on one pixel row: the whole frame's 64-sample chunks each cover one pixel
+    (the eye slots hold layer 0's sums), the windows' chunks do not."""
+    m = FRAMES[CBOX_CASE]
+    n = bound_of(CBOX_CASE) + 1
+    row = dict(row_offset=40, row_stride=m["height"])
+    full = golden_integrator(CBOX_CASE, spp=64).render_layers(n, **row)
+    a = golden_integrator(CBOX_CASE, spp=64).render_layers(n, window=bdpt_amd.SampleWindow(0, 1, 40), **row)
+    b = golden_integrator(CBOX_CASE, spp=64).render_layers(n, window=bdpt_amd.SampleWindow(40, 1, 24), **row)
+    assert full[0, 40].any() or full[1, 40].any()
+    worst = worst_per_layer(a + b, full)
+    print(f"sample windows 40 + 24 of 64: worst per-layer per-pixel rel L2 {worst:.3g}")
+    assert worst <= 1e-4
+    assert rel_l2(layer_sum(full), golden_integrator(CBOX_CASE, spp=64).render_frame(**row)).max() <= TOL
+
+
+# ----------------------------------------------------- 5. the ring-full path is layered
+@pytest.mark.parametrize("name", [BDPT_CASE, RING_CASE])
+def test_gpu_ring_full_fallback_is_layered(name, monkeypatch):
+    """BDPT_TASK_CAP=64 (read when the context is created): pushes are refused and the owner
+    traces those shadow rays itself; each such connection must still land in its own layer.
+    A layered render cannot count (flags are refused), so the evidence that the fallback runs
+    is a counting pass of the same frame on the same context with the default build, whose
+    schedule this build shares: it must refuse pushes on the caustic frame. For test 1's small
+    BDPT case (32 x 32 x 4) nothing shows that a push is refused; it is here because the issue
+    asks that it still adds up at this capacity, and its refusals are printed, not asserted."""
+    n = bound_of(name) + 1
+    default = layers_of(name, n)
+    monkeypatch.setenv("BDPT_TASK_CAP", "64")
+    it = golden_integrator(name)
+    small = it.render_layers(n)
+    assert it.stats()["kernel"] == "bdpt_frame_kernel_layers" and it.stats()["schedule_errors"] == 0
+    worst_sum = rel_l2(layer_sum(small), load_golden(name)).max()
+    worst = worst_per_layer(small, default)
+    print(f"{name} at BDPT_TASK_CAP=64: layer sum vs golden {worst_sum:.3g}, per layer vs default ring {worst:.3g}")
+    assert worst_sum <= TOL
+    assert worst <= 1e-4
+    it.render_frame(flags=bdpt_amd.FLAG_COUNT)
+    st = it.stats()
+    pushed, refusals = st["sched"]["step_tasks"], st["sched"]["shade_steps"]  # (tests/test_gpu_task_ring.py)
+    print(f"{name}: counting pass of the default build at this capacity: pushed {pushed}, refused {refusals}")
+    if name == RING_CASE:
+        assert refusals > 0, "no push was refused: the ring-full fallback did not run"
+
+
+# ---------------------------------------------------------------------- 6. compose
+def test_gpu_compose_is_the_sequential_float32_sum():
+    n = bound_of(CBOX_CASE) + 1
+    layers = layers_of(CBOX_CASE, n)
+    it = golden_integrator(CBOX_CASE)
+    masks = {"all": list(range(n)), "0": [0], "1": [1], ">=2": list(range(2, n)), "sparse": [0, 3, 7]}
+    for label, ls in masks.items():
+        want = layers[ls[0]].copy()
+        for l in ls[1:]:
+            want = want + layers[l]  # float32 + float32, ascending
+        assert want.dtype == np.float32
+        for arg in (ls, sum(1 << l for l in ls)):  # an iterable of indices, an int mask
+            got = it.compose_layers(layers, arg)
+            assert got.shape == want.shape and got.dtype == np.float32
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), label
+    for bad in (0, [], 1 << n, [n], [0, n]):
+        with pytest.raises(bdpt_amd.BdptError) as e:
+            it.compose_layers(layers, bad)
+        assert e.value.code == bdpt_amd.ERR_INVALID, str(e.value)
+
+
+# ------------------------------------------------- 7. refusals and non-interference
+def test_gpu_layers_unsupported_and_invalid(monkeypatch):
+    def refused(fn, code, *words):
+        with pytest.raises(bdpt_amd.BdptError) as e:
+            fn()
+        assert e.value.code == code, str(e.value)
+        for w in words:
+            assert w in str(e.value), str(e.value)
+
+    U, I = bdpt_amd.ERR_UNSUPPORTED, bdpt_amd.ERR_INVALID
+    name = CBOX_CASE
+    refused(lambda: golden_integrator(name, russian_roulette=bdpt_amd.RR_LUMINANCE).render_layers(4), U, "layers")
+    refused(lambda: golden_integrator(name, rr_depth=29).render_layers(4), U, "layers", "rr_depth")
+    refused(lambda: golden_integrator(name).render_layers(4, flags=bdpt_amd.FLAG_COUNT), U, "layers", "flags")
+    with open(os.path.join(REPO, "tests", "golden", "tex_manifest.json")) as f:
+        tex = json.load(f)
+    tm = tex["frames"]["tex_T1_texbox_bdpt"]
+    cam = bdpt_amd.Camera(**{k: tuple(v) if isinstance(v, list) else v for k, v in tex["camera"].items()})
+    tcfg = bdpt_amd.Config(camera=cam, width=tm["width"], height=tm["height"], spp=tm["spp"], rr_depth=tm["rr_depth"])
+    refused(lambda: bdpt_amd.BDPTIntegrator(scene(os.path.join(REPO, "scenes", "tex", tm["obj"])), tcfg).render_layers(4),
+            U, "layers", "texture")
+    with monkeypatch.context() as mp:  # (the context reads it when it is created)
+        mp.setenv("BDPT_BSDF_IN_HBM", "1")
+        hbm = golden_integrator(name)
+    refused(lambda: hbm.render_layers(4), U, "layers", "HBM")
+    it = golden_integrator(name)
+    refused(lambda: it.render_layers(0), I, "n_layers")
+    refused(lambda: it.render_layers(65), I, "n_layers")
+    # n_layers * W * H >= 2^30, in the params only: refused before anything is allocated
+    big = golden_integrator(name)
+    big.config.width, big.config.height = 32768, 16384
+    refused(lambda: big.render_layers(2), I, "2^30")
+    big.config.width, big.config.height = 32768, 32768
+    refused(lambda: big.render_layers(1), I, "2^30")
+
+
+def test_gpu_plain_frames_around_a_layered_render_are_unchanged():
+    m = FRAMES[RING_CASE]  # caustic: glossy materials, so the default build by name
+    it = golden_integrator(RING_CASE)
+    before = it.render_frame().copy()
+    k0 = it.stats()["kernel"]
+    layers = it.render_layers(bound_of(RING_CASE) + 1)
+    assert it.stats()["kernel"] == "bdpt_frame_kernel_layers"
+    it.rgb[:] = 0
+    after = it.render_frame().copy()
+    k1 = it.stats()["kernel"]
+    assert k0 == k1 == "bdpt_frame_kernel", (k0, k1)
+    assert rel_l2(after, before).max() <= 1e-4
+    assert rel_l2(before, load_golden(RING_CASE)).max() <= TOL
+    assert rel_l2(layer_sum(layers), before).max() <= 1e-4
+    assert m["rr_depth"] == 8
+
+
+# ------------------------------------------------------------------- 8. the command line
+def test_gpu_cli_writes_one_exr_per_layer(tmp_path):
+    """--layers 3 on the small cbox scene: three extra EXRs that sum to the main one within
+    3 half-ulps (3 * 2^-11 relative), the issue's bound. Every file is rounded to half once
+    (relative error <= 2^-11 for a normal half) and the layers are non-negative, so the sum of
+    the three rounded layers is within 2^-11 of the exact sum, the main file within 2^-11 more,
+    and two renders differ by the order of their float32 atomic additions (<= 1e-4, about 0.2
+    of 2^-11): about 2.2 of the 3 units. Subnormal halves round absolutely, by at most 2^-25
+    in each of the four files: the floor 2^-23."""
+    W = H = 32
+    spp = 4
+    cli = os.path.join(os.path.dirname(bdpt_amd.LIB_PATH), "tinyrender_amd")
+    for sub in ("plain", "layers"):
+        (tmp_path / sub).mkdir()
+        (tmp_path / sub / "scene.toml").write_text(variants.toml_text("cbox_low", W, H, spp))
+    r = subprocess.run([cli, str(tmp_path / "plain" / "scene.toml")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([cli, str(tmp_path / "layers" / "scene.toml"), "--layers", "3"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert sorted(os.listdir(tmp_path / "plain")) == ["scene.exr", "scene.toml"]
+    assert sorted(os.listdir(tmp_path / "layers")) == ["scene.L00.exr", "scene.L01.exr", "scene.L02.exr", "scene.exr",
+                                                       "scene.toml"]
+    main = decode_exr((tmp_path / "layers" / "scene.exr").read_bytes()).astype(np.float64)
+    plain = decode_exr((tmp_path / "plain" / "scene.exr").read_bytes()).astype(np.float64)
+    assert np.abs(main - plain).max() <= 2.0 ** -10 * np.abs(plain).max()  # the same frame (one half ulp apart at most)
+    parts = [decode_exr((tmp_path / "layers" / f"scene.L{l:02d}.exr").read_bytes()).astype(np.float64) for l in range(3)]
+    assert all(p.any() for p in parts)
+    total = parts[0] + parts[1] + parts[2]
+    tol = 3 * 2.0 ** -11 * np.maximum(total, main) + 2.0 ** -23
+    assert (np.abs(total - main) <= tol).all(), float((np.abs(total - main) / np.maximum(main, 1e-6)).max())
