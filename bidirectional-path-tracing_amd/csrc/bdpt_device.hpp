@@ -1043,26 +1043,79 @@ __device__ __forceinline__ bool ref_leaf_passes(const float4* __restrict__ lbox,
     if (COUNT) cnt.c[15] += fb;
     return pass;
 }
+// The triangles are fetched BDPT_WLEAF_GROUP at a time, all loads of a group
+// issued before its first test (the magnitude of leaf_tests' BDPT_LEAF_GROUP
+// for this walk):
+//   1  one triangle per round trip: triangle k + 1's loads sit behind triangle
+//      k's test and its branch, a leaf of `count` triangles exposes `count`
+//      dependent latencies (the device code before the grouped form; A/B runs)
+//   2  pairs (k, k + 1): half the round trips. An odd count's last pair loads
+//      the leaf's last triangle twice (the second index clamped to count - 1:
+//      no address outside [start, start + count)), its second result unused.
+// The tests run in index order with the ungrouped loop's decisions; a triangle
+// the ungrouped loop would not have reached (past the count, or behind the hit
+// that ends an occlusion query) is loaded but neither tested nor counted.
+// 24 VGPRs per pair, under the node step's 28 (WNode), which is dead here.
+#ifndef BDPT_WLEAF_GROUP
+#define BDPT_WLEAF_GROUP 2
+#endif
 template <bool COUNT>
 __device__ __forceinline__ bool wleaf_tests(const float4* __restrict__ wtri, const float4* __restrict__ lbox,
                                             uint32_t link, const Ray& r, const RayInv& ri, bool any, float& best_t,
                                             int& best, float& best_u, float& best_v, Counts& cnt) {
+    constexpr uint32_t G = BDPT_WLEAF_GROUP;
+    static_assert(G == 1 || G == 2, "BDPT_WLEAF_GROUP: 1 or 2 (four triangles do not fit under the node step's registers)");
     const uint32_t start = (link >> 3) & 0x0fffffffu, count = link & 7u;
-    for (uint32_t k = 0; k < count; k++) {
-        const size_t i = static_cast<size_t>(start + k);
-        const float4 q0 = gld4(wtri + 3 * i), q1 = gld4(wtri + 3 * i + 1), q2 = gld4(wtri + 3 * i + 2);
-        float t, u, v;
-        if (COUNT) cnt.c[3]++;
-        if (!tri_test_edges(xyz(q0), xyz(q1), xyz(q2), r, t, u, v)) continue;
-        const int idx = __float_as_int(q0.w);
-        if (any) {
-            if (t <= r.max_t && ref_leaf_passes<COUNT>(lbox, __float_as_uint(q1.w), r, ri, cnt)) {
-                best = idx;
-                return true;
+    if constexpr (G == 1) {  // the ungrouped loop as it was written: the same device code (tools/asm_identity.sh)
+        for (uint32_t k = 0; k < count; k++) {
+            const size_t i = static_cast<size_t>(start + k);
+            const float4 q0 = gld4(wtri + 3 * i), q1 = gld4(wtri + 3 * i + 1), q2 = gld4(wtri + 3 * i + 2);
+            float t, u, v;
+            if (COUNT) cnt.c[3]++;
+            if (!tri_test_edges(xyz(q0), xyz(q1), xyz(q2), r, t, u, v)) continue;
+            const int idx = __float_as_int(q0.w);
+            if (any) {
+                if (t <= r.max_t && ref_leaf_passes<COUNT>(lbox, __float_as_uint(q1.w), r, ri, cnt)) {
+                    best = idx;
+                    return true;
+                }
+            } else if ((t < best_t || (t == best_t && best >= 0 && idx < best)) &&
+                       ref_leaf_passes<COUNT>(lbox, __float_as_uint(q1.w), r, ri, cnt)) {
+                best_t = t, best = idx, best_u = u, best_v = v;
             }
-        } else if ((t < best_t || (t == best_t && best >= 0 && idx < best)) &&
-                   ref_leaf_passes<COUNT>(lbox, __float_as_uint(q1.w), r, ri, cnt)) {
-            best_t = t, best = idx, best_u = u, best_v = v;
+        }
+        return false;
+    }
+    for (uint32_t k0 = 0; k0 < count; k0 += G) {
+        float4 q[G][3];
+#pragma unroll
+        for (uint32_t g = 0; g < G; g++) {
+            const size_t i = static_cast<size_t>(start + (g == 0 || k0 + g < count ? k0 + g : count - 1));
+            q[g][0] = gld4(wtri + 3 * i), q[g][1] = gld4(wtri + 3 * i + 1), q[g][2] = gld4(wtri + 3 * i + 2);
+        }
+        if (G > 1) {  // every load of the group in flight before the first test
+#pragma unroll
+            for (uint32_t g = 0; g < G; g++)
+#pragma unroll
+                for (int j = 0; j < 3; j++) asm volatile("" ::"v"(q[g][j].x), "v"(q[g][j].y), "v"(q[g][j].z), "v"(q[g][j].w));
+        }
+#pragma unroll
+        for (uint32_t g = 0; g < G; g++) {
+            if (g > 0 && k0 + g >= count) break;
+            const float4 q0 = q[g][0], q1 = q[g][1], q2 = q[g][2];
+            float t, u, v;
+            if (COUNT) cnt.c[3]++;
+            if (!tri_test_edges(xyz(q0), xyz(q1), xyz(q2), r, t, u, v)) continue;
+            const int idx = __float_as_int(q0.w);
+            if (any) {
+                if (t <= r.max_t && ref_leaf_passes<COUNT>(lbox, __float_as_uint(q1.w), r, ri, cnt)) {
+                    best = idx;
+                    return true;
+                }
+            } else if ((t < best_t || (t == best_t && best >= 0 && idx < best)) &&
+                       ref_leaf_passes<COUNT>(lbox, __float_as_uint(q1.w), r, ri, cnt)) {
+                best_t = t, best = idx, best_u = u, best_v = v;
+            }
         }
     }
     return false;
