@@ -15,6 +15,9 @@ Mirrors the reference's plugin surface for the BDPT path
     .denoise(samples_done=...)         edge-avoiding a-trous filter of a low-spp frame (bdpt_denoise; no counterpart)
     .render_layers(n) / .compose_layers(layers, mask)
                                        the BDPT frame split by path length (bdpt_render_layers; no counterpart)
+    .render_light_groups(map, n) / .relight(groups, gains)
+                                       the BDPT frame split by emitter and recombined with per-group RGB gains
+                                       (bdpt_render_light_groups, bdpt_light_groups_relight; no counterpart)
   Sampler(seed)                        Sampler              src/core/math.h:63-76 (seed + draw count)
   Ray(o, d, min_t, max_t)              Ray                  src/core/core.h:117-122
   load_toml(path) -> SceneConfig       loadTOML             src/main.cpp:22-116
@@ -172,6 +175,11 @@ LAYOUT_ARRAYS = ("tri", "shade", "nodes", "wnodes", "wtri", "lbox", "bsdfs", "em
                  "shape_emitter", "roots", "bsdfs_ingested")  # bdpt_scene_export_layout ids 0..12
 
 
+class _EmitterInfo(ctypes.Structure):
+    _fields_ = [("shape", ctypes.c_int32), ("material", ctypes.c_int32), ("area", ctypes.c_float),
+                ("radiance", ctypes.c_float * 3)]
+
+
 @dataclass
 class SceneDesc:
     """bdpt_scene_desc as numpy arrays: the Scene a caller already holds in memory
@@ -211,7 +219,7 @@ class _Stats(ctypes.Structure):
 
 # Sources that make up the frame kernels' code objects: their hash stamps the
 # profiles (PMC passes) so bench.py only reuses a measurement of the same kernel.
-KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_kernels_layers.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
+KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_kernels_layers.hip", "csrc/bdpt_kernels_groups.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
                   "csrc/powf_restated.inc", "csrc/bdpt_types.h", "Makefile")
 
 
@@ -307,6 +315,11 @@ def lib():
         L.bdpt_render_layers.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp, vp]
         L.bdpt_render_layers_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp]
         L.bdpt_layers_compose.argtypes = [vp, vp, i32, i32, i32, ctypes.c_uint64, vp, vp]
+        L.bdpt_scene_emitter_count.argtypes = [vp, ctypes.POINTER(i32)]
+        L.bdpt_scene_get_emitter.argtypes = [vp, i32, ctypes.POINTER(_EmitterInfo)]
+        L.bdpt_render_light_groups.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp, vp, vp]
+        L.bdpt_render_light_groups_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp, vp]
+        L.bdpt_light_groups_relight.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
         L.bdpt_synchronize.argtypes = [vp]
         L.bdpt_config_load_toml.argtypes = [ctypes.c_char_p, ctypes.POINTER(_Config)]
         L.bdpt_render_path.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_PathParams), vp, vp]
@@ -702,6 +715,20 @@ class Scene:
         _check(lib().bdpt_scene_get_info(self._h, ctypes.byref(i)))
         return {n: getattr(i, n) for n, _ in _SceneInfo._fields_}
 
+    def emitters(self) -> list:
+        """The emitters in Scene::emitters order (the index selectEmitter draws and
+        render_light_groups' group_of_emitter is indexed by): dicts of shape, material (index
+        into the MTL's materials in file order), area and radiance (the material's Ke)."""
+        n = ctypes.c_int32()
+        _check(lib().bdpt_scene_emitter_count(self._h, ctypes.byref(n)))
+        out = []
+        for i in range(n.value):
+            e = _EmitterInfo()
+            _check(lib().bdpt_scene_get_emitter(self._h, i, ctypes.byref(e)))
+            out.append(dict(shape=int(e.shape), material=int(e.material), area=float(e.area),
+                            radiance=tuple(float(x) for x in e.radiance)))
+        return out
+
     def bsdf_type(self, mat: int) -> tuple:
         """(BSDF::getType() flags, kind) of material `mat` (core.h:311; kind 1 diffuse,
         2 mirror, 3 glass, 4 mixture, 5 phong, 0 null)."""
@@ -1061,6 +1088,81 @@ class BDPTIntegrator:
         _check(lib().bdpt_layers_compose(self._h, ctypes.c_void_p(layers_ptr), int(n_layers), int(width), int(height),
                                          ctypes.c_uint64(mask), ctypes.c_void_p(out_ptr),
                                          ctypes.c_void_p(stream_ptr)))
+
+    def _group_map(self, group_of_emitter, n_groups):
+        """(int32 array or None, n_groups) as bdpt_render_light_groups takes them: no map is the
+        identity, whose plane count defaults to the emitter count; with a map it defaults to
+        max(map) + 1."""
+        if group_of_emitter is None:
+            n = len(self.scene.emitters()) if n_groups is None else int(n_groups)
+            return None, n
+        m = np.ascontiguousarray(group_of_emitter, np.int32).reshape(-1)
+        if m.size != len(self.scene.emitters()):
+            raise BdptError(f"render_light_groups: group_of_emitter has {m.size} entries, the scene "
+                            f"{len(self.scene.emitters())} emitters")
+        return m, (int(m.max()) + 1 if n_groups is None else int(n_groups))
+
+    def render_light_groups(self, group_of_emitter=None, n_groups: int | None = None, window: SampleWindow | None = None,
+                            row_offset: int = 0, row_stride: int = 1, flags: int = 0) -> np.ndarray:
+        """bdpt_render_light_groups_host: the BDPT frame split by emitter, a new (n_groups, H, W, 3)
+        array. Plane g holds the contributions of the paths that end on an emitter e with
+        group_of_emitter[e] == g (Scene.emitters() order; None: one plane per emitter); the planes
+        sum to render_frame()'s frame, and relight() recombines them under other emitter colours."""
+        H, W = self.config.height, self.config.width
+        p = self.params(row_offset, row_stride, flags)
+        w = window.c() if window is not None else None
+        m, n = self._group_map(group_of_emitter, n_groups)
+        # a count or size the library refuses (before it touches the buffer) is not allocated here
+        ok = 1 <= n <= 64 and n * W * H < 1 << 30
+        out = np.zeros((n, H, W, 3) if ok else (1,), np.float32)
+        _check(lib().bdpt_render_light_groups_host(self._h, ctypes.byref(p), w and ctypes.byref(w), n,
+                                                   None if m is None else m.ctypes.data, out.ctypes.data))
+        return out
+
+    def render_light_groups_device(self, fb_ptr: int, group_of_emitter=None, n_groups: int | None = None,
+                                   stream_ptr: int = 0, window: SampleWindow | None = None, row_offset: int = 0,
+                                   row_stride: int = 1) -> None:
+        """bdpt_render_light_groups: asynchronous, ADDED to a device buffer of n_groups * H * W * 3 floats."""
+        p = self.params(row_offset, row_stride, 0)
+        w = window.c() if window is not None else None
+        m, n = self._group_map(group_of_emitter, n_groups)
+        _check(lib().bdpt_render_light_groups(self._h, ctypes.byref(p), w and ctypes.byref(w), n,
+                                              None if m is None else m.ctypes.data, ctypes.c_void_p(fb_ptr),
+                                              ctypes.c_void_p(stream_ptr)))
+
+    def relight(self, groups, gains) -> np.ndarray:
+        """bdpt_light_groups_relight on the device: the (H, W, 3) float32 frame sum_g gains[g] *
+        groups[g] (gains: (n_groups, 3) RGB, or (n_groups,) for grey gains), each product and sum
+        rounded in float32 in ascending group order. The planes go to the device and the frame
+        comes back (a viewer that keeps the planes on the device calls relight_device)."""
+        import torch
+
+        a = np.ascontiguousarray(groups, np.float32)
+        if a.ndim != 4 or a.shape[3] != 3:
+            raise BdptError(f"relight: groups must be (n_groups, H, W, 3), got {a.shape}")
+        n, H, W = a.shape[:3]
+        g = np.asarray(gains, np.float32)
+        if g.ndim == 1:
+            g = np.repeat(g[:, None], 3, axis=1)
+        if g.shape != (n, 3):
+            raise BdptError(f"relight: gains must be ({n}, 3) or ({n},), got {g.shape}")
+        dev = torch.device("cuda", self.device)
+        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+        d_out = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.relight_device(d_in.data_ptr(), n, W, H, g, d_out.data_ptr())
+        self.synchronize()
+        return d_out.cpu().numpy()
+
+    def relight_device(self, groups_ptr: int, n_groups: int, width: int, height: int, gains, out_ptr: int,
+                       stream_ptr: int = 0) -> None:
+        """bdpt_light_groups_relight: asynchronous, on device buffers; gains: host (n_groups, 3) float32."""
+        g = np.ascontiguousarray(gains, np.float32)
+        if g.size != 3 * int(n_groups):
+            raise BdptError(f"relight_device: gains must hold {n_groups} x 3 floats, got {g.size}")
+        _check(lib().bdpt_light_groups_relight(self._h, ctypes.c_void_p(groups_ptr), int(n_groups), int(width),
+                                               int(height), g.ctypes.data, ctypes.c_void_p(out_ptr),
+                                               ctypes.c_void_p(stream_ptr)))
 
     def denoise(self, rgb=None, aov=None, samples_done: int | None = None, **params) -> np.ndarray:
         """bdpt_denoise_host of rgb (default self.rgb) guided by aov (default self.aov): a new

@@ -7,6 +7,8 @@
 #define BDPT_TEXTURED 1
 #include <hip/hip_runtime.h>
 
+#include <cstring>
+
 #include "bdpt_path.hpp"
 
 namespace bdpt {
@@ -185,7 +187,70 @@ __global__ __launch_bounds__(256) void layers_compose_kernel(const float* __rest
     }
 }
 
+// ------------------------------------------------------------ light groups
+// out[p][c] = gains[0][c] * plane_0[p][c], then + gains[g][c] * plane_g[p][c] for g = 1 ..
+// n_groups - 1 in ascending order (planes of n = W * H * 3 floats, bdpt_render_light_groups):
+// float32, the product and the sum rounded separately (the build's -ffp-contract=off), every
+// group multiplied whatever its gain, no atomics: the same bits every run and the bits of that
+// loop on the host. The gains are a kernel argument, so a slider move is one launch and no
+// copy. A lane owns UNIT consecutive pixels, whose channels are then compile-time positions and
+// the gains wave-uniform scalars: UNIT 4 reads each plane with three 16-byte loads (n a multiple
+// of 12 and 16-byte aligned pointers: launch_relight decides), UNIT 1 with three dword loads.
+struct RelightGains {
+    float g[64][3];
+};
+template <int UNIT>
+__global__ __launch_bounds__(256) void relight_kernel(const float* __restrict__ planes, size_t n, int n_groups,
+                                                      RelightGains gains, float* __restrict__ out) {
+    constexpr int kF = 3 * UNIT;  // floats per lane and step
+    const size_t units = n / kF;
+    for (size_t u = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; u < units; u += static_cast<size_t>(gridDim.x) * 256) {
+        float acc[kF];
+        for (int g = 0; g < n_groups; g++) {  // (wave-uniform)
+            const float* src = planes + static_cast<size_t>(g) * n + u * kF;
+            float v[kF];
+            if (UNIT == 4) {
+#pragma unroll
+                for (int q = 0; q < 3; q++) {
+                    const float4 t = gld4(reinterpret_cast<const float4*>(src) + q);
+                    v[4 * q] = t.x, v[4 * q + 1] = t.y, v[4 * q + 2] = t.z, v[4 * q + 3] = t.w;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < kF; j++) v[j] = gld1(src + j);
+            }
+#pragma unroll
+            for (int j = 0; j < kF; j++) {
+                const float t = gains.g[g][j % 3] * v[j];
+                acc[j] = g == 0 ? t : acc[j] + t;
+            }
+        }
+        float* dst = out + u * kF;
+        if (UNIT == 4) {
+#pragma unroll
+            for (int q = 0; q < 3; q++)
+                gst4(reinterpret_cast<float4*>(dst) + q, make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]));
+        } else {
+#pragma unroll
+            for (int j = 0; j < kF; j++) gst1(dst + j, acc[j]);
+        }
+    }
+}
+
 }  // namespace dev
+
+// gains: n_groups x 3 floats (host). n is a multiple of 3 (W * H * 3).
+hipError_t launch_relight(const float* planes, size_t n, int n_groups, const float* gains, float* out, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    dev::RelightGains k{};
+    std::memcpy(k.g, gains, sizeof(float) * 3 * static_cast<size_t>(n_groups));
+    const bool vec = n % 12 == 0 && (reinterpret_cast<uintptr_t>(planes) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
+    const size_t units = n / (vec ? 12 : 3);
+    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((units + 255) / 256, 4096));
+    if (vec) hipLaunchKernelGGL(dev::relight_kernel<4>, dim3(blocks), dim3(256), 0, st, planes, n, n_groups, k, out);
+    else hipLaunchKernelGGL(dev::relight_kernel<1>, dim3(blocks), dim3(256), 0, st, planes, n, n_groups, k, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_layers_compose(const float* layers, size_t n, uint64_t mask, float* out, hipStream_t st) {
     if (n == 0) return hipSuccess;

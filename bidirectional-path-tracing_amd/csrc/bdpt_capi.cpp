@@ -22,7 +22,7 @@
 namespace bdpt {
 // The builds of the BDPT frame kernel (bdpt_kernels_<x>.hip; FrameBuild: bdpt_device.hpp)
 extern FrameBuild frame_build, frame_build_tex, frame_build_rr, frame_build_rrc, frame_build_deep,
-    frame_build_hbm, frame_build_split, frame_build_ng, frame_build_layers;
+    frame_build_hbm, frame_build_split, frame_build_ng, frame_build_layers, frame_build_groups;
 // sample_state.hip: the single-sample kernels (the caller's std::mt19937 state at sc.mt_ring)
 hipError_t launch_sample(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf, uint2* gstack,
                          const dev::Ray& ray, float* out, hipStream_t stream);
@@ -69,6 +69,8 @@ hipError_t launch_denoise_iter(int W, int H, int step, float inv_c, float inv_n,
                                const void* guide, const void* src, void* dst, float* out, bool last, hipStream_t st);
 // aov_kernels.hip: a masked sum of path-length layers (planes of n floats)
 hipError_t launch_layers_compose(const float* layers, size_t n, uint64_t mask, float* out, hipStream_t st);
+// aov_kernels.hip: light-group planes (n floats each) recombined with per-group RGB gains (host, n_groups x 3)
+hipError_t launch_relight(const float* planes, size_t n, int n_groups, const float* gains, float* out, hipStream_t st);
 }  // namespace bdpt
 
 using namespace bdpt;
@@ -270,6 +272,10 @@ struct bdpt_ctx : CtxStream {
     bool has_glass = false;       // a GlassBSDF material: Russian-roulette renders run bdpt_kernels_rrc.hip
     bool has_glossy = false;      // a Mixture / Phong record in the device table (after device_bsdfs)
     bool has_null = false;        // a null BSDF (illum 5): not delta, not diffuse
+    // bdpt_render_light_groups: the call's emitter -> group table (DevFrame::emitter_group) and the
+    // host copy it is uploaded from (the caller's array is not read after the call returns)
+    DevBuf<int32_t> emitter_group;
+    std::vector<int32_t> emitter_group_host;
     DevBuf<int32_t> row_order;  // bdpt_set_row_order (device copy; DevFrame::row_order)
     int32_t row_order_n = 0;    // its row count (0: top to bottom)
     DevBuf<unsigned long long> row_cost;  // counting renders: queries per local row (DevFrame::row_cost)
@@ -593,6 +599,29 @@ int bdpt_scene_get_info(const bdpt_scene* s, bdpt_scene_info* out) {
                                              L.bsdfs.size() * sizeof(BsdfRecord) +
                                              L.emitters.size() * sizeof(EmitterRecord) + L.emit_cdf.size() * 4 +
                                              L.shape_emitter.size() * 4);
+    return BDPT_OK;
+}
+
+int bdpt_scene_emitter_count(const bdpt_scene* s, int32_t* out) {
+    if (!s || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    *out = static_cast<int32_t>(s->host.emitters.size());
+    return BDPT_OK;
+}
+
+int bdpt_scene_get_emitter(const bdpt_scene* s, int32_t index, bdpt_emitter_info* out) {
+    if (!s || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    const HostScene& h = s->host;
+    if (index < 0 || static_cast<size_t>(index) >= h.emitters.size())
+        return fail(BDPT_ERR_INVALID, "bdpt_scene_get_emitter: index " + std::to_string(index) + " is outside [0, " +
+                                          std::to_string(h.emitters.size()) + ")");
+    const Emitter& e = h.emitters[static_cast<size_t>(index)];
+    out->shape = e.shape;
+    // the material of the shape's first face: the one whose emission makes the shape an emitter (scene.cpp)
+    out->material = -1;
+    if (e.shape >= 0 && static_cast<size_t>(e.shape) < h.shape_first.size() && h.shape_count[e.shape] > 0)
+        out->material = h.tri_mat[static_cast<size_t>(h.shape_first[e.shape])];
+    out->area = e.area;
+    for (int k = 0; k < 3; k++) out->radiance[k] = e.radiance[k];
     return BDPT_OK;
 }
 
@@ -1007,16 +1036,39 @@ static const FrameBuild& pick_frame_build(const bdpt_ctx* c, const bdpt_frame_pa
     return frame_build;
 }
 
-// Path-length layers (bdpt_render_layers): what the one build that writes
-// them (bdpt_kernels_layers.hip) serves. Called after check_params, before any launch.
+// A frame kept as several planes: split by path length (bdpt_render_layers,
+// bdpt_kernels_layers.hip) or by emitter group (bdpt_render_light_groups, bdpt_kernels_groups.hip).
+// kNone: the plain frame.
 constexpr int kMaxLayers = 64;  // a layer mask is one 64-bit word (bdpt_layers_compose)
-static int check_layers(const bdpt_ctx* c, const bdpt_frame_params* p, int n_layers) {
-    if (n_layers < 1 || n_layers > kMaxLayers)
-        return fail(BDPT_ERR_INVALID, "bdpt_render_layers: n_layers must be in [1, 64]");
+constexpr int kMaxGroups = 64;  // the relight kernel's gains are a kernel argument (bdpt_light_groups_relight)
+struct Planes {
+    enum Kind { kNone, kLayers, kGroups } kind = kNone;
+    int n = 1;                               // planes in the framebuffer
+    const int32_t* group_of_emitter = nullptr;  // kGroups: the caller's host map (null: identity)
+};
+
+// What the two plane builds serve, checked after check_params and before any launch; the
+// messages name the entry point and its count (n_layers / n_groups).
+static int check_planes(const bdpt_ctx* c, const bdpt_frame_params* p, const Planes& pl) {
+    const bool groups = pl.kind == Planes::kGroups;
+    const std::string entry = groups ? "bdpt_render_light_groups" : "bdpt_render_layers";
+    const std::string count = groups ? "n_groups" : "n_layers";
+    if (pl.n < 1 || pl.n > (groups ? kMaxGroups : kMaxLayers))
+        return fail(BDPT_ERR_INVALID, entry + ": " + count + " must be in [1, 64]");
     // a contribution's plane and pixel travel as one index in the task record's 30-bit pixel field
-    if (static_cast<int64_t>(n_layers) * p->width * p->height >= (int64_t{1} << 30))
-        return fail(BDPT_ERR_INVALID, "bdpt_render_layers: n_layers * W * H must be below 2^30 (the shadow-ray task "
+    if (static_cast<int64_t>(pl.n) * p->width * p->height >= (int64_t{1} << 30))
+        return fail(BDPT_ERR_INVALID, entry + ": " + count + " * W * H must be below 2^30 (the shadow-ray task "
                                       "record's pixel field)");
+    if (groups) {
+        const int nemit = c->sc.nemit;
+        if (!pl.group_of_emitter && pl.n != nemit)
+            return fail(BDPT_ERR_INVALID, entry + ": a null group_of_emitter is the identity map and needs n_groups equal "
+                                          "to the emitter count (" + std::to_string(nemit) + "), got " + std::to_string(pl.n));
+        for (int e = 0; pl.group_of_emitter && e < nemit; e++)
+            if (pl.group_of_emitter[e] < 0 || pl.group_of_emitter[e] >= pl.n)
+                return fail(BDPT_ERR_INVALID, entry + ": group_of_emitter[" + std::to_string(e) + "] = " +
+                                              std::to_string(pl.group_of_emitter[e]) + " is outside [0, n_groups)");
+    }
     const char* what = p->flags != 0                              ? "with flags (a counting pass or full traversal)"
                        : p->russian_roulette != BDPT_RR_NONE      ? "with Russian roulette"
                        : p->rr_depth > kLazyRrDepth               ? "with rr_depth > 28"
@@ -1024,28 +1076,26 @@ static int check_layers(const bdpt_ctx* c, const bdpt_frame_params* p, int n_lay
                        : c->sc.lds_bsdf_off == dev::kNoLds        ? "with the BSDF records in HBM (too many materials "
                                                                     "for the LDS table)"
                                                                   : nullptr;
-    if (what) return fail(BDPT_ERR_UNSUPPORTED, std::string("path-length layers are not built ") + what);
+    if (what) return fail(BDPT_ERR_UNSUPPORTED, std::string(groups ? "light groups" : "path-length layers") + " are not built " + what);
     return BDPT_OK;
 }
 
-// bdpt_render and the BDPT form of bdpt_render_window (w null: every sample); n_layers other
-// than kNoLayers: bdpt_render_layers (fb is n_layers planes, the layers build; check_layers
-// refuses a bad count).
-constexpr int kNoLayers = -1;
+// bdpt_render and the BDPT form of bdpt_render_window (w null: every sample); with planes:
+// bdpt_render_layers / bdpt_render_light_groups (fb is pl.n planes, that build; check_planes
+// refuses what it does not serve).
 static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* fb,
-                       void* hip_stream, int n_layers = kNoLayers) {
+                       void* hip_stream, const Planes& pl = Planes{}) {
     if (!c || !fb) return fail(BDPT_ERR_INVALID, "null argument");
     int rc = check_params(p);
     if (rc) return rc;
     if ((rc = check_window(p, w))) return rc;
-    const bool layered = n_layers != kNoLayers;
-    if (layered && (rc = check_layers(c, p, n_layers))) return rc;
+    if (pl.kind != Planes::kNone && (rc = check_planes(c, p, pl))) return rc;
     if ((rc = textured_frame_check(c, p))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     dev::DevFrame fr = make_frame(p, w);
     fr.capped = c->capped;
-    fr.n_layers = layered ? n_layers : 0;
+    fr.n_layers = pl.kind == Planes::kLayers ? pl.n : 0;
     if (!fr.rr_mode && fr.total_samples > 0 && (rc = ensure_tasks(c))) return rc;
     fr.tasks = c->tasks;
     fr.task_cap = c->task_cap;
@@ -1077,6 +1127,16 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
         sc.mt_ring_stride = 1;  // slot-major blocks of kMtRingSlotWords words (DevScene::mt_ring)
     }
     if ((rc = begin_use(c, st))) return rc;
+    if (pl.kind == Planes::kGroups) {  // the call's table, from the context's own host copy, in stream order
+        const size_t nemit = static_cast<size_t>(c->sc.nemit);
+        c->emitter_group_host.resize(nemit);
+        for (size_t e = 0; e < nemit; e++)
+            c->emitter_group_host[e] = pl.group_of_emitter ? pl.group_of_emitter[e] : static_cast<int32_t>(e);
+        HIP_TRY(c->emitter_group.reserve(std::max<size_t>(nemit * sizeof(int32_t), 16)));
+        HIP_TRY(hipMemcpyAsync(c->emitter_group, c->emitter_group_host.data(), nemit * sizeof(int32_t),
+                               hipMemcpyHostToDevice, st));
+        fr.emitter_group = c->emitter_group;
+    }
     HIP_TRY(hipMemsetAsync(c->work, 0, sizeof(unsigned long long), st));
     // BDPT_SAMPLE_RANGE="lo,hi" (debugging aid, tools/rr_find.py): only the shard's
     // samples [lo, hi) — the work counter starts at lo and the frame ends at hi
@@ -1102,7 +1162,9 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
     if ((rc = begin_timed(c, st))) return rc;
     int64_t launches = 0;
     if (fr.total_samples > 0) {
-        const FrameBuild& b = layered ? frame_build_layers : pick_frame_build(c, p);
+        const FrameBuild& b = pl.kind == Planes::kLayers   ? frame_build_layers
+                              : pl.kind == Planes::kGroups ? frame_build_groups
+                                                           : pick_frame_build(c, p);
         c->last_kernel_glossy = 1;  // (until the launches below have succeeded)
         // Never more resident blocks than the slots allocated. c->grid is the default build's
         // blocks_per_cu of these LDS bytes (the HBM build's on an HBM table; bdpt_ctx_create),
@@ -1144,7 +1206,35 @@ int bdpt_render(bdpt_ctx* c, const bdpt_frame_params* p, float* fb, void* hip_st
 
 int bdpt_render_layers(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_layers,
                        float* fb_layers, void* hip_stream) {
-    return render_bdpt(c, p, w, fb_layers, hip_stream, n_layers == kNoLayers ? 0 : n_layers);  // (both: a bad count)
+    return render_bdpt(c, p, w, fb_layers, hip_stream, Planes{Planes::kLayers, n_layers});
+}
+
+int bdpt_render_light_groups(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_groups,
+                             const int32_t* group_of_emitter, float* fb_groups, void* hip_stream) {
+    return render_bdpt(c, p, w, fb_groups, hip_stream, Planes{Planes::kGroups, n_groups, group_of_emitter});
+}
+
+int bdpt_light_groups_relight(bdpt_ctx* c, const float* fb_groups, int32_t n_groups, int32_t width, int32_t height,
+                              const float* gains, float* out, void* hip_stream) {
+    if (!c || !fb_groups || !gains || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    if (n_groups < 1 || n_groups > kMaxGroups)
+        return fail(BDPT_ERR_INVALID, "bdpt_light_groups_relight: n_groups must be in [1, 64]");
+    if (width <= 0 || height <= 0 || static_cast<int64_t>(n_groups) * width * height >= (int64_t{1} << 30))
+        return fail(BDPT_ERR_INVALID, "bdpt_light_groups_relight: width/height must be > 0 and n_groups * W * H below 2^30");
+    for (int i = 0; i < 3 * n_groups; i++)
+        if (!std::isfinite(gains[i]))
+            return fail(BDPT_ERR_INVALID, "bdpt_light_groups_relight: gains[" + std::to_string(i / 3) + "][" +
+                                              std::to_string(i % 3) + "] is not finite");
+    const size_t n = static_cast<size_t>(width) * height * 3;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(fb_groups), o = reinterpret_cast<uintptr_t>(out);
+    if (o < a + n * n_groups * sizeof(float) && a < o + n * sizeof(float))
+        return fail(BDPT_ERR_INVALID, "bdpt_light_groups_relight: out overlaps the planes");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if (int rc = begin_use(c, st)) return rc;
+    if (int rc = begin_timed(c, st)) return rc;
+    HIP_TRY(launch_relight(fb_groups, n, n_groups, gains, out, st));
+    return end_timed(c, st, 0, 1);
 }
 
 int bdpt_layers_compose(bdpt_ctx* c, const float* fb_layers, int32_t n_layers, int32_t width, int32_t height,
@@ -1533,15 +1623,14 @@ int bdpt_synchronize(bdpt_ctx* c) {
 }
 
 static int render_bdpt_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* fb_host,
-                            int n_layers = kNoLayers) {
+                            const Planes& pl = Planes{}) {
     if (!c || !fb_host) return fail(BDPT_ERR_INVALID, "null argument");
     int rc = check_params(p);
     if (rc) return rc;
     if ((rc = check_window(p, w))) return rc;
-    const bool layered = n_layers != kNoLayers;
-    if (layered && (rc = check_layers(c, p, n_layers))) return rc;  // before the planes are staged
-    if ((rc = stage_host(c, fb_host, static_cast<size_t>(p->width) * p->height * 3 * (layered ? n_layers : 1),
-                         [&](float* fb) { return render_bdpt(c, p, w, fb, c->stream, n_layers); })))
+    if (pl.kind != Planes::kNone && (rc = check_planes(c, p, pl))) return rc;  // before the planes are staged
+    if ((rc = stage_host(c, fb_host, static_cast<size_t>(p->width) * p->height * 3 * pl.n,
+                         [&](float* fb) { return render_bdpt(c, p, w, fb, c->stream, pl); })))
         return rc;
     {
         bdpt_stats st;
@@ -1564,7 +1653,12 @@ int bdpt_render_host(bdpt_ctx* c, const bdpt_frame_params* p, float* fb_host) {
 
 int bdpt_render_layers_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_layers,
                             float* fb_layers_host) {
-    return render_bdpt_host(c, p, w, fb_layers_host, n_layers == kNoLayers ? 0 : n_layers);  // (both: a bad count)
+    return render_bdpt_host(c, p, w, fb_layers_host, Planes{Planes::kLayers, n_layers});
+}
+
+int bdpt_render_light_groups_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                                  int32_t n_groups, const int32_t* group_of_emitter, float* fb_groups_host) {
+    return render_bdpt_host(c, p, w, fb_groups_host, Planes{Planes::kGroups, n_groups, group_of_emitter});
 }
 
 // Sample windows: the three integrators' frame entries with a window (null: the whole

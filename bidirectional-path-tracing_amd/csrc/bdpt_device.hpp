@@ -204,7 +204,15 @@ struct DevFrame {
     // the shard's row claim order (bdpt_set_row_order; null: top to bottom) and, in a
     // counting pass, the queries issued per local row (null otherwise)
     const int32_t* row_order;
-    unsigned long long* row_cost;
+    // light groups (bdpt_render_light_groups, the bdpt_kernels_groups.hip build): the framebuffer
+    // is n_groups consecutive W x H x 3 planes and a contribution goes to plane emitter_group[e]
+    // of the emitter e its path ends on (one int32 per emitter, each in [0, n_groups)). It shares
+    // row_cost's word, so the record and every other build's code stay as they were: a grouped
+    // render is never a counting pass (flags are refused) and no other build reads it.
+    union {
+        unsigned long long* row_cost;
+        const int32_t* emitter_group;
+    };
     // sample window (bdpt_render_window): of each pixel's spp samples only k = win_first +
     // i * win_stride, 0 <= i < win_count, are rendered (the whole frame: 0, 1, spp); seeds,
     // inv_spp and camera_dir's spp == 1 rule keep the frame's full spp

@@ -69,22 +69,59 @@ __device__ __forceinline__ float rr_probability(const DevFrame& fr, int depth, f
 // A stored light vertex's depth is not its index in the store (delta vertices are walked
 // but not stored), so the record carries it in its rr word, which these NO_RR = 1 builds
 // never read (BDPT_LV_TAG). Every line of this compiles out with BDPT_LAYERS 0.
+//
+// Light groups (BDPT_GROUPS 1: bdpt_kernels_groups.hip): the same planes and
+// the same travelling index, but the plane is DevFrame::emitter_group[e] of the emitter e at
+// the light end of the contribution's path:
+//   eye walk hits an emitter (s = 0)   e = shape_emitter_of(the hit shape)
+//   connectToLight (s = 1)             e = the emitter that call sampled
+//   connectVertices, connectToCamera   e = the emitter the sample's light subpath started on
+// The light subpath's group is looked up once, at its start, and kept in LaneCold::pure for
+// the length of the light walk (isPathPureSpecular belongs to the eye walk, whose prologue
+// sets it); every stored light vertex carries it in its rr word (BDPT_LV_TAG) to the eye
+// walk's connections. Every line of this compiles out with BDPT_GROUPS 0.
 #ifndef BDPT_LAYERS
 #define BDPT_LAYERS 0
 #endif
-#if BDPT_LAYERS
-#if BDPT_RR || (defined(BDPT_SAMPLER_STATE) && BDPT_SAMPLER_STATE)
-#error "BDPT_LAYERS: the frame kernel without Russian roulette only"
+#ifndef BDPT_GROUPS
+#define BDPT_GROUPS 0
 #endif
+#define BDPT_PLANES (BDPT_LAYERS || BDPT_GROUPS)  // the framebuffer is several planes; no per-sample sum
+#if BDPT_PLANES
+#if BDPT_RR || (defined(BDPT_SAMPLER_STATE) && BDPT_SAMPLER_STATE) || (BDPT_LAYERS && BDPT_GROUPS)
+#error "BDPT_LAYERS / BDPT_GROUPS: one of them, in the frame kernel without Russian roulette only"
+#endif
+#endif
+// BDPT_PLANE_PX(fr, k, g, pixel): the index a contribution of a k-edge path lit by group g is
+// added at (each build reads the one it files by; the plain builds neither).
+// BDPT_LV_TAG(rr, depth, g): a stored light vertex's rr word.
+#if BDPT_LAYERS
 __device__ __forceinline__ int layer_index(const DevFrame& fr, int k, int pixel) {
     const int plane = max(0, min(k - 1, fr.n_layers - 1));
     return plane * (fr.W * fr.H) + pixel;  // < 2^30 (bdpt_render_layers checks n_layers * W * H)
 }
-#define BDPT_LAYER_PX(fr, k, pixel) layer_index(fr, k, pixel)
-#define BDPT_LV_TAG(rr, depth) __int_as_float(depth)
+#define BDPT_PLANE_PX(fr, k, g, pixel) layer_index(fr, k, pixel)
+#define BDPT_LV_TAG(rr, depth, g) __int_as_float(depth)
+#elif BDPT_GROUPS
+// emitter_group holds one entry in [0, n_groups) per emitter (bdpt_render_light_groups checks);
+// a hit shape that is no emitter (e < 0: its contribution is zero) reads nothing.
+__device__ __forceinline__ int group_of_emitter(const DevFrame& fr, int e) {
+    return e < 0 ? 0 : static_cast<int>(((const gbl_i32*)fr.emitter_group)[e]);
+}
+// the emitter of a primary hit kept as its triangle (light tracing; shade record: bdpt_types.h)
+__device__ __forceinline__ int prim_emitter(const DevScene& sc, int tri) {
+    return shape_emitter_of(sc, shape_id(__float_as_int(gld4(sc.shade + kShadeStride * static_cast<size_t>(tri) + 1).w)));
+}
+__device__ __forceinline__ int group_index(const DevFrame& fr, int g, int pixel) {
+    return g * (fr.W * fr.H) + pixel;  // < 2^30 (bdpt_render_light_groups checks n_groups * W * H)
+}
+#define BDPT_PLANE_PX(fr, k, g, pixel) group_index(fr, g, pixel)
+#define BDPT_LV_TAG(rr, depth, g) __int_as_float(g)
+#define BDPT_GROUP_OF(fr, e) group_of_emitter(fr, e)
+#define BDPT_LIGHT_GROUP(L) static_cast<int>((L).c.pure)  // the light subpath's group, during its walk
 #else
-#define BDPT_LAYER_PX(fr, k, pixel) (pixel)
-#define BDPT_LV_TAG(rr, depth) (rr)
+#define BDPT_PLANE_PX(fr, k, g, pixel) (pixel)
+#define BDPT_LV_TAG(rr, depth, g) (rr)
 #endif
 
 // Light-vertex scratch, one contiguous record per lane: vertex v of slot s is
@@ -437,7 +474,7 @@ __device__ __forceinline__ bool task_push(const LaneCold&, const DevFrame&, f3, 
 constexpr bool kTasks = BDPT_HELP && !BDPT_SAMPLER_STATE;
 
 // An eye-estimate addition for the pixel: the wave's slot when it holds the pixel, else the framebuffer.
-// BDPT_LAYERS: `pixel` is a layered index (layer_index). A plane-0 index equals the plain pixel
+// BDPT_PLANES: `pixel` is a plane index (layer_index / group_index). A plane-0 index equals the plain pixel
 // and uses the slot as before (the slot's flush, eye_slot_reset, writes plane 0); an index of
 // another plane matches no slot (slots hold pixels < W * H) and goes to the framebuffer.
 __device__ __forceinline__ void eye_add(float* __restrict__ fb, int pixel, f3 add) {
@@ -460,7 +497,7 @@ __device__ __forceinline__ void eye_add(float* __restrict__ fb, int pixel, f3 ad
     gadd(px + 2, add.z);
 }
 
-#if BDPT_LAYERS
+#if BDPT_PLANES
 // A term the default build sums in L.c.Li (the s = 0 emission, a connection the owner traced
 // itself): to the plane `px` names at once, scaled as finish() scales the sample's sum.
 __device__ __forceinline__ void layer_add(const DevFrame& fr, float* __restrict__ fb, int px, f3 c) {
@@ -469,9 +506,9 @@ __device__ __forceinline__ void layer_add(const DevFrame& fr, float* __restrict_
 #endif
 
 // The unoccluded connection the lane traced itself (ST_NEE / ST_CONN; with tasks: the ring was
-// full): into the sample's sum, or (layers) to its plane (pend_px) at once.
+// full): into the sample's sum, or (layers, light groups) to its plane (pend_px) at once.
 __device__ __forceinline__ void add_pending(Lane& L, const DevFrame& fr, float* __restrict__ fb) {
-#if BDPT_LAYERS
+#if BDPT_PLANES
     layer_add(fr, fb, L.c.pend_px, L.c.pend);
 #else
     (void)fr, (void)fb;
@@ -489,7 +526,7 @@ __device__ __forceinline__ void finish(Lane& L, const DevFrame& fr, float* __res
             gadd(fr.row_cost + (L.c.pixel / fr.W - fr.row_offset) / fr.row_stride,
                  static_cast<unsigned long long>(L.c.steps));
     }
-#if !BDPT_LAYERS  // (layers: every contribution was added to its plane where it was formed; no per-sample sum)
+#if !BDPT_PLANES  // (layers, light groups: every contribution was added to its plane where it was formed; no per-sample sum)
     // rgb[p] += acc * (1 / spp) (renderer.cpp:202), one sample at a time.
     if (!(fr.flags & kFlagNoEyeAccum) && (L.c.Li.x != 0.f || L.c.Li.y != 0.f || L.c.Li.z != 0.f)) {
         const float inv_spp = fr.inv_spp;  // 1.f / spp
@@ -601,7 +638,7 @@ __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
         const float lightWeight = div_w(reversePdf_a, nlight) * (L.c.vcm + prevRev * L.c.vc); \
         const float mis = rcp_w(lightWeight + 1.f + 0.f); \
         const f3 pend_ = (fr.strategy == 0) ? rad * mis : rad; \
-        const int px_ = BDPT_LAYER_PX(fr, L.c.depth + 1, yp * fr.W + xp);  /* t = 1: k = depth_light + 1 */ \
+        const int px_ = BDPT_PLANE_PX(fr, L.c.depth + 1, BDPT_LIGHT_GROUP(L), yp * fr.W + xp);  /* t = 1: k = depth_light + 1 */ \
         /* a helper walks it and forms its ray from the camera and L.h.p (act: A_LIGHT_CONTINUE) */ \
         if (kTasks && task_push(L.c, fr, cam_o, L.h.p, false, pend_, px_, true, cnt)) break; \
         L.c.pend = pend_; \
@@ -619,7 +656,7 @@ __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
         const float rrp = rr_on(fr) ? L.c.rr : 1.f; \
         /* the store is full: the vertex would be pushed only if the walk continues (bdpt.h:211-215) */ \
         const bool full = rr_on(fr) && light && !delta && L.c.nl >= fr.lv_max; \
-        if (light && !delta && !full) store_vertex(ls, L.c.nl, L.h, L.c.tp, L.c.vcm, L.c.vc, BDPT_LV_TAG(rrp, L.c.depth));  /* the pre-walk state */ \
+        if (light && !delta && !full) store_vertex(ls, L.c.nl, L.h, L.c.tp, L.c.vcm, L.c.vc, BDPT_LV_TAG(rrp, L.c.depth, BDPT_LIGHT_GROUP(L)));  /* the pre-walk state */ \
         const bool more = continue_walk(b, L.h, L.rng, L.c.tp, L.c.depth, L.c.vc, L.c.vcm, L.ray, rrp); \
         if (full && more) {  /* it would be stored: flag the sample, end the light walk */ \
             gadd(fr.capped, 1u); \
@@ -678,8 +715,8 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
         if (fr.strategy == 1) {  // LIGHT_TRACING: Li = Le at the primary hit (bdpt.h:231)
             const int mat = __float_as_int(gld4(sc.shade + kShadeStride * static_cast<size_t>(L.c.prim_tri)).w);
             L.c.Li = ld3(bsdf_of(sc, mat).emission);
-#if BDPT_LAYERS  // the camera ray's own emitter hit: k = 1
-            layer_add(fr, fb, BDPT_LAYER_PX(fr, 1, L.c.pixel), L.c.Li);
+#if BDPT_PLANES  // the camera ray's own emitter hit: k = 1, lit by the emitter of the hit shape
+            layer_add(fr, fb, BDPT_PLANE_PX(fr, 1, BDPT_GROUP_OF(fr, prim_emitter(sc, L.c.prim_tri)), L.c.pixel), L.c.Li);
 #endif
             act = A_FINISH;
             break;
@@ -714,7 +751,7 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
         const f3 emission = ld3(b.emission);  // getEmission = materials[matID].emission
         if (!is_zero(emission)) {
             const int eid = shape_emitter_of(sc, shape_id(L.h.shape));
-#if BDPT_LAYERS  // L.c.Li is zero here (nothing sums in it): after the block it holds this term alone
+#if BDPT_PLANES  // L.c.Li is zero here (nothing sums in it): after the block it holds this term alone
             L.c.Li = mk(0.f, 0.f, 0.f);
 #endif
             if (eid >= 0) {  // (the reference asserts otherwise, integrator.cpp:56)
@@ -735,8 +772,8 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
                     L.c.Li = L.c.Li + emission;
                 }
             }
-#if BDPT_LAYERS  // s = 0: k = depth_eye
-            layer_add(fr, fb, BDPT_LAYER_PX(fr, L.c.depth, L.c.pixel), L.c.Li);
+#if BDPT_PLANES  // s = 0: k = depth_eye, lit by the emitter hit
+            layer_add(fr, fb, BDPT_PLANE_PX(fr, L.c.depth, BDPT_GROUP_OF(fr, eid), L.c.pixel), L.c.Li);
 #endif
             act = A_FINISH;
             break;
@@ -775,6 +812,9 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
         L.c.vcm = div_w(areaPdf, emissionPdf);
         L.c.nl = 0;
         L.c.depth = 1;
+#if BDPT_GROUPS  // the light subpath's group, for its camera connections and its stored vertices
+        L.c.pure = static_cast<uint32_t>(BDPT_GROUP_OF(fr, e_id));
+#endif
         if (rr_on(fr)) L.c.rr = 1.f;  // bdpt.h:187
         if (edir.z <= 0.f) {  // bdpt.h:179-182 (the eye subpath follows)
             L.state = ST_DEFER;
@@ -810,10 +850,10 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
         const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
         const f3 pend = (fr.strategy == 0) ? Li * mis : Li;
         const Ray sr = shadow_ray(L.h.p, e_p);
-        const int px = BDPT_LAYER_PX(fr, L.c.depth + 1, L.c.pixel);  // s = 1: k = depth_eye + 1
+        const int px = BDPT_PLANE_PX(fr, L.c.depth + 1, BDPT_GROUP_OF(fr, e_id), L.c.pixel);  // s = 1: k = depth_eye + 1
         if (kTasks && task_push(L.c, fr, L.h.p, e_p, vertex_nocull(L, sr.d), pend * fr.inv_spp, px, false, cnt))
             break;  // a helper walks it (act: A_CONN)
-#if BDPT_LAYERS
+#if BDPT_PLANES
         L.c.pend_px = px;  // the ring is full: the owner traces it, resolve() adds it to this plane
 #endif
         L.c.pend = pend;
@@ -860,13 +900,13 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
             const float eyeWeight = eyePathRev_a * (L.c.vcm + eyePrevRev * L.c.vc);
             const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
             const Ray sr = shadow_ray(L.h.p, V.p);
-            // s >= 2, t >= 2: k = depth_eye + depth_light + 1 (the stored vertex's depth: BDPT_LV_TAG)
-            const int px = BDPT_LAYER_PX(fr, L.c.depth + __float_as_int(V.rr) + 1, L.c.pixel);
+            // s >= 2, t >= 2: k = depth_eye + depth_light + 1 (the stored vertex's depth or group: BDPT_LV_TAG)
+            const int px = BDPT_PLANE_PX(fr, L.c.depth + __float_as_int(V.rr) + 1, __float_as_int(V.rr), L.c.pixel);
             if (kTasks && task_push(L.c, fr, L.h.p, V.p, vertex_nocull(L, sr.d), (Li * mis) * fr.inv_spp, px, false, cnt)) {
                 L.c.ci++;  // a helper walks it; the next light vertex now
                 continue;
             }
-#if BDPT_LAYERS
+#if BDPT_PLANES
             L.c.pend_px = px;  // the ring is full: the owner traces it, resolve() adds it to this plane
 #endif
             L.c.pend = Li * mis;
@@ -975,7 +1015,7 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
         const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
         const Ray sr = shadow_ray(hp, V.p);
         task_push(L.c, fr, hp, V.p, graze_exempt(sr.d, hn, hshape), (Li * mis) * fr.inv_spp,
-                  BDPT_LAYER_PX(fr, oc.depth + __float_as_int(V.rr) + 1, oc.pixel), false, cnt);
+                  BDPT_PLANE_PX(fr, oc.depth + __float_as_int(V.rr) + 1, __float_as_int(V.rr), oc.pixel), false, cnt);
     }
     if (k > 0) L.c.ci = L.c.nl;
 }

@@ -26,6 +26,11 @@
 // by path length (bdpt_render_layers_host: layer l holds the paths of l + 1 edges, the last one
 // everything longer; a second render, so the main EXR is the same bytes with or without it). A
 // malformed N is refused before any device is used; with several devices the first renders them.
+// --light-groups (a bdpt scene of at most 64 emitters) also writes <out stem>.E00.exr ..., the frame
+// split by emitter under the identity map (bdpt_render_light_groups_host: file e holds the paths
+// that end on emitter e of bdpt_scene_get_emitter; a second render, so the main EXR is the same
+// bytes with or without it). Refused for path / direct scenes before any device is used; with
+// several devices the first renders the groups.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -80,7 +85,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Syntax: %s <scene.toml> [nogui] [--width W --height H --spp N --rr D --device K "
                              "--out FILE.exr --seed S --gpus N --devices a,b,... --shard samples|rows "
-                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N]\n", argv[0]);
+                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string toml = argv[1];
@@ -94,6 +99,7 @@ int main(int argc, char** argv) {
     bool want_aov = false, want_denoise = false;
     int denoise_iterations = BDPT_DENOISE_ITERATIONS;
     int layers = 0;  // --layers N (0: none)
+    bool light_groups = false;  // --light-groups
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -155,6 +161,8 @@ int main(int argc, char** argv) {
                 return EXIT_FAILURE;
             }
             layers = static_cast<int>(n);
+        } else if (a == "--light-groups") {
+            light_groups = true;
         } else if (a == "--gpus") {
             const int n = std::atoi(next("--gpus"));
             devices.clear();
@@ -205,6 +213,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--layers splits a bdpt frame (integrator type \"%s\" has no layers)\n", cfg.integrator);
         return EXIT_FAILURE;
     }
+    if (light_groups && (path || direct)) {
+        std::fprintf(stderr, "--light-groups splits a bdpt frame (integrator type \"%s\" has no light groups)\n",
+                     cfg.integrator);
+        return EXIT_FAILURE;
+    }
     if (W > 0) cfg.width = W;
     if (H > 0) cfg.height = H;
     if (spp > 0) cfg.spp = spp;
@@ -218,6 +231,15 @@ int main(int argc, char** argv) {
 
     bdpt_scene* scene = nullptr;
     if (bdpt_scene_load_obj(cfg.obj_file, &scene) != BDPT_OK) return die("Scene::load");
+    int32_t n_emitters = 0;
+    if (light_groups) {  // one plane per emitter: refused before any device is used
+        if (bdpt_scene_emitter_count(scene, &n_emitters) != BDPT_OK) return die("bdpt_scene_emitter_count");
+        if (n_emitters > 64) {
+            std::fprintf(stderr, "--light-groups: the scene has %d emitters, one plane each is built for at most 64\n",
+                         n_emitters);
+            return EXIT_FAILURE;
+        }
+    }
     bdpt_ctx* ctx = nullptr;
     bdpt_multi* multi = nullptr;
     if (!devices.empty()) {
@@ -321,6 +343,23 @@ int main(int argc, char** argv) {
             std::printf("Saved EXR image to %s\n", side.c_str());
         }
         if (lctx != ctx) bdpt_ctx_destroy(lctx);
+    }
+    if (light_groups) {
+        bdpt_ctx* gctx = ctx;  // several devices: the first renders the groups
+        if (!gctx && bdpt_ctx_create(scene, devices[0], &gctx) != BDPT_OK) return die("bdpt_ctx_create (light groups)");
+        const size_t plane = static_cast<size_t>(cfg.width) * cfg.height * 3;
+        std::vector<float> planes(plane * n_emitters, 0.f);
+        if (bdpt_render_light_groups_host(gctx, &p, win, n_emitters, nullptr, planes.data()) != BDPT_OK)
+            return die("bdpt_render_light_groups_host");
+        for (int e = 0; e < n_emitters; e++) {
+            char suffix[16];
+            std::snprintf(suffix, sizeof suffix, ".E%02d", e);
+            const std::string side = side_path(exr, suffix);
+            if (bdpt_save_exr(planes.data() + plane * e, cfg.width, cfg.height, side.c_str()) != BDPT_OK)
+                return die("saveEXR");
+            std::printf("Saved EXR image to %s\n", side.c_str());
+        }
+        if (gctx != ctx) bdpt_ctx_destroy(gctx);
     }
     if (multi) bdpt_multi_destroy(multi);
     if (ctx) bdpt_ctx_destroy(ctx);

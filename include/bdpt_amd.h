@@ -177,6 +177,18 @@ const char* bdpt_version(void);
 int bdpt_scene_load_obj(const char* obj_path, bdpt_scene** out);
 int bdpt_scene_free(bdpt_scene* scene);
 int bdpt_scene_get_info(const bdpt_scene* scene, bdpt_scene_info* out);
+/* (new) The scene's emitters in Scene::emitters order: index i is what selectEmitter draws, what
+ * BDPT_SAMPLING_EMITTER returns and what bdpt_render_light_groups' group_of_emitter is indexed by.
+ * shape: the emitting shape's id; material: the material of its first face (the one whose Ke makes
+ * it an emitter), an index into the MTL's materials in file order; area: the sum of its faces'
+ * areas; radiance: that material's Ke. BDPT_ERR_INVALID: index outside [0, count). */
+typedef struct bdpt_emitter_info {
+    int32_t shape, material;
+    float area;
+    float radiance[3];
+} bdpt_emitter_info;
+int bdpt_scene_emitter_count(const bdpt_scene* scene, int32_t* count);
+int bdpt_scene_get_emitter(const bdpt_scene* scene, int32_t index, bdpt_emitter_info* out);
 /* Reference-layout export (tests): tri_f32[ntri][18] = v0 v1 v2 n0 n1 n2 in BVH
  * leaf order, tri_i32[ntri][3] = shapeID primID matID, node_f32[nnodes][6] =
  * bbox min/max, node_u32[nnodes][3] = start nPrims rightOffset (flat preorder). */
@@ -529,6 +541,40 @@ int bdpt_render_layers_host(bdpt_ctx* ctx, const bdpt_frame_params* params, cons
  * outside 1..64 or n_layers * width * height >= 2^30. Asynchronous on `hip_stream`. */
 int bdpt_layers_compose(bdpt_ctx* ctx, const float* fb_layers_device, int32_t n_layers, int32_t width,
                         int32_t height, uint64_t mask, float* out_device, void* hip_stream);
+
+/* ---- light groups: one BDPT frame split by emitter, and relit without tracing again ---- */
+/* (new) Not in the reference. Every contribution the BDPT frame kernel forms ends on one emitter e:
+ * the emitter the eye walk hit (s = 0; light tracing: the camera ray's own hit), the one connectToLight
+ * sampled (s = 1), or the one the sample's light subpath started on (connectVertices, connectToCamera).
+ * bdpt_render_light_groups renders what bdpt_render_window (path = direct = NULL) renders - the same
+ * paths, the same contribution values - but ADDS each contribution to plane group_of_emitter[e] of
+ * fb_groups, n_groups consecutive width * height * 3 planes; the planes sum to bdpt_render's frame (up
+ * to the order of the float additions; with n_groups = 1 the plane is the frame). group_of_emitter is a
+ * HOST array of one int32 per emitter (bdpt_scene_emitter_count; copied before the call returns), NULL
+ * = the identity, one plane per emitter. Without Russian roulette a contribution is linear in its
+ * emitter's radiance and no path or weight depends on a radiance, so the planes recombined with
+ * per-group gains (bdpt_light_groups_relight) are the frame of the scene with those emitters' Ke scaled.
+ * window NULL = the whole frame; row shards and bdpt_set_row_order work as in bdpt_render.
+ * BDPT_ERR_INVALID (the message names the field): n_groups outside 1..64, n_groups * width * height >=
+ * 2^30, a map entry outside [0, n_groups), a NULL map with n_groups other than the emitter count.
+ * BDPT_ERR_UNSUPPORTED (the message says "light groups"), before any launch: flags != 0, Russian
+ * roulette, rr_depth > 28, a scene with bitmap textures, BSDF records in HBM. bdpt_last_kernel
+ * afterwards: "bdpt_frame_kernel_groups". Asynchronous on `hip_stream` like bdpt_render; the host form
+ * stages the caller's n_groups * width * height * 3 floats and is synchronous. */
+int bdpt_render_light_groups(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                             int32_t n_groups, const int32_t* group_of_emitter, float* fb_groups_device,
+                             void* hip_stream);
+int bdpt_render_light_groups_host(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                                  int32_t n_groups, const int32_t* group_of_emitter, float* fb_groups_host);
+/* (new) out[p][c] = gains[0][c] * plane_0[p][c], then + gains[g][c] * plane_g[p][c] for g = 1 ..
+ * n_groups - 1 in ascending order: float32, each product and each sum rounded on its own (no fma), every
+ * group multiplied whatever its gain, no atomics - the bits of that loop, the same every run. `gains`
+ * is a HOST array of n_groups x 3 floats and travels as a kernel argument (one launch per call);
+ * the planes and out are device pointers, out is width * height * 3 floats and must not overlap the
+ * planes. BDPT_ERR_INVALID: n_groups outside 1..64, n_groups * width * height >= 2^30, overlap, a gain
+ * that is not finite. Asynchronous on `hip_stream`. */
+int bdpt_light_groups_relight(bdpt_ctx* ctx, const float* fb_groups_device, int32_t n_groups, int32_t width,
+                              int32_t height, const float* gains, float* out_device, void* hip_stream);
 
 /* ---- several HIP devices in one process ---- */
 /* The reference fans the offline loop out over host threads (parallel_for,
