@@ -264,8 +264,11 @@ def lib():
         L.bdpt_scene_export.argtypes = [vp, vp, vp, vp, vp]
         L.bdpt_scene_export_traversal.argtypes = [vp, vp, vp, vp, vp]
         L.bdpt_intersect_from.argtypes = [vp, ctypes.c_int64, vp, vp, vp, i32, vp]
+        L.bdpt_intersect_deferred.argtypes = [vp, ctypes.c_int64, vp, vp, vp, vp, vp]
+        L.bdpt_get_leaf_rewalks.argtypes = [vp, ctypes.c_int64 * 2]
         L.bdpt_scene_create.argtypes = [ctypes.POINTER(_SceneDesc), ctypes.POINTER(vp)]
         L.bdpt_scene_export_layout.argtypes = [vp, i32, vp, ctypes.POINTER(ctypes.c_int64)]
+        L.bdpt_scene_export_shade_records.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64)]
         L.bdpt_scene_create_textured.argtypes = [ctypes.POINTER(_SceneDesc), ctypes.POINTER(_SceneTextures),
                                                  ctypes.POINTER(vp)]
         L.bdpt_scene_export_textures.argtypes = [vp, i32, vp, ctypes.POINTER(ctypes.c_int64), vp]
@@ -653,6 +656,15 @@ class Scene:
         _check(lib().bdpt_scene_export_layout(self._h, i, buf, ctypes.byref(n)))
         return buf.raw[:n.value]
 
+    def export_shade_records(self) -> bytes:
+        """bdpt_scene_export_shade_records: the device shade records as uploaded (128 bytes per
+        triangle; export_layout("shade") plus the reference leaf box or leaf id)."""
+        n = ctypes.c_int64(0)
+        _check(lib().bdpt_scene_export_shade_records(self._h, None, ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(max(n.value, 1))
+        _check(lib().bdpt_scene_export_shade_records(self._h, buf, ctypes.byref(n)))
+        return buf.raw[:n.value]
+
     def export_textures(self, array) -> bytes:
         """bdpt_scene_export_textures: one of the texture arrays (TEXTURE_ARRAYS) as bytes."""
         i = TEXTURE_ARRAYS.index(array) if isinstance(array, str) else int(array)
@@ -916,6 +928,23 @@ class BDPTIntegrator:
                                              None if ot is None else ot.ctypes.data, 1 if occlusion else 0,
                                              out.ctypes.data))
         return out
+
+    def intersect_deferred(self, rays, origin_normals=None, origin_tris=None):
+        """bdpt_intersect_deferred: the closest hits of intersect() found the way the frame
+        kernels without Russian roulette find them (the reference-leaf check deferred to the
+        walk's winner; a winner that fails is walked again with the check in the leaf step).
+        Returns (bdpt_hit array, int32 (n,) 1 where the query was walked again)."""
+        r = _af32(rays, 8)
+        out = np.zeros(r.shape[0], HIT_DTYPE)
+        again = np.zeros(r.shape[0], np.int32)
+        nr = None if origin_normals is None else _af32(origin_normals, 3)
+        ot = None if origin_tris is None or nr is None else np.ascontiguousarray(origin_tris, np.int32).reshape(-1)
+        if ot is not None and ot.shape[0] != r.shape[0]:
+            raise ValueError("origin_tris needs one entry per ray")
+        _check(lib().bdpt_intersect_deferred(self._h, r.shape[0], r.ctypes.data, None if nr is None else nr.ctypes.data,
+                                             None if ot is None else ot.ctypes.data, out.ctypes.data,
+                                             again.ctypes.data))
+        return out, again
 
     def splat_to_image_plane(self, points) -> np.ndarray:
         """BDPTIntegrator::splatToImagePlane (bdpt.h:485-496) of points (n, 3): int32 (n, 2)."""
@@ -1197,7 +1226,9 @@ class BDPTIntegrator:
     def stats(self) -> dict:
         s = _Stats()
         _check(lib().bdpt_get_stats(self._h, ctypes.byref(s)))
-        return dict(kernel_ms=s.kernel_ms, samples=s.samples, launches=s.launches,
+        leaf = (ctypes.c_int64 * 2)()  # (bdpt_get_leaf_rewalks: an entry of its own, bdpt_stats keeps its layout)
+        _check(lib().bdpt_get_leaf_rewalks(self._h, leaf))
+        return dict(leaf_rewalks=leaf[0], leaf_hits=leaf[1], kernel_ms=s.kernel_ms, samples=s.samples, launches=s.launches,
                     counters=dict(zip(COUNTER_NAMES, list(s.counters))), capped_samples=s.capped_samples,
                     span_ms=s.span_ms, tail_ms=s.tail_ms, max_light_depth=s.max_light_depth,
                     max_eye_depth=s.max_eye_depth, max_queries=s.max_queries, schedule_errors=s.schedule_errors, parked_samples=s.parked_samples,

@@ -43,6 +43,10 @@ hipError_t launch_triangle_kat(int64_t n, const float* rays, const float* verts,
 hipError_t launch_intersect_kat(const dev::DevScene& sc, int64_t n, int occlusion, const float* rays, const float* nrm,
                                 const int32_t* otri, uint2* gstack, uint32_t nslots, float* out, hipStream_t st);
 hipError_t launch_splat_kat(const dev::DevFrame& fr, int64_t n, const float* p, int32_t* xy, hipStream_t st);
+// kat_leaf_defer.hip: the closest hit with the reference-leaf check deferred to the walk's winner
+hipError_t launch_intersect_defer(const dev::DevScene& sc, int64_t n, int by_id, int force, const float* rays,
+                                  const float* nrm, const int32_t* otri, uint2* gstack, uint32_t nslots, float* out,
+                                  int32_t* rewalked, hipStream_t st);
 // kat_sampling.hip: the sampling side per function, and with the fast weights (kat_sampling_fw.hip)
 hipError_t launch_sampling_kat(const dev::DevScene& sc, const dev::DevFrame& fr, int fn, int nin, int nout, int64_t n,
                                const uint32_t* in, uint32_t* out, hipStream_t st);
@@ -100,7 +104,12 @@ const char* debug_knob(const char* name) {
     return nullptr;
 }
 
-#define HIP_TRY(expr)                                                                               \
+static bool leaf_recheck_knob() {
+    const char* e = debug_knob("BDPT_LEAF_RECHECK");
+    return e && *e == '1';
+}
+
+#define HIP_TRY(expr)                                                                         \
     do {                                                                                            \
         hipError_t e_ = (expr);                                                                     \
         if (e_ != hipSuccess) return fail(BDPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
@@ -443,8 +452,9 @@ static uint32_t graze_code(const float* v0, const float* v1, const float* v2, co
 
 // The shading records as uploaded (bdpt_types.h kShadeStride): the host five
 // (n0, mat) (n1, shape) (n2, prim) (v1) (v2), + (v0) in the wide layout, with the
-// triangle's graze code in bits 24..31 of the shape word (shape ids < 2^24).
-static std::vector<float4_t> device_shade(const DeviceLayout& L) {
+// triangle's graze code in bits 24..31 of the shape word (shape ids < 2^24) and, with
+// leaf_box, the triangle's reference leaf box or leaf id in the last two slots (below).
+static std::vector<float4_t> device_shade(const DeviceLayout& L, bool leaf_box = true) {
     const char* gz = debug_knob("BDPT_GRAZE_CODES");  // "0": every code 0 (the plain |cos| < 0.02 test; A/B only)
     const bool codes = !(gz && *gz == '0');
     const size_t ntri = L.shade.size() / 5;
@@ -466,6 +476,22 @@ static std::vector<float4_t> device_shade(const DeviceLayout& L) {
         std::memcpy(&shape, &s[1].w, 4);
         if (codes) shape |= graze_code(v0, v1, v2, n) << 24;
         std::memcpy(&out[kShadeStride * i + 1].w, &shape, 4);
+    }
+    // The triangle's reference leaf box (kShadeBox), for the deferred leaf check of a closest hit:
+    // a traversal triangle names its shade record (v0's w) and its reference leaf (e1's w). The
+    // box's two vectors go into the record's free slots; where the texture coordinates hold those,
+    // the leaf id goes into their free last word and the kernel reads lbox.
+    for (size_t k = 0; leaf_box && kShadeStride >= kShadeBox + 2 && 3 * k + 1 < L.wtri.size(); k++) {
+        uint32_t i, leaf;
+        std::memcpy(&i, &L.wtri[3 * k].w, 4);
+        std::memcpy(&leaf, &L.wtri[3 * k + 1].w, 4);
+        if (i >= ntri || 2 * static_cast<size_t>(leaf) + 1 >= L.lbox.size()) continue;
+        if (L.textured()) {
+            std::memcpy(&out[kShadeStride * i + kShadeBox + 1].w, &leaf, 4);
+        } else {
+            out[kShadeStride * i + kShadeBox] = L.lbox[2 * static_cast<size_t>(leaf)];
+            out[kShadeStride * i + kShadeBox + 1] = L.lbox[2 * static_cast<size_t>(leaf) + 1];
+        }
     }
     return out;
 }
@@ -550,7 +576,9 @@ int bdpt_scene_export_layout(const bdpt_scene* s, int32_t array, void* dst, int6
     std::vector<BsdfRecord> tmpb;
     switch (array) {
         case 0: src = L.tri.data(), n = L.tri.size() * 16; break;
-        case 1: tmp4 = device_shade(L), src = tmp4.data(), n = tmp4.size() * 16; break;
+        // (without the leaf-box words, the array as it has been exported so far; with them:
+        // bdpt_scene_export_shade_records)
+        case 1: tmp4 = device_shade(L, false), src = tmp4.data(), n = tmp4.size() * 16; break;
         case 2: src = L.nodes.data(), n = L.nodes.size() * 16; break;
         case 3: src = L.wnodes.data(), n = L.wnodes.size() * 16; break;
         case 4: src = L.wtri.data(), n = L.wtri.size() * 16; break;
@@ -567,6 +595,20 @@ int bdpt_scene_export_layout(const bdpt_scene* s, int32_t array, void* dst, int6
     if (dst) {
         if (*bytes < static_cast<int64_t>(n)) return fail(BDPT_ERR_INVALID, "destination too small");
         if (n) std::memcpy(dst, src, n);
+    }
+    *bytes = static_cast<int64_t>(n);
+    return BDPT_OK;
+}
+
+// The device shade records as bdpt_ctx_create uploads them (kShadeStride float4 per triangle),
+// the reference leaf box or leaf id of the deferred leaf check included (kShadeBox).
+int bdpt_scene_export_shade_records(const bdpt_scene* s, void* dst, int64_t* bytes) {
+    if (!s || !bytes) return fail(BDPT_ERR_INVALID, "null argument");
+    const std::vector<float4_t> rec = device_shade(s->layout);
+    const size_t n = rec.size() * 16;
+    if (dst) {
+        if (*bytes < static_cast<int64_t>(n)) return fail(BDPT_ERR_INVALID, "destination too small");
+        if (n) std::memcpy(dst, rec.data(), n);
     }
     *bytes = static_cast<int64_t>(n);
     return BDPT_OK;
@@ -935,6 +977,10 @@ static dev::DevFrame make_frame(const bdpt_frame_params* p, const bdpt_sample_wi
     fr.express_depth = kExpressDepth;
     if (const char* e = std::getenv("BDPT_EXPRESS_DEPTH")) fr.express_depth = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("BDPT_COOP_GROUPS")) fr.sched_flags |= *e == '0' ? dev::kSchedNoCoopGroups : 0u;
+    // BDPT_LEAF_RECHECK=1 (a debugging knob): the deferred reference-leaf check of the frame kernels
+    // fails for every closest hit, so each is walked again with the check in the leaf step — the
+    // same frame through the path a real failure takes (tests/test_gpu_leaf_defer.py)
+    if (leaf_recheck_knob()) fr.sched_flags |= dev::kSchedLeafRecheck;
     return fr;
 }
 
@@ -1615,6 +1661,22 @@ int bdpt_get_stats(bdpt_ctx* c, bdpt_stats* out) {
     return BDPT_OK;
 }
 
+// out[0]: checked re-walks, out[1]: closest hits applied, of the last BDPT frame render, a counting
+// pass of a build with the deferred reference-leaf check (dev::kDiagLeafRewalks, kDiagLeafHits); 0
+// for every other render.
+int bdpt_get_leaf_rewalks(bdpt_ctx* c, int64_t out[2]) {
+    if (!c || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    out[0] = out[1] = 0;
+    if (!c->diag_pending) return BDPT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    static_assert(dev::kDiagLeafHits == dev::kDiagLeafRewalks + 1, "two consecutive words");
+    unsigned long long w[2] = {0, 0};
+    HIP_TRY(hipMemcpy(w, c->diag + dev::kDiagLeafRewalks, sizeof(w), hipMemcpyDeviceToHost));
+    out[0] = static_cast<int64_t>(w[0]), out[1] = static_cast<int64_t>(w[1]);
+    return BDPT_OK;
+}
+
 int bdpt_synchronize(bdpt_ctx* c) {
     if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
     HIP_TRY(hipSetDevice(c->device));
@@ -1895,6 +1957,44 @@ int bdpt_intersect_from(bdpt_ctx* c, int64_t n, const float* rays, const float* 
                                      dt ? dt + b : nullptr, c->gstack, c->nslots, dout + 20 * b, c->stream));
     }
     HIP_TRY(hipMemcpyAsync(out, dout, 80 * N, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = end_use(c, c->stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+// The closest hits of bdpt_intersect_from through the deferred reference-leaf check of the
+// frame kernels (kat_leaf_defer.hip); rewalked (optional): per ray, 1 when its winner failed the
+// check and the query was walked again. BDPT_LEAF_RECHECK=1 (a debugging knob) fails every check.
+int bdpt_intersect_deferred(bdpt_ctx* c, int64_t n, const float* rays, const float* origin_normals,
+                            const int32_t* origin_tris, bdpt_hit* out, int32_t* rewalked) {
+    if (!c || n < 0 || (n > 0 && (!rays || !out))) return fail(BDPT_ERR_INVALID, "bad argument");
+    if (n == 0) return BDPT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = begin_use(c, c->stream))) return rc;
+    DevBuf<float> dr, dout, dn;
+    DevBuf<int32_t> dt, dre;
+    const size_t N = static_cast<size_t>(n);
+    if (origin_tris)
+        for (size_t i = 0; i < N; i++)
+            if (origin_tris[i] < -1 || origin_tris[i] >= c->ntri) return fail(BDPT_ERR_INVALID, "origin_tris out of range");
+    if ((rc = kat_in(c, dr, rays, 32 * N)) || (rc = kat_in<float>(c, dout, nullptr, 80 * N)) ||
+        (rc = kat_in<int32_t>(c, dre, nullptr, 4 * N)))
+        return rc;
+    if (origin_normals && (rc = kat_in(c, dn, origin_normals, 12 * N))) return rc;
+    if (origin_normals && origin_tris && (rc = kat_in(c, dt, origin_tris, 4 * N))) return rc;
+    std::vector<const float*> origins(N);
+    for (size_t i = 0; i < N; i++) origins[i] = rays + 8 * i;
+    dev::DevScene sc = c->sc;
+    sc.node_slack = node_slack_needed(c, origins.data(), static_cast<int>(std::min<size_t>(N, 0x7fffffff)));
+    const int force = leaf_recheck_knob() ? 1 : 0;
+    for (int64_t b = 0; b < n; b += c->nslots) {  // (the traversal-stack overflow columns serve c->nslots rays)
+        const int64_t m = std::min<int64_t>(c->nslots, n - b);
+        HIP_TRY(launch_intersect_defer(sc, m, c->textured ? 1 : 0, force, dr + 8 * b, dn ? dn + 3 * b : nullptr,
+                                       dt ? dt + b : nullptr, c->gstack, c->nslots, dout + 20 * b, dre + b, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(out, dout, 80 * N, hipMemcpyDeviceToHost, c->stream));
+    if (rewalked) HIP_TRY(hipMemcpyAsync(rewalked, dre, 4 * N, hipMemcpyDeviceToHost, c->stream));
     if ((rc = end_use(c, c->stream))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BDPT_OK;

@@ -223,7 +223,9 @@ struct DevFrame {
     int32_t n_layers;
 };
 enum : uint32_t { kParkOn = 1u, kParkResume = 2u };
-enum : uint32_t { kSchedNoCoopGroups = 1u };
+// kSchedLeafRecheck (BDPT_LEAF_DEFER builds, a debugging knob): the deferred reference-leaf
+// check reports failure for every hit, so every closest hit is walked again in checked mode
+enum : uint32_t { kSchedNoCoopGroups = 1u, kSchedLeafRecheck = 2u };
 
 struct Ray {
     f3 o, d;
@@ -873,7 +875,10 @@ struct Counts {
 // held at once, and the express-mode loop iterations of waves holding 1, 2..BDPT_COOP_MAX,
 // more such walks
 enum : int { kDiagStart = 0, kDiagLastClaim = 1, kDiagEnd = 2, kDiagErrors = 3, kDiagParked = 4, kDiagLongMax = 5,
-             kDiagExpress1 = 6, kDiagExpressCoop = 7, kDiagExpressMore = 8, kDiagWords = 9 };
+             kDiagExpress1 = 6, kDiagExpressCoop = 7, kDiagExpressMore = 8,
+             // counting pass, BDPT_LEAF_DEFER builds: checked re-walks begun, closest hits applied
+             // (bdpt_path.hpp closest_apply)
+             kDiagLeafRewalks = 9, kDiagLeafHits = 10, kDiagWords = 11 };
 
 // Set bits of a wave mask as an int. (HIP's __popcll is typed unsigned long long
 // here: mixed with int in min / max it selected the double overloads, and the
@@ -1040,7 +1045,10 @@ __device__ __forceinline__ TravScene trav_scene(const DevScene& sc) {
 // cross pairs, the reference's divisions) and only for a hit that would become
 // the closest (minimum t, ties to the lowest reference index = the reference's
 // strict `<` in its left-first DFS) or that ends an occlusion query (t <= max_t,
-// see leaf_tests).
+// see leaf_tests). A closest-hit walk with `defer` set (BDPT_LEAF_DEFER, the frame
+// kernels without Russian roulette) accepts on the comparison alone: only the
+// walk's final winner is checked, once, where its result is applied
+// (leaf_box_passes, bdpt_path.hpp closest_apply).
 template <bool COUNT>
 __device__ __forceinline__ bool ref_leaf_passes(const float4* __restrict__ lbox, uint32_t leaf, const Ray& r,
                                                 const RayInv& ri, Counts& cnt) {
@@ -1070,7 +1078,8 @@ __device__ __forceinline__ bool ref_leaf_passes(const float4* __restrict__ lbox,
 template <bool COUNT>
 __device__ __forceinline__ bool wleaf_tests(const float4* __restrict__ wtri, const float4* __restrict__ lbox,
                                             uint32_t link, const Ray& r, const RayInv& ri, bool any, float& best_t,
-                                            int& best, float& best_u, float& best_v, Counts& cnt) {
+                                            int& best, float& best_u, float& best_v, Counts& cnt,
+                                            bool defer = false) {
     constexpr uint32_t G = BDPT_WLEAF_GROUP;
     static_assert(G == 1 || G == 2, "BDPT_WLEAF_GROUP: 1 or 2 (four triangles do not fit under the node step's registers)");
     const uint32_t start = (link >> 3) & 0x0fffffffu, count = link & 7u;
@@ -1088,7 +1097,7 @@ __device__ __forceinline__ bool wleaf_tests(const float4* __restrict__ wtri, con
                     return true;
                 }
             } else if ((t < best_t || (t == best_t && best >= 0 && idx < best)) &&
-                       ref_leaf_passes<COUNT>(lbox, __float_as_uint(q1.w), r, ri, cnt)) {
+                       (defer || ref_leaf_passes<COUNT>(lbox, __float_as_uint(q1.w), r, ri, cnt))) {
                 best_t = t, best = idx, best_u = u, best_v = v;
             }
         }
@@ -1121,7 +1130,7 @@ __device__ __forceinline__ bool wleaf_tests(const float4* __restrict__ wtri, con
                     return true;
                 }
             } else if ((t < best_t || (t == best_t && best >= 0 && idx < best)) &&
-                       ref_leaf_passes<COUNT>(lbox, __float_as_uint(q1.w), r, ri, cnt)) {
+                       (defer || ref_leaf_passes<COUNT>(lbox, __float_as_uint(q1.w), r, ri, cnt))) {
                 best_t = t, best = idx, best_u = u, best_v = v;
             }
         }
@@ -1338,13 +1347,14 @@ __device__ __forceinline__ bool walk_begin_lds(const RootLds& m, const Ray& r, c
 // when the query is complete (result in ts.best / best_t / best_u / best_v).
 template <bool COUNT, bool SLACK = true>
 __device__ __forceinline__ bool trav_step(const TravScene& sc, const Ray& r, const RayInv& ri, bool any, TravState& ts,
-                                          const Stack& stk, Counts& cnt) {
+                                          const Stack& stk, Counts& cnt, bool defer = false) {
     if (COUNT) {
         cnt.c[8]++;
         if (first_active_lane()) cnt.c[9]++;
     }
     if (ts.link & kLeafBit) {
-        if (wleaf_tests<COUNT>(sc.wtri, sc.lbox, ts.link, r, ri, any, ts.best_t, ts.best, ts.best_u, ts.best_v, cnt))
+        if (wleaf_tests<COUNT>(sc.wtri, sc.lbox, ts.link, r, ri, any, ts.best_t, ts.best, ts.best_u, ts.best_v, cnt,
+                               defer))
             return true;
     } else if (trav_node<COUNT, SLACK>(sc, r, ri, any, ts, stk, cnt)) {
         return false;
@@ -1357,7 +1367,7 @@ __device__ __forceinline__ bool trav_step(const TravScene& sc, const Ray& r, con
 // the leaves are tested together — a wave iteration runs one kind of work.
 template <bool COUNT>
 __device__ __forceinline__ void trav_while_while(const TravScene& sc, const Ray& r, const RayInv& ri, bool any,
-                                                 TravState& ts, const Stack& stk, Counts& cnt) {
+                                                 TravState& ts, const Stack& stk, Counts& cnt, bool defer = false) {
     for (;;) {
         bool live = true;
         while (!(ts.link & kLeafBit)) {
@@ -1375,7 +1385,8 @@ __device__ __forceinline__ void trav_while_while(const TravScene& sc, const Ray&
             cnt.c[8]++;
             if (first_active_lane()) cnt.c[9]++;
         }
-        if (wleaf_tests<COUNT>(sc.wtri, sc.lbox, ts.link, r, ri, any, ts.best_t, ts.best, ts.best_u, ts.best_v, cnt))
+        if (wleaf_tests<COUNT>(sc.wtri, sc.lbox, ts.link, r, ri, any, ts.best_t, ts.best, ts.best_u, ts.best_v, cnt,
+                               defer))
             return;
         if (!trav_pop(r, any, ts, stk)) return;
     }
@@ -1588,8 +1599,13 @@ __device__ __forceinline__ int texel_of(float sx, float sy, int tw, int th) {
 }
 #endif
 // AcceleratorBVH::intersect's shading of a closest hit (accel.h:133-166).
-__device__ __forceinline__ void shade_hit(const DevScene& sc, int i, float u, float v, float t, f3 dir, Hit& h) {
+// box (optional): the record's last two vectors, loaded with the others — the
+// triangle's reference leaf box, or in the textured layout the word that names it
+// (leaf_box_passes).
+__device__ __forceinline__ void shade_hit(const DevScene& sc, int i, float u, float v, float t, f3 dir, Hit& h,
+                                          float4* box = nullptr) {
     const float4* sh = sc.shade + kShadeStride * static_cast<size_t>(i);
+    if (box) box[0] = gld4(sh + kShadeBox), box[1] = gld4(sh + kShadeBox + 1);
     const f3 v0 = xyz(gld4(sh + kShadeV0)),
              v1 = xyz(gld4(sh + 3)), v2 = xyz(gld4(sh + 4));
     const float4 s0 = gld4(sh), s1 = gld4(sh + 1), s2 = gld4(sh + 2);
@@ -1619,6 +1635,28 @@ __device__ __forceinline__ void shade_hit(const DevScene& sc, int i, float u, fl
         if (ks0 >= 0) h.tks = ks0 + texel_of(sx, sy, __float_as_int(ms_.y), __float_as_int(ms_.z));
     }
 #endif
+}
+
+// The deferred reference-leaf check of a closest-hit walk's winner (wleaf_tests,
+// `defer`): box_test on the reference leaf box of triangle `tri` with the query's
+// ray, the test the walk would have made in its leaf step. box = the two vectors
+// at kShadeBox of the triangle's shade record (shade_hit loads them with the rest
+// of the line; shade_box loads just them): the six floats of lbox[leaf], or with
+// by_id (the textured layout: those slots hold texture coordinates) the leaf id in
+// the last word, and the box is read from lbox.
+__device__ __forceinline__ void shade_box(const DevScene& sc, int tri, float4* box) {
+    const float4* sh = sc.shade + kShadeStride * static_cast<size_t>(tri);
+    box[0] = gld4(sh + kShadeBox), box[1] = gld4(sh + kShadeBox + 1);
+}
+template <bool COUNT>
+__device__ __forceinline__ bool leaf_box_passes(const DevScene& sc, const float4* box, bool by_id, const Ray& r,
+                                                const RayInv& ri, Counts& cnt) {
+    if (by_id) return ref_leaf_passes<COUNT>(sc.lbox, __float_as_uint(box[1].w), r, ri, cnt);
+    float tn, tf;
+    uint32_t fb = 0;
+    const bool pass = box_test<COUNT>(box[0].x, box[0].y, box[0].z, box[1].x, box[1].y, box[1].z, r, ri, tn, tf, fb);
+    if (COUNT) cnt.c[15] += fb;
+    return pass;
 }
 
 // The shadow ray of visibilityQuery (bdpt.h:498-505).

@@ -64,6 +64,18 @@
 #define BDPT_HELP 0
 #endif
 
+// The reference-leaf check of a closest-hit walk made once, on the walk's winner, where
+// its result is applied, instead of in the leaf step on every hit that improves best_t
+// (bdpt_path.hpp closest_apply): the builds with the task walk loop.
+// 0: the check in the leaf step (the device code before; lib/libbdpt_amd_defer0.so).
+#ifndef BDPT_LEAF_DEFER
+#define BDPT_LEAF_DEFER BDPT_HELP
+#endif
+#if !BDPT_HELP
+#undef BDPT_LEAF_DEFER
+#define BDPT_LEAF_DEFER 0
+#endif
+
 // The eye-estimate slots (bdpt_path.hpp) are claimed with the 64-sample chunks.
 #if defined(BDPT_SEED_CHUNK) && !BDPT_SEED_CHUNK && !defined(BDPT_EYE_SLOTS)
 #define BDPT_EYE_SLOTS 0
@@ -277,6 +289,29 @@ __device__ __forceinline__ uint64_t tail_chunk(uint64_t last_base, uint64_t tota
     return last_base + BDPT_TAIL_Z16 * lanes / 4 < total ? 64 : last_base + BDPT_TAIL_Z4 * lanes / 4 < total ? 16 : 4;
 }
 
+// The kind of a lane's walk, kept until its result is applied: a bool (true: an occlusion
+// query) or, with BDPT_LEAF_DEFER, one word that reads and assigns as that bool and also
+// tells a closest hit's two forms apart: the reference-leaf check deferred to the walk's
+// winner, or (that winner failed, closest_apply) the same query walked again with the check
+// in the leaf step.
+#if BDPT_LEAF_DEFER
+struct WalkKind {
+    uint32_t k = 0;  // 0: closest, deferred; 1: occlusion; 2: closest, checked
+    __device__ __forceinline__ operator bool() const { return k == 1u; }
+    __device__ __forceinline__ WalkKind& operator=(bool any) {
+        k = any ? 1u : 0u;
+        return *this;
+    }
+    __device__ __forceinline__ bool deferred() const { return k == 0u; }
+    __device__ __forceinline__ bool checked() const { return k == 2u; }
+    __device__ __forceinline__ void recheck() { k = 2u; }
+};
+__device__ __forceinline__ bool walk_deferred(const WalkKind& q) { return q.deferred(); }
+#else
+typedef bool WalkKind;
+__device__ __forceinline__ constexpr bool walk_deferred(bool) { return false; }
+#endif
+
 template <bool FULL, bool COUNT, bool SLACK>
 __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_frame_kernel)(const KParams* __restrict__ kpp) {
     const KParams& kp = *kpp;
@@ -323,7 +358,8 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
 #endif
 #endif
     const TravScene tsc = trav_scene(kp.sc);
-    bool tracing = false, has_res = false, q_any = false;
+    bool tracing = false, has_res = false;
+    WalkKind q_any{};
     TravState ts{};
     RayInv ri{};
     int res = -1;
@@ -508,6 +544,9 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
                 if (COUNT) cnt.c[2] += q.nodes, cnt.c[3] += q.tris, cnt.c[15] += q.exact;
                 res = q.best, rt = q.t, ru = q.u, rv = q.v;
                 has_res = true;
+#if BDPT_LEAF_DEFER
+                if (q_any.deferred()) q_any.recheck();  // the reference's own walk: checked, nothing deferred
+#endif
             } else {
                 ts = trav_begin(tsc, L.ray);
                 tracing = true;
@@ -727,6 +766,23 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
         // read once per shading step: in the walk loop its scalar load waited (lgkmcnt)
         // on the lane's LDS stack traffic every iteration
         const int steady_ready = P->fr.shade_ready > 0 ? P->fr.shade_ready : BDPT_SHADE_READY;
+#if BDPT_LEAF_DEFER
+        const bool recheck_all = (P->fr.sched_flags & kSchedLeafRecheck) != 0;  // (debugging knob; wave-uniform)
+        // a closest hit whose winner failed its check (closest_apply): the same query again from
+        // the root with the check in the leaf step; the lane's ray, ri and stack column are its own
+        auto recheck_begin = [&]() {
+            q_any.recheck();
+            if (COUNT && P->fr.diag) gadd(P->fr.diag + kDiagLeafRewalks, 1ull);
+            ts = trav_begin(tsc, L.ray);
+            tracing = true;
+            has_res = false;
+            if (root_in_lds && !walk_begin_lds<COUNT, SLACK>(root_lds, L.ray, ri, false, ts, stk, cnt)) {
+                res = -1, rt = ts.best_t, ru = ts.best_u, rv = ts.best_v;  // no child hit: a miss
+                tracing = false;
+                has_res = true;
+            }
+        };
+#endif
 #if BDPT_HELP
         // the ring's positions in scalar registers while the wave walks (pushes happen
         // only in the shading step; claims below write the head back)
@@ -776,12 +832,31 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
                 if (popc64(cm) < BDPT_HELP_MIN && popc64(cm) < static_cast<int>(tail - head) && __ballot(tracing)) cm = 0;
                 if (cm) {
                     if (COUNT && lane0()) cnt.q[2]++;  // (counting pass: claim rounds)
+#if BDPT_LEAF_DEFER
+                    // a taker's own result is applied first (frees L.ray); one whose winner fails its
+                    // check walks its own query again instead, and the others take the tasks in order
+                    uint32_t n = min(static_cast<uint32_t>(popc64(cm)), tail - head);
+                    uint32_t rank = static_cast<uint32_t>(lanes_below(cm));
+                    bool take = cand && rank < n;
+                    if (take && has_res && res >= 0 && is_closest_state(L.state) &&
+                        !closest_apply<COUNT>(L, res, rt, ru, rv, P->sc, ri, q_any.checked(), recheck_all, P->fr, cnt)) {
+                        take = false;
+                        recheck_begin();
+                    }
+                    const uint64_t tm = __ballot(take);
+                    n = static_cast<uint32_t>(popc64(tm));
+                    rank = static_cast<uint32_t>(lanes_below(tm));
+                    *ctl.head = head + n;
+                    qhead = head + n;
+                    if (take) {
+#else
                     const uint32_t n = min(static_cast<uint32_t>(popc64(cm)), tail - head);
                     const uint32_t rank = static_cast<uint32_t>(lanes_below(cm));
                     *ctl.head = head + n;
                     qhead = head + n;
                     if (cand && rank < n) {
                         if (has_res) help_compact(L, res, rt, ru, rv, P->sc);  // frees L.ray
+#endif
                         const uint32_t slot = (head + rank) & (P->fr.task_cap - 1);
                         float4* const ring = task_ring(P->fr);
                         const uint32_t cap = P->fr.task_cap;
@@ -824,15 +899,15 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
             const bool at_leaf = (ts.link & kLeafBit) != 0;
             const uint64_t lv = __ballot(tracing && at_leaf);
             const bool do_leaf = popc64(lv) * 4 >= popc64(tr & ~lv) * BDPT_TRAV_SPLIT;
-            bool fin = tracing && at_leaf == do_leaf && trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt);
+            bool fin = tracing && at_leaf == do_leaf && trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt, walk_deferred(q_any));
             // BDPT_WALK_UNROLL more interior-node steps before the wave's ballots, also after
             // a leaf iteration, for lanes that popped to an interior node
 #pragma unroll
             for (int k = 0; k < BDPT_WALK_UNROLL; k++)
-                if (tracing && !fin && !(ts.link & kLeafBit)) fin = trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt);
+                if (tracing && !fin && !(ts.link & kLeafBit)) fin = trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt, walk_deferred(q_any));
             if (fin) {
 #else
-            if (tracing && trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt)) {
+            if (tracing && trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt, walk_deferred(q_any))) {
 #endif
 #if BDPT_HELP
                 tracing = false;
@@ -865,7 +940,17 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
 #endif
         }
         const uint64_t c1 = COUNT ? __builtin_amdgcn_s_memtime() : 0;
+#if BDPT_LEAF_DEFER
+        bool shade_now = has_res && !helping;  // (a helper mid-walk shades next time)
+        // the walk's winner checked and applied (closest_apply), or walked again
+        if (shade_now && res >= 0 && is_closest_state(L.state) &&
+            !closest_apply<COUNT>(L, res, rt, ru, rv, P->sc, ri, q_any.checked(), recheck_all, P->fr, cnt)) {
+            shade_now = false;
+            recheck_begin();
+        }
+#else
         const bool shade_now = has_res && !(BDPT_HELP && helping);  // (a helper mid-walk shades next time)
+#endif
 #if BDPT_HELP_BATCH
         uint32_t act2 = A_DONE;
 #endif

@@ -9,5 +9,10 @@
 // 1..28 without Russian roulette, untextured scenes with the BSDF table in LDS and all
 // three strategies; every host-visible symbol gets a _groups name.
 #define BDPT_GROUPS 1
+// The reference-leaf check stays in the leaf step (bdpt_kernels.hip BDPT_LEAF_DEFER): deferred,
+// this build's register allocation spills more (2 -> 4 spilled VGPRs).
+#ifndef BDPT_LEAF_DEFER
+#define BDPT_LEAF_DEFER 0
+#endif
 #define BDPT_VARIANT _groups
 #include "bdpt_kernels.hip"

@@ -401,6 +401,12 @@ __device__ __forceinline__ void eye_slot_reset(float* __restrict__ fb, int k, in
 #ifndef BDPT_HELP
 #define BDPT_HELP 0
 #endif
+#ifndef BDPT_LEAF_DEFER
+#define BDPT_LEAF_DEFER 0  // closest_apply below; bdpt_kernels.hip sets it for the builds that take it
+#endif
+#if BDPT_LEAF_DEFER && !(BDPT_HELP && !BDPT_SAMPLER_STATE)
+#error "BDPT_LEAF_DEFER is built on the task builds' walk loop (BDPT_HELP)"
+#endif
 #if BDPT_HELP && !BDPT_SAMPLER_STATE
 constexpr uint32_t kTaskSplat = 0x40000000u;   // meta bit: a camera splat (framebuffer add, bdpt.h:363-370)
 constexpr uint32_t kTaskNoCull = 0x80000000u;  // meta bit: no near cull (kNoCullNear; clear: kCullNear)
@@ -1138,6 +1144,45 @@ __device__ __forceinline__ void help_compact(Lane& L, int& res, float t, float u
     }
     res = kResShaded;
 }
+
+#if BDPT_LEAF_DEFER
+// BDPT_LEAF_DEFER (the overlapped frame kernels without Russian roulette): a closest-hit
+// walk accepts triangle hits without the reference-leaf check (wleaf_tests, `defer`) and
+// its winner res >= 0 is checked here, once, where the result is applied — by resolve()'s
+// caller or in place of help_compact — while L.ray and ri are still the query's. The
+// winner's box comes with the shade record's line (leaf_box_passes), so the check costs no
+// round trip of its own. A winner that passes is the reference's result and
+// is applied as help_compact applies it: res becomes kResShaded or, outside accel.h:133's
+// range, -1. One that fails (or any, with force: kSchedLeafRecheck) says nothing about the
+// result: false, nothing applied, and the lane walks the same query again with the check
+// in the leaf step; that walk's result (checked) is applied without a second check.
+__device__ __forceinline__ bool is_closest_state(uint32_t st) { return st == ST_PRIMARY || st == ST_LIGHT || st == ST_EYE; }
+template <bool COUNT>
+__device__ __forceinline__ bool closest_apply(Lane& L, int& res, float t, float u, float v, const DevScene& sc,
+                                              const RayInv& ri, bool checked, bool force, const DevFrame& fr,
+                                              Counts& cnt) {
+    const uint32_t st = L.state;
+    const bool in_range = t <= L.ray.max_t && t >= L.ray.min_t;  // accel.h:133, after the check
+    float4 box[2];
+    Hit h;
+    if (in_range && st != ST_PRIMARY) shade_hit(sc, res, u, v, t, L.ray.d, h, box);
+    else shade_box(sc, res, box);  // (the primary hit is shaded later, by the eye walk's first vertex)
+    if (!checked && (force || !leaf_box_passes<COUNT>(sc, box, BDPT_TEXTURED != 0, L.ray, ri, cnt))) return false;
+    if (!in_range) {
+        res = -1;
+        return true;
+    }
+    if (st == ST_PRIMARY) {
+        L.c.prim_tri = res;
+        L.c.Li = mk(t, u, v);
+    } else {
+        L.h = h;
+    }
+    if (COUNT && fr.diag) gadd(fr.diag + kDiagLeafHits, 1ull);
+    res = kResShaded;
+    return true;
+}
+#endif
 
 // Schedules without an overlapped walk run a deferred action at once.
 template <bool COUNT>

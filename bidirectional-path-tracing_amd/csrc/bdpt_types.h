@@ -7,7 +7,8 @@
 //                                                            id_2 = primID (int bits)
 //                  c=3,4: (v1, 0), (v2, 0)                   for the hit point of a closest hit
 //     (host layout; the device copy has kShadeStride float4 per triangle: the
-//      same five, then (v0, 0) and padding — one 128-byte line per closest hit)
+//      same five, then (v0, 0) and the reference leaf box or texture coordinates
+//      (kShadeBox, kShadeSt) — one 128-byte line per closest hit)
 //   nodes[4*j + q] interior node j (2-wide, both child boxes inline):
 //       q0 = c0.min.xyz, c0.max.x   q1 = c0.max.yz, c1.min.xy
 //       q2 = c1.min.z, c1.max.xyz   q3 = (link0, link1, 0, 0) as uint bits
@@ -74,6 +75,12 @@ constexpr int kShadeV0 = 5;  // slot of (v0, 0) in a wide record
 // Scenes with bitmap textures: slots 6, 7 of a wide record hold the corners' texture
 // coordinates (s0 t0 s1 t1) (s2 t2 0 0), zero otherwise (as before).
 constexpr int kShadeSt = 6;
+// The triangle's reference leaf box (wide_bvh.hpp; DevScene::lbox), for the deferred
+// leaf check of a closest hit (bdpt_device.hpp leaf_box_passes): in the same two slots
+// (lo, 0) (hi, 0), the bits of lbox[2 * leaf], lbox[2 * leaf + 1], in a scene without
+// bitmap textures; with them the slots hold the texture coordinates and the last word
+// (slot 7's w) the leaf id.
+constexpr int kShadeBox = 6;
 
 constexpr uint32_t kLeafBit = 0x80000000u;
 // Words per lane slot of the BDPT megakernel's MT19937 ring (DevScene::mt_ring):

@@ -290,6 +290,11 @@ int bdpt_scene_export_textures(const bdpt_scene* scene, int32_t array, void* dst
  * array's size; dst may be NULL (size only), else it must hold *bytes on entry. */
 #define BDPT_LAYOUT_ARRAYS 13
 int bdpt_scene_export_layout(const bdpt_scene* scene, int32_t array, void* dst, int64_t* bytes);
+/* (new) The device shade records as a context uploads them: 8 float4 (128 bytes) per triangle in
+ * leaf order — array 1 of bdpt_scene_export_layout plus, in the two last vectors, the triangle's
+ * reference leaf box (lo, 0) (hi, 0), or in a scene with bitmap textures (texture coordinates in
+ * those vectors) the reference leaf's index in the last word. Same size protocol. */
+int bdpt_scene_export_shade_records(const bdpt_scene* scene, void* dst, int64_t* bytes);
 /* Camera constants: worldToCamera, cameraToWorld, cameraToClip, NDCToScreen
  * (column-major) then invWidth, invHeight, tan(fov/2), aspect, forward.xyz,
  * virtual near-plane distance — 72 floats. */
@@ -687,6 +692,19 @@ int bdpt_intersect(bdpt_ctx* ctx, int64_t n, const float* rays, int32_t occlusio
  * 0.02 + the triangle's normal-cone margin. */
 int bdpt_intersect_from(bdpt_ctx* ctx, int64_t n, const float* rays, const float* origin_normals,
                         const int32_t* origin_tris, int32_t occlusion, bdpt_hit* out);
+/* (new) The closest hits of bdpt_intersect_from the way the frame kernels without Russian
+ * roulette find them: the walk accepts triangle hits without the reference-leaf
+ * check, its winner is checked once against the box in the winner's shade record, and a winner
+ * that fails is discarded and the query walked again with the check in the leaf step. The same
+ * results as bdpt_intersect_from, bit for bit. rewalked (n, may be NULL): 1 where the query was
+ * walked again. With BDPT_DEBUG_KNOBS=1, BDPT_LEAF_RECHECK=1 fails the first check of every hit
+ * (here and in the frame kernels), so every hit takes the second walk. */
+int bdpt_intersect_deferred(bdpt_ctx* ctx, int64_t n, const float* rays, const float* origin_normals,
+                            const int32_t* origin_tris, bdpt_hit* out, int32_t* rewalked);
+/* (new) out[0]: the second walks begun, out[1]: the closest hits applied (after the check, inside
+ * accel.h:133's range) in the context's last BDPT frame render, counted by a counting pass
+ * (BDPT_FLAG_COUNT) of a frame-kernel build with the deferred check; 0 otherwise. */
+int bdpt_get_leaf_rewalks(bdpt_ctx* ctx, int64_t out[2]);
 /* BDPTIntegrator::splatToImagePlane (bdpt.h:485-496) of points p (n x 3) for the
  * camera and image of params: xy = n x 2 (the reference's int truncation). */
 int bdpt_splat_to_image_plane(bdpt_ctx* ctx, const bdpt_frame_params* params, int64_t n, const float* p,
