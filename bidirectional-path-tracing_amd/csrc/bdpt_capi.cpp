@@ -374,7 +374,7 @@ static int stage_host(bdpt_ctx* c, float* host, size_t n, Run run) {
 }
 
 // The LDS tables with the emitter faces (5 float4 each) and CDFs appended to `base` words:
-// their word offsets, and the total (16-byte rounded parts; bdpt_device.hpp scene_tables_to_lds).
+// their word offsets, and the total (16-byte rounded parts; dev_scene.hpp scene_tables_to_lds).
 constexpr uint32_t kLdsBudget = 24u * 1024u;  // bytes of dynamic LDS the scene tables may take
 static uint32_t emitter_lds_layout(const dev::DevScene& sc, uint32_t base, uint32_t& etri, uint32_t& ecdf) {
     auto up4 = [](uint32_t w) { return (w + 3u) & ~3u; };
@@ -831,7 +831,7 @@ int bdpt_ctx_create(const bdpt_scene* s, int32_t hip_device, bdpt_ctx** out) {
     c->sc.inv_nemit = 1.f / static_cast<float>(c->sc.nemit);  // the device's 1.f / nemit, bit for bit
     c->sc.nbsdf = static_cast<int32_t>(L.bsdfs.size());
     c->sc.nshapes = static_cast<int32_t>(L.shape_emitter.size());
-    {  // LDS table layout (bdpt_device.hpp scene_tables_to_lds), 16-byte aligned parts
+    {  // LDS table layout (dev_scene.hpp scene_tables_to_lds), 16-byte aligned parts
         auto up4 = [](uint32_t w) { return (w + 3u) & ~3u; };
         constexpr uint32_t kBudget = kLdsBudget;
         const uint32_t nb = static_cast<uint32_t>(L.bsdfs.size() * sizeof(BsdfRecord) / 4);

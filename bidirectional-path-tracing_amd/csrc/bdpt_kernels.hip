@@ -76,10 +76,6 @@
 #define BDPT_LEAF_DEFER 0
 #endif
 
-// The eye-estimate slots (bdpt_path.hpp) are claimed with the 64-sample chunks.
-#if defined(BDPT_SEED_CHUNK) && !BDPT_SEED_CHUNK && !defined(BDPT_EYE_SLOTS)
-#define BDPT_EYE_SLOTS 0
-#endif
 #include "bdpt_path.hpp"
 
 namespace bdpt {
@@ -90,10 +86,7 @@ namespace dev {
 #endif
 constexpr int kBlock = 256;
 #ifndef BDPT_TRAV_SPLIT
-#define BDPT_TRAV_SPLIT 8  // > 0: leaf and interior-node steps in separate iterations (leaf step if 4 * leaf lanes >= SPLIT * node lanes; round 5: 6 over 8, then 8 over 6 / 10 / 12 once node steps also follow leaf iterations)
-#endif
-#ifndef BDPT_SEED_CHUNK
-#define BDPT_SEED_CHUNK 1  // refill from per-wave chunks of 64 samples seeded together (0: per-refill seeding)
+#define BDPT_TRAV_SPLIT 8  // leaf and interior-node steps run in separate iterations: a leaf step if 4 * leaf lanes >= SPLIT * node lanes (round 5: 6 over 8, then 8 over 6 / 10 / 12 once node steps also follow leaf iterations)
 #endif
 #ifndef BDPT_WALK_UNROLL
 #define BDPT_WALK_UNROLL 1  // extra interior-node steps per walk iteration (measured: 0: 201.7, 1: 203.6)
@@ -108,9 +101,7 @@ constexpr int kBlock = 256;
 #define BDPT_EXPRESS_DEPTH 512  // Russian-roulette build: a subpath this deep puts its wave in express mode (below; DevFrame::express_depth, set per render)
 #endif
 
-#ifndef BDPT_COOP_ALONE
 #define BDPT_COOP_ALONE (BDPT_RR == 1 && !BDPT_SAMPLER_STATE)  // a lone trapped walk walked by its whole wave (below)
-#endif
 #ifndef BDPT_COOP_MAX
 #define BDPT_COOP_MAX 4  // express waves with up to this many busy lanes walk their closest hits in turn with the whole wave
 #endif
@@ -207,7 +198,7 @@ __device__ __forceinline__ void step(Lane& L, const DevScene& sc, const DevFrame
     const uint64_t c0 = COUNT ? __builtin_amdgcn_s_memtime() : 0;
     const int res = query ? traverse<FULL, COUNT>(sc, L.ray, any, stk, t, u, v, cnt, cull_near_for(L)) : -1;
     const uint64_t c1 = COUNT ? __builtin_amdgcn_s_memtime() : 0;
-#if BDPT_DEEP_RNG && BDPT_RING_AHEAD
+#if BDPT_DEEP_RNG
     if (L.rng.n + BDPT_RING_AHEAD >= 227 && !mt_ring_ahead(L.rng) && fr.diag) gadd(fr.diag + kDiagErrors, 1ull);
 #endif
     const uint32_t act = resolve<COUNT>(L, res, t, u, v, sc, fr, fb, cnt);
@@ -238,22 +229,8 @@ struct KParams {
 // SLACK: interior boxes with slab_fast's ambiguity slack (DevScene::node_slack,
 // decided per render on the host); a template parameter so the node step of
 // the walk loop carries no branch on it.
-#ifndef BDPT_HELP_BATCH
-#define BDPT_HELP_BATCH 1  // BDPT_HELP: the shading step's connections flattened over the wave (conn_batch; serial: 283.0 vs 322.8)
-#endif
-#if !BDPT_HELP
-#undef BDPT_HELP_BATCH
-#define BDPT_HELP_BATCH 0
-#endif
 #ifndef BDPT_EXPRESS_CHAIN
 #define BDPT_EXPRESS_CHAIN 0  // RR build: a lone long walk's delta bounces back to back inside the express block
-#endif
-#ifndef BDPT_CHAIN_RING_WAVE
-#define BDPT_CHAIN_RING_WAVE 1  // the inline chain's generator ring refilled by the whole wave (mt_ring_ahead_wave)
-#endif
-#if !(BDPT_EXPRESS_CHAIN && BDPT_DEEP_RNG && BDPT_RING_AHEAD)
-#undef BDPT_CHAIN_RING_WAVE
-#define BDPT_CHAIN_RING_WAVE 0
 #endif
 #ifndef BDPT_EXPRESS_PROBE
 #define BDPT_EXPRESS_PROBE 0  // measurement only (RR build): express waves with one busy lane, clocks per iteration and in the coop walk
@@ -268,7 +245,7 @@ struct KParams {
 #ifndef BDPT_TAIL_PROBE
 #define BDPT_TAIL_PROBE 0  // measurement only (non-RR builds): the drain phase in the RR diag words (tools/tail_probe.py)
 #endif
-// "this is lane 0" from an opaque threadIdx.x (lanes_below: bdpt_device.hpp).
+// "this is lane 0" from an opaque threadIdx.x (lanes_below: dev_traverse.hpp).
 __device__ __forceinline__ bool lane0() { return (opaque_tid() & 63) == 0; }
 // Where the finer claims begin, in quarters of the grid's lanes from the frame's end:
 // 16-sample claims from BDPT_TAIL_Z16 / 4 x lanes, 4-sample ones from BDPT_TAIL_Z4 / 4 x
@@ -345,18 +322,15 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
         }
     }
 #endif
-#if BDPT_SEED_CHUNK
     uint64_t chunk_base = 0;  // wave-uniform: the wave's current chunk of samples
     int chunk_pos = 0, chunk_n = 0;
     bool global_done = false;
     uint32_t chunk_x397 = 0;  // lane i: mt_x397 of sample chunk_base + i
-#if BDPT_EYE_SLOTS
+    // the eye-estimate slots (bdpt_path.hpp) are claimed with the 64-sample chunks
     static_assert(kBlock == 64 * kEyeSlotWaves, "one eye-slot row per wave");
     uint32_t chunk_seq = 0;  // wave-uniform: chunks claimed so far (their eye slot: seq mod BDPT_EYE_SLOTS)
     if (lane0())
         for (int k = 0; k < BDPT_EYE_SLOTS; k++) wave_eye_slots()[k] = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-#endif
-#endif
     const TravScene tsc = trav_scene(kp.sc);
     bool tracing = false, has_res = false;
     WalkKind q_any{};
@@ -423,7 +397,6 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
             gadd(P->fr.diag + (k == 1 ? kDiagExpress1 : k <= BDPT_COOP_MAX ? kDiagExpressCoop : kDiagExpressMore), 1ull);
         }
 #endif
-#if BDPT_SEED_CHUNK
         // Refill idle lanes from the wave's chunk of 64 consecutive samples. A
         // chunk is claimed with one atomic and the seeding recurrence of all its
         // samples (mt_x397) runs once with every lane busy, instead of once per
@@ -461,38 +434,19 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
                     P->fr.diag[kDiagLastClaim] = __builtin_amdgcn_s_memrealtime();
                 int px;
                 chunk_x397 = mt_x397(sample_seed(base + (opaque_tid() & 63), P->fr, px));
-#if BDPT_EYE_SLOTS
                 // the chunk's pixel when all 64 samples share one (the rendered samples per
                 // pixel, the window's count, a multiple of 64; spp alone does not say so)
                 const int cpx = lane_val(px, 0);
                 if (lane0())
                     eye_slot_reset(P->fb, static_cast<int>(chunk_seq % BDPT_EYE_SLOTS), P->fr.win_count % 64 == 0 ? cpx : -1);
                 chunk_seq++;
-#endif
             }
             const int m = min(popc64(idle), chunk_n - chunk_pos);
             const int rank = lanes_below(idle);
             const uint32_t x397 = __shfl(chunk_x397, (chunk_pos + rank) & 63);
-            if (refill && rank < m) start_sample<true>(L, chunk_base + chunk_pos + rank, P->fr, x397);
+            if (refill && rank < m) start_sample(L, chunk_base + chunk_pos + rank, P->fr, x397);
             chunk_pos += m;
         }
-#else
-        if (!exhausted) {  // refill idle lanes: one atomic per wave
-            const uint64_t idle = __ballot(L.state == ST_IDLE);
-            if (idle) {
-                const int n = popc64(idle);
-                const int leader = __ffsll(static_cast<unsigned long long>(idle)) - 1;
-                unsigned long long base = 0;
-                if ((opaque_tid() & 63) == static_cast<uint32_t>(leader)) base = gadd(work, static_cast<unsigned long long>(n));
-                base = __shfl(base, leader);
-                if (L.state == ST_IDLE) {
-                    const uint64_t s = base + lanes_below(idle);
-                    if (s < total) start_sample(L, s, P->fr);
-                }
-                if (base + n >= total) exhausted = true;
-            }
-        }
-#endif
 #if BDPT_HELP
         // the wave ends only with its task ring drained and no helper walking
         if (__ballot(BDPT_BUSY(L.state) || helping) == 0 && *task_ctl(L.c).head == *task_ctl(L.c).tail) {
@@ -524,8 +478,6 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
 #endif
 #if BDPT_COOP_ALONE
         bool began = false;  // this lane began a culled closest-hit walk in this iteration
-#endif
-#if BDPT_COOP_ALONE
         if (BDPT_BUSY(L.state) && !tracing && !has_res && !coop_wait) {  // a new query: begin its walk
 #else
         if (BDPT_BUSY(L.state) && !tracing && !has_res) {  // a new query: begin its walk
@@ -648,7 +600,7 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
                 // took ~40 % of each bounce's clocks (round 6 probe, BDPT_EXPRESS_PROBE).
                 const bool chain = BDPT_EXPRESS_CHAIN && popc64(busy) == 1;
                 int bounced = -1;  // -1: the result goes to the sweep; 0: the chain ended here; 2: its next query begins at the loop top
-#if BDPT_CHAIN_RING_WAVE
+#if BDPT_EXPRESS_CHAIN && BDPT_DEEP_RNG
                 uint32_t chain_g = 0;  // lane b's ring outputs generated, as the wave last left it (0: unknown)
 #endif
                 for (;;) {
@@ -676,7 +628,7 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
                     if (xp_lone) xp_walk += __builtin_amdgcn_s_memtime() - xw0;
 #endif
                     if (!chain || !ok) break;
-#if BDPT_CHAIN_RING_WAVE
+#if BDPT_EXPRESS_CHAIN && BDPT_DEEP_RNG
                     if (chain) {  // lane b's generator ring, refilled by the wave when its next bounce could reach the end
                         const uint32_t bn = static_cast<uint32_t>(lane_val(static_cast<int>(L.rng.n), b));
                         if (bn + BDPT_RING_AHEAD >= chain_g)
@@ -696,8 +648,8 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
                             shade_hit(P->sc, r, u, v, t, L.ray.d, L.h);
                             const float dist2 = L.h.dist * L.h.dist;
                             const float absCosIn = fabsf(L.h.wo.z);
-#if BDPT_DEEP_RNG && BDPT_RING_AHEAD
-#if BDPT_CHAIN_RING_WAVE
+#if BDPT_DEEP_RNG
+#if BDPT_EXPRESS_CHAIN
                             const bool ring_ok = chain_g >= L.rng.n + BDPT_RING_AHEAD;  // the wave generated far enough
 #else
                             constexpr bool ring_ok = false;
@@ -892,7 +844,6 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
                                               : steady_ready))
                 break;
 #endif
-#if BDPT_TRAV_SPLIT
             // Lanes at a leaf and lanes at an interior node step in alternate
             // iterations (whichever group is larger in the sense of the ratio
             // below) instead of both code paths running in every iteration.
@@ -906,9 +857,6 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
             for (int k = 0; k < BDPT_WALK_UNROLL; k++)
                 if (tracing && !fin && !(ts.link & kLeafBit)) fin = trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt, walk_deferred(q_any));
             if (fin) {
-#else
-            if (tracing && trav_step<COUNT, SLACK>(tsc, L.ray, ri, q_any, ts, stk, cnt, walk_deferred(q_any))) {
-#endif
 #if BDPT_HELP
                 tracing = false;
                 if (helping) {
@@ -951,13 +899,13 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
 #else
         const bool shade_now = has_res && !(BDPT_HELP && helping);  // (a helper mid-walk shades next time)
 #endif
-#if BDPT_HELP_BATCH
+#if BDPT_HELP
         uint32_t act2 = A_DONE;
 #endif
         const bool shading = COUNT && __ballot(shade_now) != 0;
         if (shade_now) {
             has_res = false;
-#if BDPT_DEEP_RNG && BDPT_RING_AHEAD
+#if BDPT_DEEP_RNG
             // the draws of this step past 227 are read from the ring: generate them first
             if (L.rng.n + BDPT_RING_AHEAD >= 227 && !mt_ring_ahead(L.rng) && P->fr.diag)
                 gadd(P->fr.diag + kDiagErrors, 1ull);
@@ -965,15 +913,16 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
             const uint64_t r0 = COUNT ? __builtin_amdgcn_s_memtime() : 0;
             const uint32_t act = resolve<COUNT>(L, res, rt, ru, rv, P->sc, P->fr, P->fb, cnt);
             if (COUNT && first_active_lane()) cnt.c[20] += static_cast<uint32_t>(__builtin_amdgcn_s_memtime() - r0);
-#if BDPT_HELP_BATCH
+#if BDPT_HELP
             act2 = advance<COUNT, 1>(L, act, P->sc, P->fr, P->fb, ls, cnt);
 #else
             advance<COUNT>(L, act, P->sc, P->fr, P->fb, ls, cnt);
 #endif
             if (BDPT_RR == 1) long_walk = L.state != ST_IDLE && L.c.depth > P->fr.express_depth;
         }
-#if BDPT_HELP_BATCH
-        // the connections of the eye vertices reached in this step, over the whole wave
+#if BDPT_HELP
+        // the connections of the eye vertices reached in this step, flattened over the whole wave
+        // (conn_batch; each lane's own connections in turn: 283.0 vs 322.8 Msamples/s)
         if (__ballot(shade_now)) {
             conn_batch<COUNT>(L, shade_now && act2 == A_CONN && P->fr.strategy == 0, P->sc, P->fr, ls, cnt);
             if (shade_now) advance<COUNT, 2>(L, act2, P->sc, P->fr, P->fb, ls, cnt);
@@ -991,10 +940,8 @@ __global__ __launch_bounds__(kBlock, BDPT_WAVES_PER_EU) void BDPT_NAME(bdpt_fram
             if (lane0()) cnt.q[0] += tw, cnt.q[1]++, cnt.q[2] += tw >= 32u, cnt.q[3] += tw >= 64u;
         }
     }
-#if BDPT_SEED_CHUNK && BDPT_EYE_SLOTS
     if (lane0())  // every sample of the wave has finished: the slots' sums to the framebuffer
         for (int k = 0; k < BDPT_EYE_SLOTS; k++) eye_slot_reset(kp.fb, k, -1);
-#endif
     if (lane0() && kpp->fr.diag) gmax(kpp->fr.diag + kDiagEnd, __builtin_amdgcn_s_memrealtime());
 #if BDPT_EXPRESS_PROBE
     if (lane0() && xp_iters) {  // into bdpt_stats.sched (a timed run writes nothing else there)
@@ -1031,10 +978,8 @@ __global__ __launch_bounds__(64) void BDPT_NAME(bdpt_chain_kernel)(const KParams
     __shared__ uint32_t lring[kMtRingSlotWords];
     scene_tables_to_lds(kp.sc);
     const uint32_t lane = threadIdx.x;
-#if BDPT_EYE_SLOTS
     if (lane == 0)  // no eye-estimate slots here: a sample that ends adds to the framebuffer itself
         for (int k = 0; k < BDPT_EYE_SLOTS; k++) wave_eye_slots()[k] = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-#endif
     const DevScene& sc = kp.sc;
     const DevFrame& fr = kp.fr;
     const TravScene tsc = trav_scene(sc);
@@ -1094,10 +1039,8 @@ __global__ __launch_bounds__(64) void BDPT_NAME(bdpt_chain_kernel)(const KParams
                 shade_hit(sc, r, u, v, t, L.ray.d, L.h);
                 const float dist2 = L.h.dist * L.h.dist;
                 const float absCosIn = fabsf(L.h.wo.z);
-#if BDPT_RING_AHEAD
                 if (L.rng.n + BDPT_RING_AHEAD >= 227 && !mt_ring_ahead(L.rng) && fr.diag)
                     gadd(fr.diag + kDiagErrors, 1ull);
-#endif
                 L.c.vcm *= div_cr(dist2, absCosIn);
                 L.c.vc *= rcp_cr(absCosIn);
                 L.c.rr = rr_probability(fr, L.c.depth, L.c.tp);

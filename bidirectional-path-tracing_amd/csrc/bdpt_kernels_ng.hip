@@ -1,5 +1,5 @@
 // The BDPT megakernel for scenes without a glossy lobe: the same source as
-// bdpt_kernels.hip with BDPT_GLOSSY 0 (bdpt_device.hpp). It serves material tables
+// bdpt_kernels.hip with BDPT_GLOSSY 0 (dev_shade.hpp). It serves material tables
 // that hold only DiffuseBSDF, PerfectMirrorBSDF and GlassBSDF records after the
 // upload's Ks = 0 conversion (device_bsdfs, bdpt_capi.cpp), in the renders the
 // default build serves (no Russian roulette, untextured, rrDepth 4..28, LDS records):

@@ -8,7 +8,7 @@
 // cannot trap a subpath (no GlassBSDF) keep bdpt_kernels_rr.hip (HardLight RR
 // 82.9 vs 78.9 Msamples/s). Chosen per render (bdpt_capi.cpp); every host-visible
 // symbol gets an _rrc name.
-// Leaf triangles one at a time (bdpt_device.hpp BDPT_WLEAF_GROUP): with pairs
+// Leaf triangles one at a time (dev_traverse.hpp BDPT_WLEAF_GROUP): with pairs
 // this build's register allocation spills 79 VGPRs instead of 73 (304 instead
 // of 288 bytes of scratch per lane).
 #ifndef BDPT_WLEAF_GROUP

@@ -361,9 +361,9 @@ __device__ __forceinline__ void splat_add(float* __restrict__ fb, int pixel, f3 
 // atomics already are); each framebuffer add is a memory-side request of its
 // own, so ~3 of the ~9 per sample become ~3 per 64 samples.
 #ifndef BDPT_EYE_SLOTS
-#define BDPT_EYE_SLOTS 4
+#define BDPT_EYE_SLOTS 4  // (a count, > 0)
 #endif
-#if BDPT_EYE_SLOTS && !BDPT_SAMPLER_STATE
+#if !BDPT_SAMPLER_STATE
 constexpr int kEyeSlotWaves = 4;  // waves per 256-lane frame-kernel block
 __shared__ float4 eye_slots[kEyeSlotWaves][BDPT_EYE_SLOTS];
 __device__ __forceinline__ float4* wave_eye_slots() { return eye_slots[(threadIdx.x >> 6) & (kEyeSlotWaves - 1)]; }
@@ -484,7 +484,7 @@ constexpr bool kTasks = BDPT_HELP && !BDPT_SAMPLER_STATE;
 // and uses the slot as before (the slot's flush, eye_slot_reset, writes plane 0); an index of
 // another plane matches no slot (slots hold pixels < W * H) and goes to the framebuffer.
 __device__ __forceinline__ void eye_add(float* __restrict__ fb, int pixel, f3 add) {
-#if BDPT_EYE_SLOTS && !BDPT_SAMPLER_STATE
+#if !BDPT_SAMPLER_STATE
     float4* const s = wave_eye_slots();
     int k = -1;
 #pragma unroll
@@ -701,7 +701,7 @@ __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
     } BDPT_END;
 
 // PART 0: the whole sweep; 1: the bodies before connectVertices, returning the
-// action reached; 2: connectVertices and the bodies after it (the BDPT_HELP_BATCH
+// action reached; 2: connectVertices and the bodies after it (the BDPT_HELP
 // schedule runs the wave's connections between the two, conn_batch).
 template <bool COUNT, int PART = 0>
 __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const DevFrame& fr, float* __restrict__ fb,
@@ -1044,14 +1044,12 @@ __device__ __forceinline__ uint32_t sample_seed(uint64_t s, const DevFrame& fr, 
 }
 
 // Starts sample `s` of the shard on this lane: seed, camera ray, primary query.
-// x397 = mt_x397(seed) when the caller precomputed it (HAVE_X397).
-template <bool HAVE_X397 = false>
-__device__ __forceinline__ void start_sample(Lane& L, uint64_t s, const DevFrame& fr, uint32_t x397 = 0) {
+// x397 = mt_x397(seed), which the caller computed for the whole chunk at once.
+__device__ __forceinline__ void start_sample(Lane& L, uint64_t s, const DevFrame& fr, uint32_t x397) {
     int pixel;
     const uint32_t seed = sample_seed(s, fr, pixel);
     L.c.pixel = pixel;
-    if (HAVE_X397) mt_seed_with(L.rng, seed, x397);
-    else mt_seed(L.rng, seed);
+    mt_seed_with(L.rng, seed, x397);
     L.c.cam_d = camera_dir(fr, L.c.pixel, L.rng);
     L.ray = Ray{mk(fr.cam_o[0], fr.cam_o[1], fr.cam_o[2]), L.c.cam_d, 1.f, 1000.f};
     L.c.Li = mk(0.f, 0.f, 0.f);
@@ -1062,7 +1060,7 @@ __device__ __forceinline__ void start_sample(Lane& L, uint64_t s, const DevFrame
 __device__ __forceinline__ bool is_shadow_state(uint32_t st) { return st == ST_SPLAT || st == ST_NEE || st == ST_CONN; }
 
 // The near-cull threshold of the lane's pending query (kGrazeCos, graze_exempt,
-// bdpt_device.hpp): none for a query that leaves the current vertex (or, for the
+// dev_traverse.hpp): none for a query that leaves the current vertex (or, for the
 // first light-subpath ray, the emitter: A_START_LIGHT puts its normal and face
 // code in L.h) nearly parallel to its triangle's plane; camera queries keep it.
 __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d) {
@@ -1183,14 +1181,6 @@ __device__ __forceinline__ bool closest_apply(Lane& L, int& res, float t, float 
     return true;
 }
 #endif
-
-// Schedules without an overlapped walk run a deferred action at once.
-template <bool COUNT>
-__device__ __forceinline__ void run_deferred(Lane& L, const DevScene& sc, const DevFrame& fr, float* __restrict__ fb,
-                                             const LightStore& ls, Counts& cnt) {
-    while (L.state == ST_DEFER)
-        advance<COUNT>(L, resolve<COUNT>(L, -1, 0.f, 0.f, 0.f, sc, fr, fb, cnt), sc, fr, fb, ls, cnt);
-}
 
 // out: kCounters sums, then the 3 maxima of Counts::m.
 __device__ __forceinline__ void flush_counts(const Counts& cnt, unsigned long long* out) {

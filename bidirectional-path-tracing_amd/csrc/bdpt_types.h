@@ -76,7 +76,7 @@ constexpr int kShadeV0 = 5;  // slot of (v0, 0) in a wide record
 // coordinates (s0 t0 s1 t1) (s2 t2 0 0), zero otherwise (as before).
 constexpr int kShadeSt = 6;
 // The triangle's reference leaf box (wide_bvh.hpp; DevScene::lbox), for the deferred
-// leaf check of a closest hit (bdpt_device.hpp leaf_box_passes): in the same two slots
+// leaf check of a closest hit (dev_shade.hpp leaf_box_passes): in the same two slots
 // (lo, 0) (hi, 0), the bits of lbox[2 * leaf], lbox[2 * leaf + 1], in a scene without
 // bitmap textures; with them the slots hold the texture coordinates and the last word
 // (slot 7's w) the leaf id.
@@ -84,7 +84,7 @@ constexpr int kShadeBox = 6;
 
 constexpr uint32_t kLeafBit = 0x80000000u;
 // Words per lane slot of the BDPT megakernel's MT19937 ring (DevScene::mt_ring):
-// the 624-word ring and the generate-ahead cursor (bdpt_device.hpp, mt_ring_ahead).
+// the 624-word ring and the generate-ahead cursor (dev_rng.hpp, mt_ring_ahead).
 constexpr uint32_t kMtRingSlotWords = 640;
 // Words per lane slot of the Russian-roulette continuation records (DevFrame::park;
 // bdpt_kernels.hip, park_save); the list of parked slots follows the records.

@@ -8,7 +8,7 @@
 // of the path against the reference's own functions.
 //
 // The BSDF kernel is compiled three times, because the frame kernels compile its
-// device functions three ways (bdpt_device.hpp, device_math.hpp):
+// device functions three ways (dev_shade.hpp, device_math.hpp):
 //   kat_kernels.hip     IEEE weights, BDPT_GLOSSY 1: the Russian-roulette and single-
 //                       sample builds' arithmetic (bit-exact to the reference)
 //   kat_kernels_fw.hip  BDPT_FAST_WEIGHTS 1: the default frame kernels' (pow_w on

@@ -9,7 +9,7 @@
 // and per ray whether it was walked again.
 #include <hip/hip_runtime.h>
 
-#include "bdpt_path.hpp"
+#include "dev_shade.hpp"
 
 namespace bdpt {
 namespace dev {

@@ -175,10 +175,6 @@ enum : int {  // explicit-level steps between queries
     PS_WAIT,        // a query was issued
 };
 
-// Runs the lane from step `ps` until it issues a query or finishes its sample.
-#ifndef PT_INLINE_ADVANCE
-#define PT_INLINE_ADVANCE 1  // pt_advance inlined: the lane state stays in registers (not scratch)
-#endif
 // The overlapped walk / advance schedule (as the BDPT megakernel's) runs for
 // the path tracer (+9 % on Caustic, 512²×64); the direct integrator's one-level
 // samples are faster without it (1439 vs 1334 Msamples/s).
@@ -186,26 +182,18 @@ enum : int {  // explicit-level steps between queries
 #define PT_SHADE_READY 56
 #endif
 #ifndef PT_TRAV_SPLIT
-#define PT_TRAV_SPLIT 8
+#define PT_TRAV_SPLIT 8  // a leaf step if 4 * leaf lanes >= SPLIT * node lanes (as BDPT_TRAV_SPLIT)
 #endif
 #ifndef PT_WALK_UNROLL
 #define PT_WALK_UNROLL 1  // extra interior-node steps per walk iteration, after either kind of step (path +0.8 %)
 #endif
-#ifndef PT_EARLY_COS
-#define PT_EARLY_COS 1  // emitter samples rejected on the cosine (dot(v, n), the frame z) before the shading frame is built (+0.7 % path tracer)
-#endif
-#ifndef PT_ROOT_LDS
-#define PT_ROOT_LDS 1  // the overlapped schedule's walks start two levels down (RootLds, as the BDPT megakernel)
-#endif
 #ifndef PT_WAVES_PER_EU
 #define PT_WAVES_PER_EU 4  // 128 VGPRs, 4 blocks of 256 lanes per CU
 #endif
-#if PT_INLINE_ADVANCE
-__device__ __forceinline__
-#else
-__device__
-#endif
-void pt_advance(PtLane& L, int ps, f3 Lr, const PtParams& P, uint32_t slot) {
+// Runs the lane from step `ps` until it issues a query or finishes its sample. Inlined: the
+// lane state stays in registers (not scratch). Emitter samples are rejected on the cosine
+// (dot(v, n), the frame z) before the shading frame is built (+0.7 % path tracer).
+__device__ __forceinline__ void pt_advance(PtLane& L, int ps, f3 Lr, const PtParams& P, uint32_t slot) {
     const DevScene& sc = P.sc;
     const PtSettings& S = P.ps;
     for (int guard = 0; guard < 1 << 20; guard++) {
@@ -245,19 +233,11 @@ void pt_advance(PtLane& L, int ps, f3 Lr, const PtParams& P, uint32_t slot) {
                 f3 en, ep;
                 const int id = sample_emitter(sc, L.rng, epdf, en, ep, eapdf);
                 const f3 wiW = normalize(ep - L.h.p);
-#if PT_EARLY_COS
                 const f3 dd = L.h.p - ep;  // glm::distance2(positionOut, hit.p)
                 const float d2 = dot(dd, dd);
                 const float cosOut = dot(-wiW, en);
                 if (cosOut > 0.f && dot(wiW, L.h.n) > 0.f) {  // dot(v, n) = the frame's z (to_local)
                     const f3 wil = local_at(L.h.n, wiW);
-#else
-                const f3 wil = local_at(L.h.n, wiW);
-                const f3 dd = L.h.p - ep;  // glm::distance2(positionOut, hit.p)
-                const float d2 = dot(dd, dd);
-                const float cosOut = dot(-wiW, en);
-                if (cosOut > 0.f && wil.z > 0.f) {
-#endif
                     L.e_shape = emitter_of(sc, id).shape;
                     L.e_cos = cosOut, L.e_d2 = d2, L.e_pdf = epdf, L.e_apdf = eapdf, L.e_wil = wil;
                     L.ray = pt_ray(L.h.p, wiW);
@@ -374,13 +354,8 @@ void pt_advance(PtLane& L, int ps, f3 Lr, const PtParams& P, uint32_t slot) {
                     const f3 dd = L.h.p - pos;
                     const float d2 = dot(dd, dd);
                     const float cosOut = dot(-wiW, ne);
-#if PT_EARLY_COS
                     if (cosOut <= 0.f || dot(wiW, L.h.n) <= 0.f) break;
                     const f3 wil = local_at(L.h.n, wiW);
-#else
-                    const f3 wil = local_at(L.h.n, wiW);
-                    if (cosOut <= 0.f || wil.z <= 0.f) break;
-#endif
                     L.e_id = static_cast<int>(id), L.e_pdf = epdf, L.e_apdf = pdf, L.e_wil = wil;
                     L.e_cos = cosOut * rcp_cr(d2);  // areaToSolidAngle
                     L.ray = Ray{L.h.p, wiW, kEpsilon, sqrt_cr(d2) - kEpsilon};
@@ -389,13 +364,8 @@ void pt_advance(PtLane& L, int ps, f3 Lr, const PtParams& P, uint32_t slot) {
                 }
                 float pdf;  // solid angle (direct.h:262-309) or MIS (:333-372)
                 const f3 wiW = sphere_solid_angle(u, L.h.p, center, e.radius, pdf);
-#if PT_EARLY_COS
                 if (dot(wiW, L.h.n) <= 0.f) break;
                 const f3 wil = local_at(L.h.n, wiW);
-#else
-                const f3 wil = local_at(L.h.n, wiW);
-                if (wil.z <= 0.f) break;
-#endif
                 L.e_id = static_cast<int>(id), L.e_pdf = epdf, L.e_apdf = pdf, L.e_wil = wil;
                 const f3 dc = center - L.h.p;
                 L.ray = Ray{L.h.p, wiW, kEpsilon, st == DI_SOLID_ANGLE ? sqrt_cr(dot(dc, dc)) + kEpsilon
@@ -598,11 +568,11 @@ template <bool COUNT, bool OVERLAP, bool SLACK = true>
 __global__ __launch_bounds__(256, PT_WAVES_PER_EU) void pt_frame_kernel(const PtParams* __restrict__ pp) {
     const PtParams& P = *pp;
     __shared__ uint2 stack_mem[kLdsStack * 256];
-#if PT_ROOT_LDS
-    __shared__ RootLds root_lds;  // the walk's first two node tests at query issue (bdpt_device.hpp)
+    // the overlapped schedule's walks start two levels down: the first two node tests at
+    // query issue (RootLds, dev_traverse.hpp; as the BDPT megakernel)
+    __shared__ RootLds root_lds;
     const bool root_in_lds = OVERLAP && root_lds_usable(P.sc);
     if (OVERLAP) root_lds_fill(root_lds, P.sc);
-#endif
     scene_tables_to_lds(P.sc);
     const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
     const Stack stk{stack_mem + threadIdx.x, 256, kLdsStack, P.gstack, P.nslots, slot};
@@ -670,13 +640,11 @@ __global__ __launch_bounds__(256, PT_WAVES_PER_EU) void pt_frame_kernel(const Pt
             } else {
                 ts = trav_begin(tsc, L.ray);
                 tracing = true;
-#if PT_ROOT_LDS
                 if (root_in_lds && !walk_begin_lds<COUNT, SLACK>(root_lds, L.ray, ri, false, ts, stk, cnt)) {
                     res = -1, rt = ts.best_t, ru = ts.best_u, rv = ts.best_v;  // no child hit: a miss
                     tracing = false;
                     has_res = true;
                 }
-#endif
             }
         }
         for (;;) {

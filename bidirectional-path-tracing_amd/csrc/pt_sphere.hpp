@@ -4,7 +4,7 @@
 // sampling kernel (kat_sampling.hip).
 #pragma once
 
-#include "bdpt_device.hpp"
+#include "dev_warp.hpp"
 
 namespace bdpt {
 namespace dev {

@@ -1,7 +1,7 @@
 """What every BDPT connection evaluates, per function and per compilation.
 
 connectToLight, connectToCamera and connectVertices go through local_for + bsdf_eval_pdfs
-(bdpt_device.hpp): the fused one-powf form of eval / pdf / reverse pdf and the diffuse frame
+(dev_shade.hpp): the fused one-powf form of eval / pdf / reverse pdf and the diffuse frame
 skip, which bsdf_eval / bsdf_pdf (test_gpu_kat.py) never reach. The frame kernels compile
 them three ways; bdpt_bsdf_eval_pdfs / bdpt_bsdf_local_for run each:
   exact  IEEE weights: bit-equal to the reference's BSDF::eval / pdf, the reverse pdf to

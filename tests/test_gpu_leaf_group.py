@@ -1,4 +1,4 @@
-"""The walk's leaf triangles fetched in pairs (bdpt_device.hpp wleaf_tests,
+"""The walk's leaf triangles fetched in pairs (dev_traverse.hpp wleaf_tests,
 BDPT_WLEAF_GROUP = 2): the same decisions in the same order as one triangle at a
 time.
 

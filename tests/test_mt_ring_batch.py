@@ -1,4 +1,4 @@
-"""The generator ring's batched refill (bdpt_device.hpp mt_ring_ahead_wave): a wave
+"""The generator ring's batched refill (dev_rng.hpp mt_ring_ahead_wave): a wave
 computes outputs g .. g + 63 of std::mt19937 at once, every lane reading its three
 ring words before any lane writes. Checked here on the CPU against numpy's MT19937
 (the same engine as std::mt19937, seeded with std::mt19937's recurrence): the

@@ -5,6 +5,9 @@
 # the texts byte for byte (-cuid=cmp fixes the one symbol that depends on the source
 # path). For refactors of the shared kernel sources: identical assembly is identical
 # behaviour and speed. A unit that does not compile prints its compiler output.
+# EXTRA="-DBDPT_WLEAF_GROUP=1" tools/asm_identity.sh [REF] appends the flags to both sides'
+# compile lines (the side libraries' and the probes' switches); a unit that then compiles
+# on neither side (a flag it never takes) is reported and does not count.
 set -e
 cd "$(dirname "$0")/.."
 PKG=bidirectional-path-tracing_amd
@@ -21,13 +24,15 @@ for side in old new; do
   FLAGS=$(make -s print-FLAGS 2>/dev/null || make -s -C "$T/new/$PKG" print-FLAGS)
   HIPCC=$(make -s -C "$T/new/$PKG" print-HIPCC)
   units $side | tr ' ' '\n' | grep . | xargs -P "${JOBS:-16}" -I{} sh -c \
-    "$HIPCC $FLAGS --cuda-device-only -S -cuid=cmp -x hip csrc/{}.hip -o {}.s 2>{}.log || { echo 'FAILED $side {}:'; cat {}.log; }"
+    "$HIPCC $FLAGS $EXTRA --cuda-device-only -S -cuid=cmp -x hip csrc/{}.hip -o {}.s 2>{}.log || { echo 'FAILED $side {}:'; cat {}.log; }"
   cd - >/dev/null
 done
 if [ "$(units old | tr ' ' '\n' | sort | xargs)" != "$(units new | tr ' ' '\n' | sort | xargs)" ]; then
   echo "unit lists differ: old: $(units old | xargs)  new: $(units new | xargs)"; rc=1
 fi
 for t in $(units new); do
-  if [ -s "$T/old/$PKG/$t.s" ] && cmp -s "$T/old/$PKG/$t.s" "$T/new/$PKG/$t.s"; then echo "same   $t"; else echo "DIFFER $t"; rc=1; fi
+  if [ -s "$T/old/$PKG/$t.s" ] && cmp -s "$T/old/$PKG/$t.s" "$T/new/$PKG/$t.s"; then echo "same   $t"
+  elif [ -n "$EXTRA" ] && [ ! -s "$T/old/$PKG/$t.s" ] && [ ! -s "$T/new/$PKG/$t.s" ]; then echo "neither $t"
+  else echo "DIFFER $t"; rc=1; fi
 done
 exit $rc
