@@ -18,6 +18,10 @@ Mirrors the reference's plugin surface for the BDPT path
     .render_light_groups(map, n) / .relight(groups, gains)
                                        the BDPT frame split by emitter and recombined with per-group RGB gains
                                        (bdpt_render_light_groups, bdpt_light_groups_relight; no counterpart)
+    .render_strategies(n_s, n_t, unweighted) / .strategies_sheet(planes, gains)
+                                       the BDPT frame split by sampling strategy (s, t), with or without the
+                                       MIS weights, and its contact sheet (bdpt_render_strategies,
+                                       bdpt_strategies_sheet; no counterpart)
   Sampler(seed)                        Sampler              src/core/math.h:63-76 (seed + draw count)
   Ray(o, d, min_t, max_t)              Ray                  src/core/core.h:117-122
   load_toml(path) -> SceneConfig       loadTOML             src/main.cpp:22-116
@@ -219,7 +223,7 @@ class _Stats(ctypes.Structure):
 
 # Sources that make up the frame kernels' code objects: their hash stamps the
 # profiles (PMC passes) so bench.py only reuses a measurement of the same kernel.
-KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_kernels_layers.hip", "csrc/bdpt_kernels_groups.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
+KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_kernels_layers.hip", "csrc/bdpt_kernels_groups.hip", "csrc/bdpt_kernels_strat.hip", "csrc/bdpt_kernels_strat_unweighted.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
                   "csrc/dev_scene.hpp", "csrc/dev_rng.hpp", "csrc/dev_warp.hpp", "csrc/dev_traverse.hpp", "csrc/dev_shade.hpp", "csrc/dev_emitter.hpp",
                   "csrc/powf_restated.inc", "csrc/bdpt_types.h", "Makefile")
 
@@ -324,6 +328,10 @@ def lib():
         L.bdpt_render_light_groups.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp, vp, vp]
         L.bdpt_render_light_groups_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp, vp]
         L.bdpt_light_groups_relight.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
+        L.bdpt_render_strategies.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, i32, i32, vp, vp]
+        L.bdpt_render_strategies_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, i32, i32, vp]
+        L.bdpt_strategies_shape.argtypes = [i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        L.bdpt_strategies_sheet.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
         L.bdpt_synchronize.argtypes = [vp]
         L.bdpt_config_load_toml.argtypes = [ctypes.c_char_p, ctypes.POINTER(_Config)]
         L.bdpt_render_path.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_PathParams), vp, vp]
@@ -796,6 +804,70 @@ def layers_longest_path(rr_depth: int, strategy: int = STRATEGY_BDPT) -> int:
     return D if strategy == STRATEGY_PATH_TRACING else 2 * D - 1
 
 
+STRATEGIES_WEIGHTED, STRATEGIES_UNWEIGHTED = 0, 1  # bdpt_render_strategies' weighting (BDPT_STRATEGIES_*)
+STRATEGIES_MAX_S, STRATEGIES_MAX_T = 29, 28
+
+
+def strategies_shape(rr_depth: int, strategy: int = STRATEGY_BDPT) -> tuple:
+    """bdpt_strategies_shape: (n_s, n_t), the smallest render_strategies shape that holds every
+    strategy of an rr_depth without clamping: n_s = max(D, 1) + 1 (s reaches D
+    through a light vertex stored at depth D - 1), n_t = max(D, 2) (t reaches D through an eye
+    vertex at depth D - 1; light tracing's primary emission is (0, 2) whatever D is)."""
+    n_s, n_t = ctypes.c_int32(), ctypes.c_int32()
+    _check(lib().bdpt_strategies_shape(int(rr_depth), int(strategy), ctypes.byref(n_s), ctypes.byref(n_t)))
+    return n_s.value, n_t.value
+
+
+def strategy_plane(s: int, t: int, n_s: int, n_t: int) -> int:
+    """The plane of render_strategies' (n_s, n_t) framebuffer that strategy (s, t) is added to:
+    min(s, n_s - 1) * n_t + min(t, n_t) - 1, the last row and column collecting what is longer
+    (s >= 0 light-subpath vertices, t >= 1 eye-subpath vertices with the camera counted)."""
+    s, t, n_s, n_t = int(s), int(t), int(n_s), int(n_t)
+    if s < 0 or t < 1 or n_s < 1 or n_t < 1:
+        raise ValueError(f"strategy_plane: s >= 0, t >= 1, n_s >= 1, n_t >= 1, got {(s, t, n_s, n_t)}")
+    return min(s, n_s - 1) * n_t + min(t, n_t) - 1
+
+
+def _sheet_args(planes, gains):
+    """strategies_sheet's arguments checked as bdpt_strategies_sheet checks them (before anything is
+    copied): planes (n_s, n_t, H, W, 3) within the shape limits and below 2^31 floats, gains None or
+    finite (n_s, n_t, 3) / (n_s, n_t) / (n_s * n_t, 3). -> (float32 planes, float32 (n_s * n_t, 3) or None)."""
+    shape = np.shape(planes)
+    if len(shape) != 5 or shape[4] != 3:
+        raise BdptError(f"strategies_sheet: planes must be (n_s, n_t, H, W, 3), got {shape}")
+    n_s, n_t, H, W = shape[:4]
+    if not 1 <= n_s <= STRATEGIES_MAX_S or not 1 <= n_t <= STRATEGIES_MAX_T or H < 1 or W < 1:
+        raise BdptError(f"strategies_sheet: n_s must be in [1, 29], n_t in [1, 28], H and W > 0, got {shape}")
+    if n_s * n_t * H * W * 3 >= 1 << 31:
+        raise BdptError("strategies_sheet: the sheet (n_s * n_t * W * H * 3 floats) must be below 2^31 floats")
+    g = None
+    if gains is not None:
+        g = np.asarray(gains, np.float32)
+        if g.shape == (n_s, n_t):
+            g = np.repeat(g[:, :, None], 3, axis=2)
+        if g.shape not in ((n_s, n_t, 3), (n_s * n_t, 3)):
+            raise BdptError(f"strategies_sheet: gains must be ({n_s}, {n_t}, 3), ({n_s}, {n_t}) or "
+                            f"({n_s * n_t}, 3), got {g.shape}")
+        g = np.ascontiguousarray(g.reshape(n_s * n_t, 3))
+        if not np.isfinite(g).all():
+            raise BdptError("strategies_sheet: a gain is not finite")
+    return np.ascontiguousarray(planes, np.float32), g
+
+
+def strategies_sheet_numpy(planes, gains=None) -> np.ndarray:
+    """What bdpt_strategies_sheet computes, as the obvious loop on the host: the (n_t * H, n_s * W, 3)
+    float32 image with the tile of (s, t) at tile column s, tile row t - 1, each float one float32
+    product gains[s, t - 1, c] * planes[s, t - 1, y, x, c] (no gains: the plane's float)."""
+    a, g = _sheet_args(planes, gains)
+    n_s, n_t, H, W = a.shape[:4]
+    out = np.zeros((n_t * H, n_s * W, 3), np.float32)
+    for s in range(n_s):
+        for r in range(n_t):  # r = t - 1
+            tile = a[s, r] if g is None else g[s * n_t + r][None, None, :] * a[s, r]
+            out[r * H:(r + 1) * H, s * W:(s + 1) * W] = tile
+    return out
+
+
 class BDPTIntegrator:
     """GPU BDPT integrator with the reference's Integrator interface."""
 
@@ -1193,6 +1265,71 @@ class BDPTIntegrator:
         _check(lib().bdpt_light_groups_relight(self._h, ctypes.c_void_p(groups_ptr), int(n_groups), int(width),
                                                int(height), g.ctypes.data, ctypes.c_void_p(out_ptr),
                                                ctypes.c_void_p(stream_ptr)))
+
+    def _strategies_shape(self, n_s, n_t):
+        if n_s is None or n_t is None:  # (a given shape reaches the library as it is)
+            d_s, d_t = strategies_shape(self.config.rr_depth, self.config.strategy)
+            return (d_s if n_s is None else int(n_s)), (d_t if n_t is None else int(n_t))
+        return int(n_s), int(n_t)
+
+    def render_strategies(self, n_s: int | None = None, n_t: int | None = None, unweighted: bool = False,
+                          window: SampleWindow | None = None, row_offset: int = 0, row_stride: int = 1,
+                          flags: int = 0) -> np.ndarray:
+        """bdpt_render_strategies_host: the BDPT frame split by sampling strategy, a new
+        (n_s, n_t, H, W, 3) array. out[s, t - 1] holds the contributions formed with s light-subpath
+        and t eye-subpath vertices (the camera counted), the last row and column everything longer;
+        the default shape, strategies_shape(rr_depth, strategy), clamps nothing. Weighted, the planes
+        sum to render_frame()'s frame; unweighted, no contribution carries its MIS weight and each
+        plane is its strategy's plain estimator. `unweighted` may also be a STRATEGIES_* value."""
+        H, W = self.config.height, self.config.width
+        p = self.params(row_offset, row_stride, flags)
+        w = window.c() if window is not None else None
+        n_s, n_t = self._strategies_shape(n_s, n_t)
+        # a shape or size the library refuses (before it touches the buffer) is not allocated here
+        ok = 1 <= n_s <= STRATEGIES_MAX_S and 1 <= n_t <= STRATEGIES_MAX_T and n_s * n_t * W * H < 1 << 30
+        out = np.zeros((n_s, n_t, H, W, 3) if ok else (1,), np.float32)
+        _check(lib().bdpt_render_strategies_host(self._h, ctypes.byref(p), w and ctypes.byref(w), n_s, n_t,
+                                                 int(unweighted), out.ctypes.data))
+        return out
+
+    def render_strategies_device(self, fb_ptr: int, n_s: int | None = None, n_t: int | None = None,
+                                 unweighted: bool = False, stream_ptr: int = 0, window: SampleWindow | None = None,
+                                 row_offset: int = 0, row_stride: int = 1) -> None:
+        """bdpt_render_strategies: asynchronous, ADDED to a device buffer of n_s * n_t * H * W * 3 floats."""
+        p = self.params(row_offset, row_stride, 0)
+        w = window.c() if window is not None else None
+        n_s, n_t = self._strategies_shape(n_s, n_t)
+        _check(lib().bdpt_render_strategies(self._h, ctypes.byref(p), w and ctypes.byref(w), n_s, n_t,
+                                            int(unweighted), ctypes.c_void_p(fb_ptr), ctypes.c_void_p(stream_ptr)))
+
+    def strategies_sheet(self, planes, gains=None) -> np.ndarray:
+        """bdpt_strategies_sheet on the device: the contact sheet of render_strategies' planes, an
+        (n_t * H, n_s * W, 3) float32 image with the tile of (s, t) at tile column s, tile row t - 1,
+        each tile times its gain (gains: (n_s, n_t, 3) RGB or (n_s, n_t) grey; None: copied). The
+        bits of strategies_sheet_numpy. The planes go to the device and the sheet comes back."""
+        import torch
+
+        a, g = _sheet_args(planes, gains)
+        n_s, n_t, H, W = a.shape[:4]
+        dev = torch.device("cuda", self.device)
+        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+        d_out = torch.zeros((n_t * H, n_s * W, 3), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.strategies_sheet_device(d_in.data_ptr(), n_s, n_t, W, H, g, d_out.data_ptr())
+        self.synchronize()
+        return d_out.cpu().numpy()
+
+    def strategies_sheet_device(self, planes_ptr: int, n_s: int, n_t: int, width: int, height: int, gains,
+                                out_ptr: int, stream_ptr: int = 0) -> None:
+        """bdpt_strategies_sheet: asynchronous, on device buffers; gains: None or host n_s * n_t x 3 float32."""
+        g = None
+        if gains is not None:
+            g = np.ascontiguousarray(gains, np.float32)
+            if g.size != 3 * int(n_s) * int(n_t):
+                raise BdptError(f"strategies_sheet_device: gains must hold {n_s} x {n_t} x 3 floats, got {g.size}")
+        _check(lib().bdpt_strategies_sheet(self._h, ctypes.c_void_p(planes_ptr), int(n_s), int(n_t), int(width),
+                                           int(height), None if g is None else g.ctypes.data,
+                                           ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream_ptr)))
 
     def denoise(self, rgb=None, aov=None, samples_done: int | None = None, **params) -> np.ndarray:
         """bdpt_denoise_host of rgb (default self.rgb) guided by aov (default self.aov): a new

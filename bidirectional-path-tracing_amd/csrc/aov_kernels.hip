@@ -237,7 +237,43 @@ __global__ __launch_bounds__(256) void relight_kernel(const float* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------ strategy images
+// The contact sheet of a strategy render (bdpt_render_strategies: n_s * n_t planes of W x H x 3
+// floats, plane s * n_t + t - 1): one image of n_s columns by n_t rows of W x H tiles, the tile
+// of (s, t) at column s, row t - 1. Float i of the sheet is gains[plane][channel] * the plane's
+// float (gains null: the plane's float itself): one float32 product, no atomics, every output
+// written once by one lane — the same bits every run and the bits of that loop on the host.
+// Grid-stride over the sheet's floats (fewer than 2^31: bdpt_strategies_sheet checks), so a
+// wave writes 256 consecutive bytes and reads 256 consecutive bytes of one plane (two at a
+// tile's edge).
+__global__ __launch_bounds__(256) void strategies_sheet_kernel(const float* __restrict__ planes, int n_s, int n_t,
+                                                               int W, int H, const float* __restrict__ gains,
+                                                               float* __restrict__ out) {
+    const uint32_t row = 3u * static_cast<uint32_t>(n_s) * static_cast<uint32_t>(W);  // floats per sheet row
+    const uint32_t total = row * static_cast<uint32_t>(n_t) * static_cast<uint32_t>(H);
+    const size_t plane_floats = static_cast<size_t>(W) * H * 3;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        const uint32_t Y = i / row, q = i % row;  // sheet row; float within it
+        const uint32_t X = q / 3u, c = q % 3u;
+        const uint32_t s = X / static_cast<uint32_t>(W), x = X % static_cast<uint32_t>(W);
+        const uint32_t r = Y / static_cast<uint32_t>(H), y = Y % static_cast<uint32_t>(H);  // r = t - 1
+        const uint32_t plane = s * static_cast<uint32_t>(n_t) + r;
+        const float v = gld1(planes + plane * plane_floats + (static_cast<size_t>(y) * W + x) * 3 + c);
+        gst1(out + i, gains ? gld1(gains + 3u * plane + c) * v : v);
+    }
+}
+
 }  // namespace dev
+
+// gains: a device table of n_s * n_t x 3 floats, or null. The sheet has fewer than 2^31 floats.
+hipError_t launch_strategies_sheet(const float* planes, int n_s, int n_t, int W, int H, const float* gains, float* out,
+                                   hipStream_t st) {
+    const size_t total = static_cast<size_t>(n_s) * n_t * W * H * 3;
+    if (total == 0) return hipSuccess;
+    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((total + 255) / 256, 4096));
+    hipLaunchKernelGGL(dev::strategies_sheet_kernel, dim3(blocks), dim3(256), 0, st, planes, n_s, n_t, W, H, gains, out);
+    return hipGetLastError();
+}
 
 // gains: n_groups x 3 floats (host). n is a multiple of 3 (W * H * 3).
 hipError_t launch_relight(const float* planes, size_t n, int n_groups, const float* gains, float* out, hipStream_t st) {

@@ -22,7 +22,7 @@
 namespace bdpt {
 // The builds of the BDPT frame kernel (bdpt_kernels_<x>.hip; FrameBuild: bdpt_device.hpp)
 extern FrameBuild frame_build, frame_build_tex, frame_build_rr, frame_build_rrc, frame_build_deep,
-    frame_build_hbm, frame_build_split, frame_build_ng, frame_build_layers, frame_build_groups;
+    frame_build_hbm, frame_build_split, frame_build_ng, frame_build_layers, frame_build_groups, frame_build_strat, frame_build_strat_unweighted;
 // sample_state.hip: the single-sample kernels (the caller's std::mt19937 state at sc.mt_ring)
 hipError_t launch_sample(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf, uint2* gstack,
                          const dev::Ray& ray, float* out, hipStream_t stream);
@@ -75,6 +75,9 @@ hipError_t launch_denoise_iter(int W, int H, int step, float inv_c, float inv_n,
 hipError_t launch_layers_compose(const float* layers, size_t n, uint64_t mask, float* out, hipStream_t st);
 // aov_kernels.hip: light-group planes (n floats each) recombined with per-group RGB gains (host, n_groups x 3)
 hipError_t launch_relight(const float* planes, size_t n, int n_groups, const float* gains, float* out, hipStream_t st);
+// aov_kernels.hip: the contact sheet of n_s x n_t strategy planes (gains: a device table of n_s * n_t x 3 floats, or null)
+hipError_t launch_strategies_sheet(const float* planes, int n_s, int n_t, int W, int H, const float* gains, float* out,
+                                   hipStream_t st);
 }  // namespace bdpt
 
 using namespace bdpt;
@@ -285,6 +288,9 @@ struct bdpt_ctx : CtxStream {
     // host copy it is uploaded from (the caller's array is not read after the call returns)
     DevBuf<int32_t> emitter_group;
     std::vector<int32_t> emitter_group_host;
+    // bdpt_strategies_sheet: the call's per-plane RGB gains, likewise
+    DevBuf<float> sheet_gains;
+    std::vector<float> sheet_gains_host;
     DevBuf<int32_t> row_order;  // bdpt_set_row_order (device copy; DevFrame::row_order)
     int32_t row_order_n = 0;    // its row count (0: top to bottom)
     DevBuf<unsigned long long> row_cost;  // counting renders: queries per local row (DevFrame::row_cost)
@@ -1082,21 +1088,43 @@ static const FrameBuild& pick_frame_build(const bdpt_ctx* c, const bdpt_frame_pa
     return frame_build;
 }
 
-// A frame kept as several planes (DESIGN.md §7d, §7e): split by path length (bdpt_render_layers,
-// bdpt_kernels_layers.hip) or by emitter group (bdpt_render_light_groups, bdpt_kernels_groups.hip).
+// A frame kept as several planes (DESIGN.md §7d, §7e, §7f): split by path length (bdpt_render_layers,
+// bdpt_kernels_layers.hip), by emitter group (bdpt_render_light_groups, bdpt_kernels_groups.hip) or by
+// sampling strategy (bdpt_render_strategies, bdpt_kernels_strat.hip / _strat_unweighted.hip).
 // kNone: the plain frame.
 constexpr int kMaxLayers = 64;  // a layer mask is one 64-bit word (bdpt_layers_compose)
 constexpr int kMaxGroups = 64;  // the relight kernel's gains are a kernel argument (bdpt_light_groups_relight)
 struct Planes {
-    enum Kind { kNone, kLayers, kGroups } kind = kNone;
-    int n = 1;                               // planes in the framebuffer
+    enum Kind { kNone, kLayers, kGroups, kStrats } kind = kNone;
+    int n = 1;                               // planes in the framebuffer (kStrats: strategy_planes fills it in)
     const int32_t* group_of_emitter = nullptr;  // kGroups: the caller's host map (null: identity)
+    int n_s = 0, n_t = 0, weighting = 0;     // kStrats: the shape (n = n_s * n_t) and BDPT_STRATEGIES_*
 };
+constexpr int kMaxStratS = kLazyRrDepth + 1, kMaxStratT = kLazyRrDepth;  // every strategy of rr_depth 28
+static Planes strategy_planes(int32_t n_s, int32_t n_t, int32_t weighting) {
+    Planes pl;
+    pl.kind = Planes::kStrats;
+    pl.n_s = n_s, pl.n_t = n_t, pl.weighting = weighting;
+    // (a shape check_planes refuses keeps n = 1: nothing is sized by it)
+    if (n_s >= 1 && n_s <= kMaxStratS && n_t >= 1 && n_t <= kMaxStratT) pl.n = n_s * n_t;
+    return pl;
+}
 
-// What the two plane builds serve, checked after check_params and before any launch; the
-// messages name the entry point and its count (n_layers / n_groups).
+// What the plane builds serve, checked after check_params and before any launch; the
+// messages name the entry point and its count (n_layers / n_groups / n_s, n_t).
 static int check_planes(const bdpt_ctx* c, const bdpt_frame_params* p, const Planes& pl) {
     const bool groups = pl.kind == Planes::kGroups;
+    if (pl.kind == Planes::kStrats) {
+        const std::string entry = "bdpt_render_strategies: ";
+        if (pl.n_s < 1 || pl.n_s > kMaxStratS) return fail(BDPT_ERR_INVALID, entry + "n_s must be in [1, 29]");
+        if (pl.n_t < 1 || pl.n_t > kMaxStratT) return fail(BDPT_ERR_INVALID, entry + "n_t must be in [1, 28]");
+        if (pl.weighting != BDPT_STRATEGIES_WEIGHTED && pl.weighting != BDPT_STRATEGIES_UNWEIGHTED)
+            return fail(BDPT_ERR_INVALID, entry + "weighting must be BDPT_STRATEGIES_WEIGHTED (0) or "
+                                                  "BDPT_STRATEGIES_UNWEIGHTED (1)");
+        if (static_cast<int64_t>(pl.n_s) * pl.n_t * p->width * p->height >= (int64_t{1} << 30))
+            return fail(BDPT_ERR_INVALID, entry + "n_s * n_t * W * H must be below 2^30 (the shadow-ray task record's "
+                                                  "pixel field)");
+    } else {
     const std::string entry = groups ? "bdpt_render_light_groups" : "bdpt_render_layers";
     const std::string count = groups ? "n_groups" : "n_layers";
     if (pl.n < 1 || pl.n > (groups ? kMaxGroups : kMaxLayers))
@@ -1115,6 +1143,7 @@ static int check_planes(const bdpt_ctx* c, const bdpt_frame_params* p, const Pla
                 return fail(BDPT_ERR_INVALID, entry + ": group_of_emitter[" + std::to_string(e) + "] = " +
                                               std::to_string(pl.group_of_emitter[e]) + " is outside [0, n_groups)");
     }
+    }
     const char* what = p->flags != 0                              ? "with flags (a counting pass or full traversal)"
                        : p->russian_roulette != BDPT_RR_NONE      ? "with Russian roulette"
                        : p->rr_depth > kLazyRrDepth               ? "with rr_depth > 28"
@@ -1122,7 +1151,11 @@ static int check_planes(const bdpt_ctx* c, const bdpt_frame_params* p, const Pla
                        : c->sc.lds_bsdf_off == dev::kNoLds        ? "with the BSDF records in HBM (too many materials "
                                                                     "for the LDS table)"
                                                                   : nullptr;
-    if (what) return fail(BDPT_ERR_UNSUPPORTED, std::string(groups ? "light groups" : "path-length layers") + " are not built " + what);
+    if (what)
+        return fail(BDPT_ERR_UNSUPPORTED, std::string(pl.kind == Planes::kStrats ? "strategies (per-(s, t) images)"
+                                                      : groups                   ? "light groups"
+                                                                                 : "path-length layers") +
+                                              " are not built " + what);
     return BDPT_OK;
 }
 
@@ -1142,6 +1175,7 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
     dev::DevFrame fr = make_frame(p, w);
     fr.capped = c->capped;
     fr.n_layers = pl.kind == Planes::kLayers ? pl.n : 0;
+    if (pl.kind == Planes::kStrats) fr.strat_shape = pl.n_s << 8 | pl.n_t;  // (shares n_layers' word)
     if (!fr.rr_mode && fr.total_samples > 0 && (rc = ensure_tasks(c))) return rc;
     fr.tasks = c->tasks;
     fr.task_cap = c->task_cap;
@@ -1210,7 +1244,9 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
     if (fr.total_samples > 0) {
         const FrameBuild& b = pl.kind == Planes::kLayers   ? frame_build_layers
                               : pl.kind == Planes::kGroups ? frame_build_groups
-                                                           : pick_frame_build(c, p);
+                              : pl.kind == Planes::kStrats
+                                  ? (pl.weighting == BDPT_STRATEGIES_UNWEIGHTED ? frame_build_strat_unweighted : frame_build_strat)
+                                  : pick_frame_build(c, p);
         c->last_kernel_glossy = 1;  // (until the launches below have succeeded)
         // Never more resident blocks than the slots allocated. c->grid is the default build's
         // blocks_per_cu of these LDS bytes (the HBM build's on an HBM table; bdpt_ctx_create),
@@ -1258,6 +1294,57 @@ int bdpt_render_layers(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
 int bdpt_render_light_groups(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_groups,
                              const int32_t* group_of_emitter, float* fb_groups, void* hip_stream) {
     return render_bdpt(c, p, w, fb_groups, hip_stream, Planes{Planes::kGroups, n_groups, group_of_emitter});
+}
+
+int bdpt_render_strategies(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_s, int32_t n_t,
+                           int32_t weighting, float* fb_planes, void* hip_stream) {
+    return render_bdpt(c, p, w, fb_planes, hip_stream, strategy_planes(n_s, n_t, weighting));
+}
+
+int bdpt_strategies_shape(int32_t rr_depth, int32_t strategy, int32_t* n_s, int32_t* n_t) {
+    if (!n_s || !n_t) return fail(BDPT_ERR_INVALID, "null argument");
+    if (rr_depth < 1 || rr_depth > kLazyRrDepth)
+        return fail(BDPT_ERR_INVALID, "bdpt_strategies_shape: rr_depth must be in [1, 28]");
+    if (strategy < BDPT_STRATEGY_BDPT || strategy > BDPT_STRATEGY_PATH_TRACING)
+        return fail(BDPT_ERR_INVALID, "bdpt_strategies_shape: strategy must be a BDPT_STRATEGY_* value");
+    // s reaches D through a light vertex stored at depth D - 1, t through an eye vertex at depth
+    // D - 1; light tracing's primary emission is (0, 2) whatever D is. One shape for the three
+    // strategies: the planes of a frame's light- and path-tracing forms line up with its BDPT form's.
+    *n_s = std::max(rr_depth, 1) + 1;
+    *n_t = std::max(rr_depth, 2);
+    return BDPT_OK;
+}
+
+int bdpt_strategies_sheet(bdpt_ctx* c, const float* planes, int32_t n_s, int32_t n_t, int32_t width, int32_t height,
+                          const float* gains, float* out, void* hip_stream) {
+    if (!c || !planes || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    if (n_s < 1 || n_s > kMaxStratS) return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: n_s must be in [1, 29]");
+    if (n_t < 1 || n_t > kMaxStratT) return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: n_t must be in [1, 28]");
+    if (width <= 0 || height <= 0) return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: width/height must be > 0");
+    const int64_t floats = static_cast<int64_t>(n_s) * n_t * width * height * 3;
+    if (floats >= (int64_t{1} << 31))
+        return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: the sheet (n_s * n_t * W * H * 3 floats) must be below 2^31 floats");
+    const int ngain = 3 * n_s * n_t;
+    for (int i = 0; gains && i < ngain; i++)
+        if (!std::isfinite(gains[i]))
+            return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: gains[" + std::to_string(i / 3) + "][" +
+                                              std::to_string(i % 3) + "] is not finite");
+    const uintptr_t a = reinterpret_cast<uintptr_t>(planes), o = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t bytes = static_cast<uintptr_t>(floats) * sizeof(float);  // the planes' and the sheet's size alike
+    if (o < a + bytes && a < o + bytes) return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: out overlaps the planes");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if (int rc = begin_use(c, st)) return rc;
+    const float* dgains = nullptr;
+    if (gains) {  // the call's table, from the context's own host copy, in stream order
+        c->sheet_gains_host.assign(gains, gains + ngain);
+        HIP_TRY(c->sheet_gains.reserve(sizeof(float) * 3 * kMaxStratS * kMaxStratT));
+        HIP_TRY(hipMemcpyAsync(c->sheet_gains, c->sheet_gains_host.data(), sizeof(float) * ngain, hipMemcpyHostToDevice, st));
+        dgains = c->sheet_gains;
+    }
+    if (int rc = begin_timed(c, st)) return rc;
+    HIP_TRY(launch_strategies_sheet(planes, n_s, n_t, width, height, dgains, out, st));
+    return end_timed(c, st, 0, 1);
 }
 
 int bdpt_light_groups_relight(bdpt_ctx* c, const float* fb_groups, int32_t n_groups, int32_t width, int32_t height,
@@ -1716,6 +1803,29 @@ int bdpt_render_host(bdpt_ctx* c, const bdpt_frame_params* p, float* fb_host) {
 int bdpt_render_layers_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_layers,
                             float* fb_layers_host) {
     return render_bdpt_host(c, p, w, fb_layers_host, Planes{Planes::kLayers, n_layers});
+}
+
+int bdpt_strategies_sheet_host(bdpt_ctx* c, const float* planes, int32_t n_s, int32_t n_t, int32_t width, int32_t height,
+                               const float* gains, float* out) {
+    if (!c || !planes || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    // a shape the device form refuses: refused by it (its first checks, which read no pointer) before anything is staged
+    const bool shape_ok = n_s >= 1 && n_s <= kMaxStratS && n_t >= 1 && n_t <= kMaxStratT && width > 0 && height > 0 &&
+                          static_cast<int64_t>(n_s) * n_t * width * height * 3 < (int64_t{1} << 31);
+    if (!shape_ok) return bdpt_strategies_sheet(c, planes, n_s, n_t, width, height, gains, out, c->stream);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = static_cast<size_t>(n_s) * n_t * width * height * 3;
+    HIP_TRY(c->tmp_fb.reserve(2 * n * sizeof(float)));
+    float *din = c->tmp_fb, *dout = c->tmp_fb + n;
+    HIP_TRY(hipMemcpyAsync(din, planes, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (int rc = bdpt_strategies_sheet(c, din, n_s, n_t, width, height, gains, dout, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+int bdpt_render_strategies_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_s,
+                                int32_t n_t, int32_t weighting, float* fb_planes_host) {
+    return render_bdpt_host(c, p, w, fb_planes_host, strategy_planes(n_s, n_t, weighting));
 }
 
 int bdpt_render_light_groups_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,

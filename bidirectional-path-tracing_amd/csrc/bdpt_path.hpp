@@ -80,27 +80,53 @@ __device__ __forceinline__ float rr_probability(const DevFrame& fr, int depth, f
 // the length of the light walk (isPathPureSpecular belongs to the eye walk, whose prologue
 // sets it); every stored light vertex carries it in its rr word (BDPT_LV_TAG) to the eye
 // walk's connections. Every line of this compiles out with BDPT_GROUPS 0.
+//
+// Strategy images (BDPT_STRATS 1: bdpt_kernels_strat.hip): the same planes and
+// the same travelling index, filed by the sampling strategy (s, t) that formed the contribution:
+// s light-subpath vertices, t eye-subpath vertices with the camera counted, k = s + t - 1. The
+// framebuffer is n_s * n_t planes (DevFrame::strat_shape) and the plane is
+// min(s, n_s - 1) * n_t + min(t, n_t) - 1. Each site names its s next to its k (t = k + 1 - s):
+//   eye walk hits an emitter           s = 0                (t = depth_eye + 1)
+//   connectToLight                     s = 1                (t = depth_eye + 1)
+//   connectVertices                    s = depth_light + 1  (t = depth_eye + 1)
+//   connectToCamera                    s = depth_light + 1  (t = 1)
+// with a stored vertex's depth_light from its rr word, as for the layers. BDPT_UNWEIGHTED 1
+// (bdpt_kernels_strat_unweighted.hip) is the same build with no contribution multiplied by its
+// misWeight (bdpt.h:98, :356, :427, :482): each plane is then its strategy's plain estimator.
+// Every line of this compiles out with BDPT_STRATS 0.
 #ifndef BDPT_LAYERS
 #define BDPT_LAYERS 0
 #endif
 #ifndef BDPT_GROUPS
 #define BDPT_GROUPS 0
 #endif
-#define BDPT_PLANES (BDPT_LAYERS || BDPT_GROUPS)  // the framebuffer is several planes; no per-sample sum
+#ifndef BDPT_STRATS
+#define BDPT_STRATS 0
+#endif
+#ifndef BDPT_UNWEIGHTED
+#define BDPT_UNWEIGHTED 0
+#endif
+#define BDPT_PLANES (BDPT_LAYERS || BDPT_GROUPS || BDPT_STRATS)  // the framebuffer is several planes; no per-sample sum
 #if BDPT_PLANES
-#if BDPT_RR || (defined(BDPT_SAMPLER_STATE) && BDPT_SAMPLER_STATE) || (BDPT_LAYERS && BDPT_GROUPS)
-#error "BDPT_LAYERS / BDPT_GROUPS: one of them, in the frame kernel without Russian roulette only"
+#if BDPT_RR || (defined(BDPT_SAMPLER_STATE) && BDPT_SAMPLER_STATE) || (BDPT_LAYERS + BDPT_GROUPS + BDPT_STRATS != 1)
+#error "BDPT_LAYERS / BDPT_GROUPS / BDPT_STRATS: one of them, in the frame kernel without Russian roulette only"
 #endif
 #endif
-// BDPT_PLANE_PX(fr, k, g, pixel): the index a contribution of a k-edge path lit by group g is
-// added at (each build reads the one it files by; the plain builds neither).
+#if BDPT_UNWEIGHTED && !BDPT_STRATS
+#error "BDPT_UNWEIGHTED is a form of the strategy build (BDPT_STRATS)"
+#endif
+// A contribution's misWeight: the reference's, or (the unweighted strategy build) none.
+__device__ __forceinline__ float mis_factor(float mis) { return BDPT_UNWEIGHTED ? 1.f : mis; }
+// BDPT_PLANE_PX(fr, k, g, s, pixel): the index a contribution of a k-edge path lit by group g and
+// formed with s light-subpath vertices is added at (each build reads what it files by; the plain
+// builds nothing).
 // BDPT_LV_TAG(rr, depth, g): a stored light vertex's rr word.
 #if BDPT_LAYERS
 __device__ __forceinline__ int layer_index(const DevFrame& fr, int k, int pixel) {
     const int plane = max(0, min(k - 1, fr.n_layers - 1));
     return plane * (fr.W * fr.H) + pixel;  // < 2^30 (bdpt_render_layers checks n_layers * W * H)
 }
-#define BDPT_PLANE_PX(fr, k, g, pixel) layer_index(fr, k, pixel)
+#define BDPT_PLANE_PX(fr, k, g, s, pixel) layer_index(fr, k, pixel)
 #define BDPT_LV_TAG(rr, depth, g) __int_as_float(depth)
 #elif BDPT_GROUPS
 // emitter_group holds one entry in [0, n_groups) per emitter (bdpt_render_light_groups checks);
@@ -115,12 +141,21 @@ __device__ __forceinline__ int prim_emitter(const DevScene& sc, int tri) {
 __device__ __forceinline__ int group_index(const DevFrame& fr, int g, int pixel) {
     return g * (fr.W * fr.H) + pixel;  // < 2^30 (bdpt_render_light_groups checks n_groups * W * H)
 }
-#define BDPT_PLANE_PX(fr, k, g, pixel) group_index(fr, g, pixel)
+#define BDPT_PLANE_PX(fr, k, g, s, pixel) group_index(fr, g, pixel)
 #define BDPT_LV_TAG(rr, depth, g) __int_as_float(g)
 #define BDPT_GROUP_OF(fr, e) group_of_emitter(fr, e)
 #define BDPT_LIGHT_GROUP(L) static_cast<int>((L).c.pure)  // the light subpath's group, during its walk
+#elif BDPT_STRATS
+// strat_shape = n_s << 8 | n_t (bdpt_render_strategies checks n_s <= 29, n_t <= 28); s >= 0, t >= 1
+__device__ __forceinline__ int strat_index(const DevFrame& fr, int s, int t, int pixel) {
+    const int n_s = fr.strat_shape >> 8, n_t = fr.strat_shape & 0xff;
+    const int plane = min(s, n_s - 1) * n_t + (max(1, min(t, n_t)) - 1);
+    return plane * (fr.W * fr.H) + pixel;  // < 2^30 (bdpt_render_strategies checks n_s * n_t * W * H)
+}
+#define BDPT_PLANE_PX(fr, k, g, s, pixel) strat_index(fr, s, (k) + 1 - (s), pixel)
+#define BDPT_LV_TAG(rr, depth, g) __int_as_float(depth)
 #else
-#define BDPT_PLANE_PX(fr, k, g, pixel) (pixel)
+#define BDPT_PLANE_PX(fr, k, g, s, pixel) (pixel)
 #define BDPT_LV_TAG(rr, depth, g) (rr)
 #endif
 
@@ -480,7 +515,7 @@ __device__ __forceinline__ bool task_push(const LaneCold&, const DevFrame&, f3, 
 constexpr bool kTasks = BDPT_HELP && !BDPT_SAMPLER_STATE;
 
 // An eye-estimate addition for the pixel: the wave's slot when it holds the pixel, else the framebuffer.
-// BDPT_PLANES: `pixel` is a plane index (layer_index / group_index). A plane-0 index equals the plain pixel
+// BDPT_PLANES: `pixel` is a plane index (layer_index / group_index / strat_index). A plane-0 index equals the plain pixel
 // and uses the slot as before (the slot's flush, eye_slot_reset, writes plane 0); an index of
 // another plane matches no slot (slots hold pixels < W * H) and goes to the framebuffer.
 __device__ __forceinline__ void eye_add(float* __restrict__ fb, int pixel, f3 add) {
@@ -643,8 +678,8 @@ __device__ __forceinline__ bool vertex_nocull(const Lane& L, f3 d);
         const float prevRev = ep.rev * (rr_on(fr) ? L.c.rr : 1.f);  /* swapped (wi, wo) * lightVertex.rr (bdpt.h:342) */ \
         const float lightWeight = div_w(reversePdf_a, nlight) * (L.c.vcm + prevRev * L.c.vc); \
         const float mis = rcp_w(lightWeight + 1.f + 0.f); \
-        const f3 pend_ = (fr.strategy == 0) ? rad * mis : rad; \
-        const int px_ = BDPT_PLANE_PX(fr, L.c.depth + 1, BDPT_LIGHT_GROUP(L), yp * fr.W + xp);  /* t = 1: k = depth_light + 1 */ \
+        const f3 pend_ = (fr.strategy == 0) ? rad * mis_factor(mis) : rad; \
+        const int px_ = BDPT_PLANE_PX(fr, L.c.depth + 1, BDPT_LIGHT_GROUP(L), L.c.depth + 1, yp * fr.W + xp);  /* t = 1: k = depth_light + 1 = s */ \
         /* a helper walks it and forms its ray from the camera and L.h.p (act: A_LIGHT_CONTINUE) */ \
         if (kTasks && task_push(L.c, fr, cam_o, L.h.p, false, pend_, px_, true, cnt)) break; \
         L.c.pend = pend_; \
@@ -722,7 +757,7 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
             const int mat = __float_as_int(gld4(sc.shade + kShadeStride * static_cast<size_t>(L.c.prim_tri)).w);
             L.c.Li = ld3(bsdf_of(sc, mat).emission);
 #if BDPT_PLANES  // the camera ray's own emitter hit: k = 1, lit by the emitter of the hit shape
-            layer_add(fr, fb, BDPT_PLANE_PX(fr, 1, BDPT_GROUP_OF(fr, prim_emitter(sc, L.c.prim_tri)), L.c.pixel), L.c.Li);
+            layer_add(fr, fb, BDPT_PLANE_PX(fr, 1, BDPT_GROUP_OF(fr, prim_emitter(sc, L.c.prim_tri)), 0, L.c.pixel), L.c.Li);
 #endif
             act = A_FINISH;
             break;
@@ -771,7 +806,7 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
                     if (fr.strategy == 2) {  // PATH_TRACING (bdpt.h:110-113)
                         if (L.c.pure) L.c.Li = L.c.Li + contrib;
                     } else {
-                        if (!L.c.pure) contrib = contrib * mis;
+                        if (!L.c.pure) contrib = contrib * mis_factor(mis);
                         L.c.Li = L.c.Li + contrib;
                     }
                 } else if (L.c.depth == 1) {
@@ -779,7 +814,7 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
                 }
             }
 #if BDPT_PLANES  // s = 0: k = depth_eye, lit by the emitter hit
-            layer_add(fr, fb, BDPT_PLANE_PX(fr, L.c.depth, BDPT_GROUP_OF(fr, eid), L.c.pixel), L.c.Li);
+            layer_add(fr, fb, BDPT_PLANE_PX(fr, L.c.depth, BDPT_GROUP_OF(fr, eid), 0, L.c.pixel), L.c.Li);
 #endif
             act = A_FINISH;
             break;
@@ -854,9 +889,9 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
         const float eyeCurRev_a = cosAtEye * rcp_w(d2) * kInvTwoPi;
         const float eyeWeight = eyeCurRev_a * (L.c.vcm + eyePrevRev * L.c.vc);
         const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
-        const f3 pend = (fr.strategy == 0) ? Li * mis : Li;
+        const f3 pend = (fr.strategy == 0) ? Li * mis_factor(mis) : Li;
         const Ray sr = shadow_ray(L.h.p, e_p);
-        const int px = BDPT_PLANE_PX(fr, L.c.depth + 1, BDPT_GROUP_OF(fr, e_id), L.c.pixel);  // s = 1: k = depth_eye + 1
+        const int px = BDPT_PLANE_PX(fr, L.c.depth + 1, BDPT_GROUP_OF(fr, e_id), 1, L.c.pixel);  // s = 1: k = depth_eye + 1
         if (kTasks && task_push(L.c, fr, L.h.p, e_p, vertex_nocull(L, sr.d), pend * fr.inv_spp, px, false, cnt))
             break;  // a helper walks it (act: A_CONN)
 #if BDPT_PLANES
@@ -906,16 +941,16 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
             const float eyeWeight = eyePathRev_a * (L.c.vcm + eyePrevRev * L.c.vc);
             const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
             const Ray sr = shadow_ray(L.h.p, V.p);
-            // s >= 2, t >= 2: k = depth_eye + depth_light + 1 (the stored vertex's depth or group: BDPT_LV_TAG)
-            const int px = BDPT_PLANE_PX(fr, L.c.depth + __float_as_int(V.rr) + 1, __float_as_int(V.rr), L.c.pixel);
-            if (kTasks && task_push(L.c, fr, L.h.p, V.p, vertex_nocull(L, sr.d), (Li * mis) * fr.inv_spp, px, false, cnt)) {
+            // s >= 2, t >= 2: k = depth_eye + depth_light + 1, s = depth_light + 1 (the stored vertex's depth or group: BDPT_LV_TAG)
+            const int px = BDPT_PLANE_PX(fr, L.c.depth + __float_as_int(V.rr) + 1, __float_as_int(V.rr), __float_as_int(V.rr) + 1, L.c.pixel);
+            if (kTasks && task_push(L.c, fr, L.h.p, V.p, vertex_nocull(L, sr.d), (Li * mis_factor(mis)) * fr.inv_spp, px, false, cnt)) {
                 L.c.ci++;  // a helper walks it; the next light vertex now
                 continue;
             }
 #if BDPT_PLANES
             L.c.pend_px = px;  // the ring is full: the owner traces it, resolve() adds it to this plane
 #endif
-            L.c.pend = Li * mis;
+            L.c.pend = Li * mis_factor(mis);
             L.ray = sr;
             L.state = ST_CONN;
             act = A_ISSUED;
@@ -1020,8 +1055,8 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
         const float eyeWeight = eyePathRev_a * (oc.vcm + eyePrevRev * oc.vc);
         const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
         const Ray sr = shadow_ray(hp, V.p);
-        task_push(L.c, fr, hp, V.p, graze_exempt(sr.d, hn, hshape), (Li * mis) * fr.inv_spp,
-                  BDPT_PLANE_PX(fr, oc.depth + __float_as_int(V.rr) + 1, __float_as_int(V.rr), oc.pixel), false, cnt);
+        task_push(L.c, fr, hp, V.p, graze_exempt(sr.d, hn, hshape), (Li * mis_factor(mis)) * fr.inv_spp,
+                  BDPT_PLANE_PX(fr, oc.depth + __float_as_int(V.rr) + 1, __float_as_int(V.rr), __float_as_int(V.rr) + 1, oc.pixel), false, cnt);
     }
     if (k > 0) L.c.ci = L.c.nl;
 }

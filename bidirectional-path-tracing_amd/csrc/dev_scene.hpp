@@ -220,7 +220,12 @@ struct DevFrame {
     // path-length layers (bdpt_render_layers, the bdpt_kernels_layers.hip build): the framebuffer
     // is n_layers consecutive W x H x 3 planes and a contribution of a path with k edges goes to
     // plane min(k - 1, n_layers - 1). 0 and unread in every other build.
-    int32_t n_layers;
+    // Strategy images (bdpt_render_strategies, the bdpt_kernels_strat*.hip builds) keep their
+    // shape in the same word: strat_shape = n_s << 8 | n_t, the framebuffer n_s * n_t planes.
+    union {
+        int32_t n_layers;
+        int32_t strat_shape;
+    };
 };
 enum : uint32_t { kParkOn = 1u, kParkResume = 2u };
 // kSchedLeafRecheck (BDPT_LEAF_DEFER builds, a debugging knob): the deferred reference-leaf

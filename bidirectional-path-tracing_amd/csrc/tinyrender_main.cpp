@@ -31,6 +31,13 @@
 // that end on emitter e of bdpt_scene_get_emitter; a second render, so the main EXR is the same
 // bytes with or without it). Refused for path / direct scenes before any device is used; with
 // several devices the first renders the groups.
+// --strategies[=unweighted] (a bdpt scene) also writes <out stem>.S<ss>T<tt>.exr for every plane of
+// the frame split by sampling strategy that is not all zero (bdpt_render_strategies_host at
+// bdpt_strategies_shape's shape: s light-subpath and t eye-subpath vertices; =unweighted: without the
+// MIS weights) and <out stem>.strategies.exr, their contact sheet at gain 1 (bdpt_strategies_sheet).
+// A second render, so the main EXR is the same bytes with or without it. A bad value, a path / direct
+// scene or an rr_depth outside 1..28 is refused before any device is used; with several devices the
+// first renders the planes.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -85,7 +92,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Syntax: %s <scene.toml> [nogui] [--width W --height H --spp N --rr D --device K "
                              "--out FILE.exr --seed S --gpus N --devices a,b,... --shard samples|rows "
-                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups]\n", argv[0]);
+                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted]]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string toml = argv[1];
@@ -100,6 +107,7 @@ int main(int argc, char** argv) {
     int denoise_iterations = BDPT_DENOISE_ITERATIONS;
     int layers = 0;  // --layers N (0: none)
     bool light_groups = false;  // --light-groups
+    int strategies = -1;        // --strategies[=unweighted]: BDPT_STRATEGIES_* (-1: none)
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -163,6 +171,13 @@ int main(int argc, char** argv) {
             layers = static_cast<int>(n);
         } else if (a == "--light-groups") {
             light_groups = true;
+        } else if (a == "--strategies" || a == "--strategies=weighted") {
+            strategies = BDPT_STRATEGIES_WEIGHTED;
+        } else if (a == "--strategies=unweighted") {
+            strategies = BDPT_STRATEGIES_UNWEIGHTED;
+        } else if (a.rfind("--strategies", 0) == 0) {
+            std::fprintf(stderr, "%s: --strategies takes no value, =weighted or =unweighted\n", a.c_str());
+            return EXIT_FAILURE;
         } else if (a == "--gpus") {
             const int n = std::atoi(next("--gpus"));
             devices.clear();
@@ -218,10 +233,18 @@ int main(int argc, char** argv) {
                      cfg.integrator);
         return EXIT_FAILURE;
     }
+    if (strategies >= 0 && (path || direct)) {
+        std::fprintf(stderr, "--strategies splits a bdpt frame (integrator type \"%s\" has no (s, t) strategies)\n",
+                     cfg.integrator);
+        return EXIT_FAILURE;
+    }
     if (W > 0) cfg.width = W;
     if (H > 0) cfg.height = H;
     if (spp > 0) cfg.spp = spp;
     if (rr > 0) cfg.rr_depth = rr;
+    int32_t n_s = 0, n_t = 0;  // --strategies: the shape that clamps nothing
+    if (strategies >= 0 && bdpt_strategies_shape(cfg.rr_depth, BDPT_STRATEGY_BDPT, &n_s, &n_t) != BDPT_OK)
+        return die("--strategies");
     if (windowed && window.count > 0 &&
         static_cast<long long>(window.first) + static_cast<long long>(window.count - 1) * window.stride >= cfg.spp) {
         std::fprintf(stderr, "--sample-window %d:%d:%d: count reaches past spp = %d\n", window.first, window.stride,
@@ -360,6 +383,33 @@ int main(int argc, char** argv) {
             std::printf("Saved EXR image to %s\n", side.c_str());
         }
         if (gctx != ctx) bdpt_ctx_destroy(gctx);
+    }
+    if (strategies >= 0) {
+        bdpt_ctx* sctx = ctx;  // several devices: the first renders the planes
+        if (!sctx && bdpt_ctx_create(scene, devices[0], &sctx) != BDPT_OK) return die("bdpt_ctx_create (strategies)");
+        const size_t plane = static_cast<size_t>(cfg.width) * cfg.height * 3, n = static_cast<size_t>(n_s) * n_t;
+        std::vector<float> planes(plane * n, 0.f);
+        if (bdpt_render_strategies_host(sctx, &p, win, n_s, n_t, strategies, planes.data()) != BDPT_OK)
+            return die("bdpt_render_strategies_host");
+        for (int s = 0; s < n_s; s++)
+            for (int t = 1; t <= n_t; t++) {
+                const float* const px = planes.data() + plane * (static_cast<size_t>(s) * n_t + (t - 1));
+                bool any = false;
+                for (size_t i = 0; i < plane && !any; i++) any = px[i] != 0.f;
+                if (!any) continue;
+                char suffix[24];
+                std::snprintf(suffix, sizeof suffix, ".S%02dT%02d", s, t);
+                const std::string side = side_path(exr, suffix);
+                if (bdpt_save_exr(px, cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
+                std::printf("Saved EXR image to %s\n", side.c_str());
+            }
+        std::vector<float> sheet(plane * n);
+        if (bdpt_strategies_sheet_host(sctx, planes.data(), n_s, n_t, cfg.width, cfg.height, nullptr, sheet.data()) != BDPT_OK)
+            return die("bdpt_strategies_sheet_host");
+        const std::string side = side_path(exr, ".strategies");
+        if (bdpt_save_exr(sheet.data(), n_s * cfg.width, n_t * cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
+        std::printf("Saved EXR image to %s\n", side.c_str());
+        if (sctx != ctx) bdpt_ctx_destroy(sctx);
     }
     if (multi) bdpt_multi_destroy(multi);
     if (ctx) bdpt_ctx_destroy(ctx);

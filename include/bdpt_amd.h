@@ -581,6 +581,50 @@ int bdpt_render_light_groups_host(bdpt_ctx* ctx, const bdpt_frame_params* params
 int bdpt_light_groups_relight(bdpt_ctx* ctx, const float* fb_groups_device, int32_t n_groups, int32_t width,
                               int32_t height, const float* gains, float* out_device, void* hip_stream);
 
+/* ---- strategy images: one BDPT frame split by sampling strategy (s, t), weighted or not ---- */
+/* (new) Not in the reference. Every contribution the BDPT frame kernel forms joins a light subpath of
+ * s vertices to an eye subpath of t vertices, the camera counted (k = s + t - 1 edges): the eye walk
+ * hits an emitter (s = 0, t = depth_eye + 1; light tracing's primary emission is (0, 2)),
+ * connectToLight (s = 1, t = depth_eye + 1), connectVertices (s = depth_light + 1, t = depth_eye + 1),
+ * connectToCamera (s = depth_light + 1, t = 1); both walks start at depth 1. bdpt_render_strategies
+ * renders what bdpt_render_window (path = direct = NULL) renders - the same paths and draws - but ADDS
+ * each contribution to plane min(s, n_s - 1) * n_t + min(t, n_t) - 1 of fb_planes, n_s * n_t
+ * consecutive width * height * 3 planes: the last row and column collect what is longer. Planes (0, 1)
+ * and (1, 1) are always empty. bdpt_strategies_shape gives the shape that holds every strategy of an
+ * rr_depth without clamping, n_s = max(rr_depth, 1) + 1 and n_t = max(rr_depth, 2) (one shape for the
+ * three BDPT_STRATEGY_* values; it needs no context; rr_depth in 1..28).
+ * weighting BDPT_STRATEGIES_WEIGHTED: the contributions have bdpt_render's values and the planes sum to
+ * its frame (up to the order of the float additions; at shape (1, 1) the plane is the frame).
+ * BDPT_STRATEGIES_UNWEIGHTED: no contribution is multiplied by its misWeight (bdpt.h:98, :356, :427,
+ * :482), all else the same, so plane (s, t) is that strategy's plain estimator; the t = 1 planes plus
+ * plane (0, 2) then sum to the frame of the reference's LIGHT_TRACING build. Under
+ * BDPT_STRATEGY_LIGHT_TRACING / PATH_TRACING the reference weights nothing and both settings agree.
+ * window NULL = the whole frame; row shards and bdpt_set_row_order work as in bdpt_render.
+ * BDPT_ERR_INVALID (the message names the field): n_s outside 1..29, n_t outside 1..28, a weighting
+ * other than the two, n_s * n_t * width * height >= 2^30. BDPT_ERR_UNSUPPORTED (the message says
+ * "strategies"), before any launch: flags != 0, Russian roulette, rr_depth > 28, a scene with bitmap
+ * textures, BSDF records in HBM. bdpt_last_kernel afterwards: "bdpt_frame_kernel_strat" or
+ * "bdpt_frame_kernel_strat_unweighted". Asynchronous on `hip_stream` like bdpt_render; the host form
+ * stages the caller's n_s * n_t * width * height * 3 floats and is synchronous. */
+#define BDPT_STRATEGIES_WEIGHTED 0
+#define BDPT_STRATEGIES_UNWEIGHTED 1
+int bdpt_render_strategies(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                           int32_t n_s, int32_t n_t, int32_t weighting, float* fb_planes_device, void* hip_stream);
+int bdpt_render_strategies_host(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                                int32_t n_s, int32_t n_t, int32_t weighting, float* fb_planes_host);
+int bdpt_strategies_shape(int32_t rr_depth, int32_t strategy, int32_t* n_s, int32_t* n_t);
+/* (new) The contact sheet of the planes: out is one image of n_s * width by n_t * height pixels (x 3
+ * floats, rows of n_s * width pixels), the tile of (s, t) at tile column s and tile row t - 1, each
+ * float multiplied by gains[s * n_t + t - 1][channel] (one float32 product; gains NULL: copied). No
+ * atomics: the bits of that loop, the same every run. `gains` is a HOST array of n_s * n_t x 3 floats
+ * (copied before the call returns); planes and out are device pointers. BDPT_ERR_INVALID: n_s outside
+ * 1..29, n_t outside 1..28, a sheet of 2^31 floats or more, out overlapping the planes, a gain that is
+ * not finite. Asynchronous on `hip_stream`; the host form stages both arrays and is synchronous. */
+int bdpt_strategies_sheet(bdpt_ctx* ctx, const float* planes_device, int32_t n_s, int32_t n_t, int32_t width,
+                          int32_t height, const float* gains, float* out_device, void* hip_stream);
+int bdpt_strategies_sheet_host(bdpt_ctx* ctx, const float* planes_host, int32_t n_s, int32_t n_t, int32_t width,
+                               int32_t height, const float* gains, float* out_host);
+
 /* ---- several HIP devices in one process ---- */
 /* The reference fans the offline loop out over host threads (parallel_for,
  * src/core/parallelfor.h:25-65, renderer.cpp:157); here every device gets one
