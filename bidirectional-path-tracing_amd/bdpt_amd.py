@@ -35,6 +35,7 @@ is no CPU fallback (a missing library or device raises).
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import subprocess
 from dataclasses import dataclass, field
@@ -806,6 +807,8 @@ def layers_longest_path(rr_depth: int, strategy: int = STRATEGY_BDPT) -> int:
 
 STRATEGIES_WEIGHTED, STRATEGIES_UNWEIGHTED = 0, 1  # bdpt_render_strategies' weighting (BDPT_STRATEGIES_*)
 STRATEGIES_MAX_S, STRATEGIES_MAX_T = 29, 28
+LAYERS_MAX = GROUPS_MAX = 64  # bdpt_render_layers' / bdpt_render_light_groups' most planes
+PLANE_PIXELS_MAX = 1 << 30    # planes * W * H of every plane render stays below it
 
 
 def strategies_shape(rr_depth: int, strategy: int = STRATEGY_BDPT) -> tuple:
@@ -1124,30 +1127,38 @@ class BDPTIntegrator:
         _check(lib().bdpt_render_aov(self._h, ctypes.byref(p), w and ctypes.byref(w), ctypes.c_void_p(aov_ptr),
                                      ctypes.c_void_p(stream_ptr)))
 
+    def _render_planes(self, entry, args, planes, ok, window, row_offset, row_stride, flags, fb_ptr=None, stream_ptr=0):
+        """One plane render (layers, light groups, strategies): entry(ctx, params, window, *args, fb[, stream]).
+        planes None: the device entry, ADDED to fb_ptr. Otherwise the host entry into a new planes + (H, W, 3)
+        array, which is returned; a count the library refuses (ok false) or a size it refuses, both before it
+        touches the buffer, is not allocated here."""
+        H, W = self.config.height, self.config.width
+        p = self.params(row_offset, row_stride, flags)
+        w = window.c() if window is not None else None
+        if planes is None:
+            _check(entry(self._h, ctypes.byref(p), w and ctypes.byref(w), *args, ctypes.c_void_p(fb_ptr),
+                         ctypes.c_void_p(stream_ptr)))
+            return None
+        ok = ok and math.prod(planes) * W * H < PLANE_PIXELS_MAX
+        out = np.zeros(tuple(planes) + (H, W, 3) if ok else (1,), np.float32)
+        _check(entry(self._h, ctypes.byref(p), w and ctypes.byref(w), *args, out.ctypes.data))
+        return out
+
     def render_layers(self, n_layers: int, window: SampleWindow | None = None, row_offset: int = 0,
                       row_stride: int = 1, flags: int = 0) -> np.ndarray:
         """bdpt_render_layers_host: the BDPT frame split by path length, a new (n_layers, H, W, 3)
         array. Layer l holds the contributions of paths camera -> ... -> emitter with l + 1 edges
         (0: emitters seen directly, 1: direct light, ...), the last layer everything longer; the
         layers sum to render_frame()'s frame."""
-        H, W = self.config.height, self.config.width
-        p = self.params(row_offset, row_stride, flags)
-        w = window.c() if window is not None else None
         n_layers = int(n_layers)
-        # a count or size the library refuses (before it touches the buffer) is not allocated here
-        ok = 1 <= n_layers <= 64 and n_layers * W * H < 1 << 30
-        out = np.zeros((n_layers, H, W, 3) if ok else (1,), np.float32)
-        _check(lib().bdpt_render_layers_host(self._h, ctypes.byref(p), w and ctypes.byref(w), n_layers,
-                                             out.ctypes.data))
-        return out
+        return self._render_planes(lib().bdpt_render_layers_host, (n_layers,), (n_layers,), 1 <= n_layers <= LAYERS_MAX,
+                                   window, row_offset, row_stride, flags)
 
     def render_layers_device(self, n_layers: int, fb_ptr: int, stream_ptr: int = 0,
                              window: SampleWindow | None = None, row_offset: int = 0, row_stride: int = 1) -> None:
         """bdpt_render_layers: asynchronous, ADDED to a device buffer of n_layers * H * W * 3 floats."""
-        p = self.params(row_offset, row_stride, 0)
-        w = window.c() if window is not None else None
-        _check(lib().bdpt_render_layers(self._h, ctypes.byref(p), w and ctypes.byref(w), int(n_layers),
-                                        ctypes.c_void_p(fb_ptr), ctypes.c_void_p(stream_ptr)))
+        self._render_planes(lib().bdpt_render_layers, (int(n_layers),), None, True, window, row_offset, row_stride, 0,
+                            fb_ptr, stream_ptr)
 
     @staticmethod
     def layer_mask(mask_or_iterable) -> int:
@@ -1164,25 +1175,38 @@ class BDPTIntegrator:
             m |= 1 << int(l)
         return m
 
+    def _combine(self, a, out_shape, call) -> np.ndarray:
+        """The round trip of compose_layers, relight and strategies_sheet: the contiguous float32 planes go to
+        the device, call(planes pointer, out pointer) runs the device form on them, the result comes back."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+        d_out = torch.zeros(out_shape, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        call(d_in.data_ptr(), d_out.data_ptr())
+        self.synchronize()
+        return d_out.cpu().numpy()
+
+    @staticmethod
+    def _gains(entry, gains, planes, shape):
+        """Host gains as a combine entry takes them: contiguous float32, 3 per plane (shape: how the message says it)."""
+        g = np.ascontiguousarray(gains, np.float32)
+        if g.size != 3 * planes:
+            raise BdptError(f"{entry}: gains must hold {shape} x 3 floats, got {g.size}")
+        return g
+
     def compose_layers(self, layers, mask_or_iterable) -> np.ndarray:
         """bdpt_layers_compose on the device: the (H, W, 3) float32 sum of the layers the mask
         names (an int bit mask or an iterable of layer indices), added in ascending layer order.
         The layers go to the device and the sum comes back (a viewer that keeps the planes on
         the device calls compose_layers_device)."""
-        import torch
-
         a = np.ascontiguousarray(layers, np.float32)
         if a.ndim != 4 or a.shape[3] != 3:
             raise BdptError(f"compose_layers: layers must be (n_layers, H, W, 3), got {a.shape}")
         n, H, W = a.shape[:3]
         mask = self.layer_mask(mask_or_iterable)
-        dev = torch.device("cuda", self.device)
-        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-        d_out = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-        self.compose_layers_device(d_in.data_ptr(), n, W, H, mask, d_out.data_ptr())
-        self.synchronize()
-        return d_out.cpu().numpy()
+        return self._combine(a, (H, W, 3), lambda d_in, d_out: self.compose_layers_device(d_in, n, W, H, mask, d_out))
 
     def compose_layers_device(self, layers_ptr: int, n_layers: int, width: int, height: int, mask: int, out_ptr: int,
                               stream_ptr: int = 0) -> None:
@@ -1210,35 +1234,23 @@ class BDPTIntegrator:
         array. Plane g holds the contributions of the paths that end on an emitter e with
         group_of_emitter[e] == g (Scene.emitters() order; None: one plane per emitter); the planes
         sum to render_frame()'s frame, and relight() recombines them under other emitter colours."""
-        H, W = self.config.height, self.config.width
-        p = self.params(row_offset, row_stride, flags)
-        w = window.c() if window is not None else None
         m, n = self._group_map(group_of_emitter, n_groups)
-        # a count or size the library refuses (before it touches the buffer) is not allocated here
-        ok = 1 <= n <= 64 and n * W * H < 1 << 30
-        out = np.zeros((n, H, W, 3) if ok else (1,), np.float32)
-        _check(lib().bdpt_render_light_groups_host(self._h, ctypes.byref(p), w and ctypes.byref(w), n,
-                                                   None if m is None else m.ctypes.data, out.ctypes.data))
-        return out
+        return self._render_planes(lib().bdpt_render_light_groups_host, (n, None if m is None else m.ctypes.data), (n,),
+                                   1 <= n <= GROUPS_MAX, window, row_offset, row_stride, flags)
 
     def render_light_groups_device(self, fb_ptr: int, group_of_emitter=None, n_groups: int | None = None,
                                    stream_ptr: int = 0, window: SampleWindow | None = None, row_offset: int = 0,
                                    row_stride: int = 1) -> None:
         """bdpt_render_light_groups: asynchronous, ADDED to a device buffer of n_groups * H * W * 3 floats."""
-        p = self.params(row_offset, row_stride, 0)
-        w = window.c() if window is not None else None
         m, n = self._group_map(group_of_emitter, n_groups)
-        _check(lib().bdpt_render_light_groups(self._h, ctypes.byref(p), w and ctypes.byref(w), n,
-                                              None if m is None else m.ctypes.data, ctypes.c_void_p(fb_ptr),
-                                              ctypes.c_void_p(stream_ptr)))
+        self._render_planes(lib().bdpt_render_light_groups, (n, None if m is None else m.ctypes.data), None, True, window,
+                            row_offset, row_stride, 0, fb_ptr, stream_ptr)
 
     def relight(self, groups, gains) -> np.ndarray:
         """bdpt_light_groups_relight on the device: the (H, W, 3) float32 frame sum_g gains[g] *
         groups[g] (gains: (n_groups, 3) RGB, or (n_groups,) for grey gains), each product and sum
         rounded in float32 in ascending group order. The planes go to the device and the frame
         comes back (a viewer that keeps the planes on the device calls relight_device)."""
-        import torch
-
         a = np.ascontiguousarray(groups, np.float32)
         if a.ndim != 4 or a.shape[3] != 3:
             raise BdptError(f"relight: groups must be (n_groups, H, W, 3), got {a.shape}")
@@ -1248,20 +1260,12 @@ class BDPTIntegrator:
             g = np.repeat(g[:, None], 3, axis=1)
         if g.shape != (n, 3):
             raise BdptError(f"relight: gains must be ({n}, 3) or ({n},), got {g.shape}")
-        dev = torch.device("cuda", self.device)
-        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-        d_out = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-        self.relight_device(d_in.data_ptr(), n, W, H, g, d_out.data_ptr())
-        self.synchronize()
-        return d_out.cpu().numpy()
+        return self._combine(a, (H, W, 3), lambda d_in, d_out: self.relight_device(d_in, n, W, H, g, d_out))
 
     def relight_device(self, groups_ptr: int, n_groups: int, width: int, height: int, gains, out_ptr: int,
                        stream_ptr: int = 0) -> None:
         """bdpt_light_groups_relight: asynchronous, on device buffers; gains: host (n_groups, 3) float32."""
-        g = np.ascontiguousarray(gains, np.float32)
-        if g.size != 3 * int(n_groups):
-            raise BdptError(f"relight_device: gains must hold {n_groups} x 3 floats, got {g.size}")
+        g = self._gains("relight_device", gains, int(n_groups), n_groups)
         _check(lib().bdpt_light_groups_relight(self._h, ctypes.c_void_p(groups_ptr), int(n_groups), int(width),
                                                int(height), g.ctypes.data, ctypes.c_void_p(out_ptr),
                                                ctypes.c_void_p(stream_ptr)))
@@ -1281,52 +1285,33 @@ class BDPTIntegrator:
         the default shape, strategies_shape(rr_depth, strategy), clamps nothing. Weighted, the planes
         sum to render_frame()'s frame; unweighted, no contribution carries its MIS weight and each
         plane is its strategy's plain estimator. `unweighted` may also be a STRATEGIES_* value."""
-        H, W = self.config.height, self.config.width
-        p = self.params(row_offset, row_stride, flags)
-        w = window.c() if window is not None else None
         n_s, n_t = self._strategies_shape(n_s, n_t)
-        # a shape or size the library refuses (before it touches the buffer) is not allocated here
-        ok = 1 <= n_s <= STRATEGIES_MAX_S and 1 <= n_t <= STRATEGIES_MAX_T and n_s * n_t * W * H < 1 << 30
-        out = np.zeros((n_s, n_t, H, W, 3) if ok else (1,), np.float32)
-        _check(lib().bdpt_render_strategies_host(self._h, ctypes.byref(p), w and ctypes.byref(w), n_s, n_t,
-                                                 int(unweighted), out.ctypes.data))
-        return out
+        return self._render_planes(lib().bdpt_render_strategies_host, (n_s, n_t, int(unweighted)), (n_s, n_t),
+                                   1 <= n_s <= STRATEGIES_MAX_S and 1 <= n_t <= STRATEGIES_MAX_T, window, row_offset,
+                                   row_stride, flags)
 
     def render_strategies_device(self, fb_ptr: int, n_s: int | None = None, n_t: int | None = None,
                                  unweighted: bool = False, stream_ptr: int = 0, window: SampleWindow | None = None,
                                  row_offset: int = 0, row_stride: int = 1) -> None:
         """bdpt_render_strategies: asynchronous, ADDED to a device buffer of n_s * n_t * H * W * 3 floats."""
-        p = self.params(row_offset, row_stride, 0)
-        w = window.c() if window is not None else None
         n_s, n_t = self._strategies_shape(n_s, n_t)
-        _check(lib().bdpt_render_strategies(self._h, ctypes.byref(p), w and ctypes.byref(w), n_s, n_t,
-                                            int(unweighted), ctypes.c_void_p(fb_ptr), ctypes.c_void_p(stream_ptr)))
+        self._render_planes(lib().bdpt_render_strategies, (n_s, n_t, int(unweighted)), None, True, window, row_offset,
+                            row_stride, 0, fb_ptr, stream_ptr)
 
     def strategies_sheet(self, planes, gains=None) -> np.ndarray:
         """bdpt_strategies_sheet on the device: the contact sheet of render_strategies' planes, an
         (n_t * H, n_s * W, 3) float32 image with the tile of (s, t) at tile column s, tile row t - 1,
         each tile times its gain (gains: (n_s, n_t, 3) RGB or (n_s, n_t) grey; None: copied). The
         bits of strategies_sheet_numpy. The planes go to the device and the sheet comes back."""
-        import torch
-
         a, g = _sheet_args(planes, gains)
         n_s, n_t, H, W = a.shape[:4]
-        dev = torch.device("cuda", self.device)
-        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-        d_out = torch.zeros((n_t * H, n_s * W, 3), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-        self.strategies_sheet_device(d_in.data_ptr(), n_s, n_t, W, H, g, d_out.data_ptr())
-        self.synchronize()
-        return d_out.cpu().numpy()
+        return self._combine(a, (n_t * H, n_s * W, 3),
+                             lambda d_in, d_out: self.strategies_sheet_device(d_in, n_s, n_t, W, H, g, d_out))
 
     def strategies_sheet_device(self, planes_ptr: int, n_s: int, n_t: int, width: int, height: int, gains,
                                 out_ptr: int, stream_ptr: int = 0) -> None:
         """bdpt_strategies_sheet: asynchronous, on device buffers; gains: None or host n_s * n_t x 3 float32."""
-        g = None
-        if gains is not None:
-            g = np.ascontiguousarray(gains, np.float32)
-            if g.size != 3 * int(n_s) * int(n_t):
-                raise BdptError(f"strategies_sheet_device: gains must hold {n_s} x {n_t} x 3 floats, got {g.size}")
+        g = None if gains is None else self._gains("strategies_sheet_device", gains, int(n_s) * int(n_t), f"{n_s} x {n_t}")
         _check(lib().bdpt_strategies_sheet(self._h, ctypes.c_void_p(planes_ptr), int(n_s), int(n_t), int(width),
                                            int(height), None if g is None else g.ctypes.data,
                                            ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream_ptr)))

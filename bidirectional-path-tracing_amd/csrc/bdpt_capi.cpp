@@ -200,6 +200,16 @@ constexpr int kRrLightVerts = 255;
 // runs for millions of bounces (the oracle over a 512^2 x 256 frame: 2.7 M light /
 // 2.1 M eye bounces in one sample); the guard sits an order of magnitude above.
 constexpr int kRrDepthGuard = 1 << 25;
+// A frame kept as several planes (path-length layers, light groups, strategy images): the most
+// planes of each kind, and the limit they share. The messages take their figures from here.
+constexpr int kMaxLayers = 64;  // a layer mask is one 64-bit word (bdpt_layers_compose)
+constexpr int kMaxGroups = 64;  // the relight kernel's gains are a kernel argument (bdpt_light_groups_relight)
+constexpr int kMaxStratS = kLazyRrDepth + 1, kMaxStratT = kLazyRrDepth;  // every strategy of rr_depth 28
+// a contribution's plane and pixel travel as one index in the task record's 30-bit pixel field
+constexpr int kPlanePixelBits = 30;
+constexpr int64_t kMaxPlanePixels = int64_t{1} << kPlanePixelBits;
+const std::string kBelowPlanePixels = "below 2^" + std::to_string(kPlanePixelBits);
+std::string in_range(int max) { return " must be in [1, " + std::to_string(max) + "]"; }
 }  // namespace
 
 // Error reporting shared with the other C-ABI translation units (exr_io.cpp, toml_config.cpp).
@@ -377,6 +387,27 @@ static int stage_host(bdpt_ctx* c, float* host, size_t n, Run run) {
     HIP_TRY(hipMemcpyAsync(host, c->tmp_fb, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BDPT_OK;
+}
+
+// The device part of a combine entry (bdpt_layers_compose, bdpt_light_groups_relight,
+// bdpt_strategies_sheet) once its arguments are accepted: one launch on the call's stream, timed
+// as a call of its own. table (null: none): the sheet's ntable gains, which reach the device in
+// stream order from the context's own host copy; launch(device table or null, stream).
+template <class Launch>
+static int combine_planes(bdpt_ctx* c, void* hip_stream, const float* table, size_t ntable, Launch launch) {
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = begin_use(c, st)) return rc;
+    const float* dtable = nullptr;
+    if (table) {
+        c->sheet_gains_host.assign(table, table + ntable);
+        HIP_TRY(c->sheet_gains.reserve(sizeof(float) * 3 * kMaxStratS * kMaxStratT));  // (the largest table, once)
+        HIP_TRY(hipMemcpyAsync(c->sheet_gains, c->sheet_gains_host.data(), sizeof(float) * ntable, hipMemcpyHostToDevice, st));
+        dtable = c->sheet_gains;
+    }
+    if (int rc = begin_timed(c, st)) return rc;
+    HIP_TRY(launch(dtable, st));
+    return end_timed(c, st, 0, 1);
 }
 
 // The LDS tables with the emitter faces (5 float4 each) and CDFs appended to `base` words:
@@ -1088,61 +1119,86 @@ static const FrameBuild& pick_frame_build(const bdpt_ctx* c, const bdpt_frame_pa
     return frame_build;
 }
 
-// A frame kept as several planes: split by path length (bdpt_render_layers,
-// bdpt_kernels_layers.hip), by emitter group (bdpt_render_light_groups, bdpt_kernels_groups.hip) or by
-// sampling strategy (bdpt_render_strategies, bdpt_kernels_strat.hip / _strat_unweighted.hip).
-// kNone: the plain frame.
-constexpr int kMaxLayers = 64;  // a layer mask is one 64-bit word (bdpt_layers_compose)
-constexpr int kMaxGroups = 64;  // the relight kernel's gains are a kernel argument (bdpt_light_groups_relight)
-struct Planes {
-    enum Kind { kNone, kLayers, kGroups, kStrats } kind = kNone;
-    int n = 1;                               // planes in the framebuffer (kStrats: strategy_planes fills it in)
-    const int32_t* group_of_emitter = nullptr;  // kGroups: the caller's host map (null: identity)
-    int n_s = 0, n_t = 0, weighting = 0;     // kStrats: the shape (n = n_s * n_t) and BDPT_STRATEGIES_*
+// A frame kept as several W x H x 3 planes. One row per kind: what its
+// entry points are called in messages, what its plane count is called and how large it may be,
+// the phrase of "... are not built ..." and the frame-kernel builds that serve it. A new kind is a
+// row here, its BDPT_PLANE_PX case and kernel unit, and its entry pair.
+
+struct PlaneKind {
+    const char* entry;            // the render entry's name
+    const char* count;            // the plane count's name (a shape: the product's)
+    int max;                      // the most planes
+    const char* phrase;           // "<phrase> are not built <with what>"
+    const FrameBuild* build[2];   // the builds, by Planes::weighting (one build: twice)
+    bool shaped;                  // the count is an (n_s, n_t) shape with a weighting
+    bool mapped;                  // a map from emitters to planes comes with the call
 };
-constexpr int kMaxStratS = kLazyRrDepth + 1, kMaxStratT = kLazyRrDepth;  // every strategy of rr_depth 28
+static const PlaneKind kLayerPlanes = {"bdpt_render_layers", "n_layers", kMaxLayers, "path-length layers",
+                                       {&frame_build_layers, &frame_build_layers}, false, false};
+static const PlaneKind kGroupPlanes = {"bdpt_render_light_groups", "n_groups", kMaxGroups, "light groups",
+                                       {&frame_build_groups, &frame_build_groups}, false, true};
+static const PlaneKind kStrategyPlanes = {"bdpt_render_strategies", "n_s * n_t", kMaxStratS * kMaxStratT,
+                                          "strategies (per-(s, t) images)",
+                                          {&frame_build_strat, &frame_build_strat_unweighted}, true, false};
+
+static int check_strategy_shape(const std::string& entry, int32_t n_s, int32_t n_t) {
+    if (n_s < 1 || n_s > kMaxStratS) return fail(BDPT_ERR_INVALID, entry + "n_s" + in_range(kMaxStratS));
+    if (n_t < 1 || n_t > kMaxStratT) return fail(BDPT_ERR_INVALID, entry + "n_t" + in_range(kMaxStratT));
+    return BDPT_OK;
+}
+static bool strategy_shape_ok(int32_t n_s, int32_t n_t) {
+    return n_s >= 1 && n_s <= kMaxStratS && n_t >= 1 && n_t <= kMaxStratT;
+}
+
+// One call's planes: its kind (null: the plain frame) and what came with the call.
+struct Planes {
+    const PlaneKind* kind = nullptr;
+    int n = 1;                                  // planes in the framebuffer
+    const int32_t* group_of_emitter = nullptr;  // mapped kinds: the caller's host map (null: identity)
+    int n_s = 0, n_t = 0, weighting = 0;        // shaped kinds: n = n_s * n_t, BDPT_STRATEGIES_*
+
+    const FrameBuild& build() const { return *kind->build[weighting == BDPT_STRATEGIES_UNWEIGHTED]; }
+    // the kind's DevFrame words (emitter_group: the context's table, uploaded for this call)
+    void fill(dev::DevFrame& fr, const int32_t* emitter_group) const {
+        if (kind->shaped) fr.strat_shape = n_s << 8 | n_t;  // (shares n_layers' word)
+        else if (kind->mapped) fr.emitter_group = emitter_group;
+        else fr.n_layers = n;
+    }
+};
 static Planes strategy_planes(int32_t n_s, int32_t n_t, int32_t weighting) {
-    Planes pl;
-    pl.kind = Planes::kStrats;
+    Planes pl{&kStrategyPlanes};
     pl.n_s = n_s, pl.n_t = n_t, pl.weighting = weighting;
     // (a shape check_planes refuses keeps n = 1: nothing is sized by it)
-    if (n_s >= 1 && n_s <= kMaxStratS && n_t >= 1 && n_t <= kMaxStratT) pl.n = n_s * n_t;
+    if (strategy_shape_ok(n_s, n_t)) pl.n = n_s * n_t;
     return pl;
 }
 
-// What the plane builds serve, checked after check_params and before any launch; the
-// messages name the entry point and its count (n_layers / n_groups / n_s, n_t).
+// What the plane builds serve, checked after check_params and before any launch: the kind's
+// count or shape, the size, the map, then what no plane build runs.
 static int check_planes(const bdpt_ctx* c, const bdpt_frame_params* p, const Planes& pl) {
-    const bool groups = pl.kind == Planes::kGroups;
-    if (pl.kind == Planes::kStrats) {
-        const std::string entry = "bdpt_render_strategies: ";
-        if (pl.n_s < 1 || pl.n_s > kMaxStratS) return fail(BDPT_ERR_INVALID, entry + "n_s must be in [1, 29]");
-        if (pl.n_t < 1 || pl.n_t > kMaxStratT) return fail(BDPT_ERR_INVALID, entry + "n_t must be in [1, 28]");
+    const PlaneKind& k = *pl.kind;
+    const std::string entry = std::string(k.entry) + ": ";
+    if (k.shaped) {
+        if (int rc = check_strategy_shape(entry, pl.n_s, pl.n_t)) return rc;
         if (pl.weighting != BDPT_STRATEGIES_WEIGHTED && pl.weighting != BDPT_STRATEGIES_UNWEIGHTED)
             return fail(BDPT_ERR_INVALID, entry + "weighting must be BDPT_STRATEGIES_WEIGHTED (0) or "
                                                   "BDPT_STRATEGIES_UNWEIGHTED (1)");
-        if (static_cast<int64_t>(pl.n_s) * pl.n_t * p->width * p->height >= (int64_t{1} << 30))
-            return fail(BDPT_ERR_INVALID, entry + "n_s * n_t * W * H must be below 2^30 (the shadow-ray task record's "
-                                                  "pixel field)");
-    } else {
-    const std::string entry = groups ? "bdpt_render_light_groups" : "bdpt_render_layers";
-    const std::string count = groups ? "n_groups" : "n_layers";
-    if (pl.n < 1 || pl.n > (groups ? kMaxGroups : kMaxLayers))
-        return fail(BDPT_ERR_INVALID, entry + ": " + count + " must be in [1, 64]");
-    // a contribution's plane and pixel travel as one index in the task record's 30-bit pixel field
-    if (static_cast<int64_t>(pl.n) * p->width * p->height >= (int64_t{1} << 30))
-        return fail(BDPT_ERR_INVALID, entry + ": " + count + " * W * H must be below 2^30 (the shadow-ray task "
-                                      "record's pixel field)");
-    if (groups) {
+    } else if (pl.n < 1 || pl.n > k.max) {
+        return fail(BDPT_ERR_INVALID, entry + k.count + in_range(k.max));
+    }
+    if (static_cast<int64_t>(pl.n) * p->width * p->height >= kMaxPlanePixels)
+        return fail(BDPT_ERR_INVALID, entry + k.count + " * W * H must be " + kBelowPlanePixels +
+                                          " (the shadow-ray task record's pixel field)");
+    if (k.mapped) {
         const int nemit = c->sc.nemit;
         if (!pl.group_of_emitter && pl.n != nemit)
-            return fail(BDPT_ERR_INVALID, entry + ": a null group_of_emitter is the identity map and needs n_groups equal "
-                                          "to the emitter count (" + std::to_string(nemit) + "), got " + std::to_string(pl.n));
+            return fail(BDPT_ERR_INVALID, entry + "a null group_of_emitter is the identity map and needs " + k.count +
+                                              " equal to the emitter count (" + std::to_string(nemit) + "), got " +
+                                              std::to_string(pl.n));
         for (int e = 0; pl.group_of_emitter && e < nemit; e++)
             if (pl.group_of_emitter[e] < 0 || pl.group_of_emitter[e] >= pl.n)
-                return fail(BDPT_ERR_INVALID, entry + ": group_of_emitter[" + std::to_string(e) + "] = " +
-                                              std::to_string(pl.group_of_emitter[e]) + " is outside [0, n_groups)");
-    }
+                return fail(BDPT_ERR_INVALID, entry + "group_of_emitter[" + std::to_string(e) + "] = " +
+                                                  std::to_string(pl.group_of_emitter[e]) + " is outside [0, " + k.count + ")");
     }
     const char* what = p->flags != 0                              ? "with flags (a counting pass or full traversal)"
                        : p->russian_roulette != BDPT_RR_NONE      ? "with Russian roulette"
@@ -1151,31 +1207,25 @@ static int check_planes(const bdpt_ctx* c, const bdpt_frame_params* p, const Pla
                        : c->sc.lds_bsdf_off == dev::kNoLds        ? "with the BSDF records in HBM (too many materials "
                                                                     "for the LDS table)"
                                                                   : nullptr;
-    if (what)
-        return fail(BDPT_ERR_UNSUPPORTED, std::string(pl.kind == Planes::kStrats ? "strategies (per-(s, t) images)"
-                                                      : groups                   ? "light groups"
-                                                                                 : "path-length layers") +
-                                              " are not built " + what);
+    if (what) return fail(BDPT_ERR_UNSUPPORTED, std::string(k.phrase) + " are not built " + what);
     return BDPT_OK;
 }
 
 // bdpt_render and the BDPT form of bdpt_render_window (w null: every sample); with planes:
-// bdpt_render_layers / bdpt_render_light_groups (fb is pl.n planes, that build; check_planes
-// refuses what it does not serve).
+// the plane kinds' render entries (fb is pl.n planes, the kind's build; check_planes refuses
+// what it does not serve).
 static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* fb,
                        void* hip_stream, const Planes& pl = Planes{}) {
     if (!c || !fb) return fail(BDPT_ERR_INVALID, "null argument");
     int rc = check_params(p);
     if (rc) return rc;
     if ((rc = check_window(p, w))) return rc;
-    if (pl.kind != Planes::kNone && (rc = check_planes(c, p, pl))) return rc;
+    if (pl.kind && (rc = check_planes(c, p, pl))) return rc;
     if ((rc = textured_frame_check(c, p))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     dev::DevFrame fr = make_frame(p, w);
     fr.capped = c->capped;
-    fr.n_layers = pl.kind == Planes::kLayers ? pl.n : 0;
-    if (pl.kind == Planes::kStrats) fr.strat_shape = pl.n_s << 8 | pl.n_t;  // (shares n_layers' word)
     if (!fr.rr_mode && fr.total_samples > 0 && (rc = ensure_tasks(c))) return rc;
     fr.tasks = c->tasks;
     fr.task_cap = c->task_cap;
@@ -1207,7 +1257,7 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
         sc.mt_ring_stride = 1;  // slot-major blocks of kMtRingSlotWords words (DevScene::mt_ring)
     }
     if ((rc = begin_use(c, st))) return rc;
-    if (pl.kind == Planes::kGroups) {  // the call's table, from the context's own host copy, in stream order
+    if (pl.kind && pl.kind->mapped) {  // the call's table, from the context's own host copy, in stream order
         const size_t nemit = static_cast<size_t>(c->sc.nemit);
         c->emitter_group_host.resize(nemit);
         for (size_t e = 0; e < nemit; e++)
@@ -1215,8 +1265,8 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
         HIP_TRY(c->emitter_group.reserve(std::max<size_t>(nemit * sizeof(int32_t), 16)));
         HIP_TRY(hipMemcpyAsync(c->emitter_group, c->emitter_group_host.data(), nemit * sizeof(int32_t),
                                hipMemcpyHostToDevice, st));
-        fr.emitter_group = c->emitter_group;
     }
+    if (pl.kind) pl.fill(fr, c->emitter_group);
     HIP_TRY(hipMemsetAsync(c->work, 0, sizeof(unsigned long long), st));
     // BDPT_SAMPLE_RANGE="lo,hi" (debugging aid, tools/rr_find.py): only the shard's
     // samples [lo, hi) — the work counter starts at lo and the frame ends at hi
@@ -1242,11 +1292,7 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
     if ((rc = begin_timed(c, st))) return rc;
     int64_t launches = 0;
     if (fr.total_samples > 0) {
-        const FrameBuild& b = pl.kind == Planes::kLayers   ? frame_build_layers
-                              : pl.kind == Planes::kGroups ? frame_build_groups
-                              : pl.kind == Planes::kStrats
-                                  ? (pl.weighting == BDPT_STRATEGIES_UNWEIGHTED ? frame_build_strat_unweighted : frame_build_strat)
-                                  : pick_frame_build(c, p);
+        const FrameBuild& b = pl.kind ? pl.build() : pick_frame_build(c, p);
         c->last_kernel_glossy = 1;  // (until the launches below have succeeded)
         // Never more resident blocks than the slots allocated. c->grid is the default build's
         // blocks_per_cu of these LDS bytes (the HBM build's on an HBM table; bdpt_ctx_create),
@@ -1288,12 +1334,12 @@ int bdpt_render(bdpt_ctx* c, const bdpt_frame_params* p, float* fb, void* hip_st
 
 int bdpt_render_layers(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_layers,
                        float* fb_layers, void* hip_stream) {
-    return render_bdpt(c, p, w, fb_layers, hip_stream, Planes{Planes::kLayers, n_layers});
+    return render_bdpt(c, p, w, fb_layers, hip_stream, Planes{&kLayerPlanes, n_layers});
 }
 
 int bdpt_render_light_groups(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_groups,
                              const int32_t* group_of_emitter, float* fb_groups, void* hip_stream) {
-    return render_bdpt(c, p, w, fb_groups, hip_stream, Planes{Planes::kGroups, n_groups, group_of_emitter});
+    return render_bdpt(c, p, w, fb_groups, hip_stream, Planes{&kGroupPlanes, n_groups, group_of_emitter});
 }
 
 int bdpt_render_strategies(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_s, int32_t n_t,
@@ -1315,77 +1361,67 @@ int bdpt_strategies_shape(int32_t rr_depth, int32_t strategy, int32_t* n_s, int3
     return BDPT_OK;
 }
 
+// What the three combine entries check alike.
+static int check_gains_finite(const char* entry, const float* gains, int planes) {
+    for (int i = 0; gains && i < 3 * planes; i++)
+        if (!std::isfinite(gains[i]))
+            return fail(BDPT_ERR_INVALID, std::string(entry) + ": gains[" + std::to_string(i / 3) + "][" +
+                                              std::to_string(i % 3) + "] is not finite");
+    return BDPT_OK;
+}
+static bool overlap(const float* a, size_t a_floats, const float* b, size_t b_floats) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pb < pa + a_floats * sizeof(float) && pa < pb + b_floats * sizeof(float);
+}
+// n planes of kind k (its count's name and limit) combined into one width x height frame
+static int check_combine_shape(const char* entry, const PlaneKind& k, int32_t n, int32_t width, int32_t height) {
+    if (n < 1 || n > k.max) return fail(BDPT_ERR_INVALID, std::string(entry) + ": " + k.count + in_range(k.max));
+    if (width <= 0 || height <= 0 || static_cast<int64_t>(n) * width * height >= kMaxPlanePixels)
+        return fail(BDPT_ERR_INVALID, std::string(entry) + ": width/height must be > 0 and " + k.count + " * W * H " +
+                                          kBelowPlanePixels);
+    return BDPT_OK;
+}
+
 int bdpt_strategies_sheet(bdpt_ctx* c, const float* planes, int32_t n_s, int32_t n_t, int32_t width, int32_t height,
                           const float* gains, float* out, void* hip_stream) {
+    const char* const entry = "bdpt_strategies_sheet";
     if (!c || !planes || !out) return fail(BDPT_ERR_INVALID, "null argument");
-    if (n_s < 1 || n_s > kMaxStratS) return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: n_s must be in [1, 29]");
-    if (n_t < 1 || n_t > kMaxStratT) return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: n_t must be in [1, 28]");
-    if (width <= 0 || height <= 0) return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: width/height must be > 0");
-    const int64_t floats = static_cast<int64_t>(n_s) * n_t * width * height * 3;
+    if (int rc = check_strategy_shape(std::string(entry) + ": ", n_s, n_t)) return rc;
+    if (width <= 0 || height <= 0) return fail(BDPT_ERR_INVALID, std::string(entry) + ": width/height must be > 0");
+    const int64_t floats = static_cast<int64_t>(n_s) * n_t * width * height * 3;  // the planes' and the sheet's size alike
     if (floats >= (int64_t{1} << 31))
-        return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: the sheet (n_s * n_t * W * H * 3 floats) must be below 2^31 floats");
-    const int ngain = 3 * n_s * n_t;
-    for (int i = 0; gains && i < ngain; i++)
-        if (!std::isfinite(gains[i]))
-            return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: gains[" + std::to_string(i / 3) + "][" +
-                                              std::to_string(i % 3) + "] is not finite");
-    const uintptr_t a = reinterpret_cast<uintptr_t>(planes), o = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t bytes = static_cast<uintptr_t>(floats) * sizeof(float);  // the planes' and the sheet's size alike
-    if (o < a + bytes && a < o + bytes) return fail(BDPT_ERR_INVALID, "bdpt_strategies_sheet: out overlaps the planes");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    if (int rc = begin_use(c, st)) return rc;
-    const float* dgains = nullptr;
-    if (gains) {  // the call's table, from the context's own host copy, in stream order
-        c->sheet_gains_host.assign(gains, gains + ngain);
-        HIP_TRY(c->sheet_gains.reserve(sizeof(float) * 3 * kMaxStratS * kMaxStratT));
-        HIP_TRY(hipMemcpyAsync(c->sheet_gains, c->sheet_gains_host.data(), sizeof(float) * ngain, hipMemcpyHostToDevice, st));
-        dgains = c->sheet_gains;
-    }
-    if (int rc = begin_timed(c, st)) return rc;
-    HIP_TRY(launch_strategies_sheet(planes, n_s, n_t, width, height, dgains, out, st));
-    return end_timed(c, st, 0, 1);
+        return fail(BDPT_ERR_INVALID, std::string(entry) + ": the sheet (n_s * n_t * W * H * 3 floats) must be below 2^31 floats");
+    if (int rc = check_gains_finite(entry, gains, n_s * n_t)) return rc;
+    if (overlap(planes, floats, out, floats)) return fail(BDPT_ERR_INVALID, std::string(entry) + ": out overlaps the planes");
+    return combine_planes(c, hip_stream, gains, 3 * n_s * n_t, [&](const float* dgains, hipStream_t st) {
+        return launch_strategies_sheet(planes, n_s, n_t, width, height, dgains, out, st);
+    });
 }
 
 int bdpt_light_groups_relight(bdpt_ctx* c, const float* fb_groups, int32_t n_groups, int32_t width, int32_t height,
                               const float* gains, float* out, void* hip_stream) {
+    const char* const entry = "bdpt_light_groups_relight";
     if (!c || !fb_groups || !gains || !out) return fail(BDPT_ERR_INVALID, "null argument");
-    if (n_groups < 1 || n_groups > kMaxGroups)
-        return fail(BDPT_ERR_INVALID, "bdpt_light_groups_relight: n_groups must be in [1, 64]");
-    if (width <= 0 || height <= 0 || static_cast<int64_t>(n_groups) * width * height >= (int64_t{1} << 30))
-        return fail(BDPT_ERR_INVALID, "bdpt_light_groups_relight: width/height must be > 0 and n_groups * W * H below 2^30");
-    for (int i = 0; i < 3 * n_groups; i++)
-        if (!std::isfinite(gains[i]))
-            return fail(BDPT_ERR_INVALID, "bdpt_light_groups_relight: gains[" + std::to_string(i / 3) + "][" +
-                                              std::to_string(i % 3) + "] is not finite");
+    if (int rc = check_combine_shape(entry, kGroupPlanes, n_groups, width, height)) return rc;
+    if (int rc = check_gains_finite(entry, gains, n_groups)) return rc;
     const size_t n = static_cast<size_t>(width) * height * 3;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(fb_groups), o = reinterpret_cast<uintptr_t>(out);
-    if (o < a + n * n_groups * sizeof(float) && a < o + n * sizeof(float))
-        return fail(BDPT_ERR_INVALID, "bdpt_light_groups_relight: out overlaps the planes");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    if (int rc = begin_use(c, st)) return rc;
-    if (int rc = begin_timed(c, st)) return rc;
-    HIP_TRY(launch_relight(fb_groups, n, n_groups, gains, out, st));
-    return end_timed(c, st, 0, 1);
+    if (overlap(fb_groups, n * n_groups, out, n)) return fail(BDPT_ERR_INVALID, std::string(entry) + ": out overlaps the planes");
+    return combine_planes(c, hip_stream, nullptr, 0, [&](const float*, hipStream_t st) {  // (the gains are a kernel argument)
+        return launch_relight(fb_groups, n, n_groups, gains, out, st);
+    });
 }
 
 int bdpt_layers_compose(bdpt_ctx* c, const float* fb_layers, int32_t n_layers, int32_t width, int32_t height,
                         uint64_t mask, float* out, void* hip_stream) {
+    const char* const entry = "bdpt_layers_compose";
     if (!c || !fb_layers || !out) return fail(BDPT_ERR_INVALID, "null argument");
-    if (n_layers < 1 || n_layers > kMaxLayers)
-        return fail(BDPT_ERR_INVALID, "bdpt_layers_compose: n_layers must be in [1, 64]");
-    if (width <= 0 || height <= 0 || static_cast<int64_t>(n_layers) * width * height >= (int64_t{1} << 30))
-        return fail(BDPT_ERR_INVALID, "bdpt_layers_compose: width/height must be > 0 and n_layers * W * H below 2^30");
-    if (mask == 0) return fail(BDPT_ERR_INVALID, "bdpt_layers_compose: empty layer mask");
-    if (n_layers < 64 && (mask >> n_layers) != 0)
-        return fail(BDPT_ERR_INVALID, "bdpt_layers_compose: the mask has bits at or above n_layers");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    if (int rc = begin_use(c, st)) return rc;
-    if (int rc = begin_timed(c, st)) return rc;
-    HIP_TRY(launch_layers_compose(fb_layers, static_cast<size_t>(width) * height * 3, mask, out, st));
-    return end_timed(c, st, 0, 1);
+    if (int rc = check_combine_shape(entry, kLayerPlanes, n_layers, width, height)) return rc;
+    if (mask == 0) return fail(BDPT_ERR_INVALID, std::string(entry) + ": empty layer mask");
+    if (n_layers < kMaxLayers && (mask >> n_layers) != 0)
+        return fail(BDPT_ERR_INVALID, std::string(entry) + ": the mask has bits at or above n_layers");
+    return combine_planes(c, hip_stream, nullptr, 0, [&](const float*, hipStream_t st) {
+        return launch_layers_compose(fb_layers, static_cast<size_t>(width) * height * 3, mask, out, st);
+    });
 }
 
 // PathTracerIntegrator (path.h) on the same substrate: pt_kernels.hip.
@@ -1777,7 +1813,7 @@ static int render_bdpt_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_
     int rc = check_params(p);
     if (rc) return rc;
     if ((rc = check_window(p, w))) return rc;
-    if (pl.kind != Planes::kNone && (rc = check_planes(c, p, pl))) return rc;  // before the planes are staged
+    if (pl.kind && (rc = check_planes(c, p, pl))) return rc;  // before the planes are staged
     if ((rc = stage_host(c, fb_host, static_cast<size_t>(p->width) * p->height * 3 * pl.n,
                          [&](float* fb) { return render_bdpt(c, p, w, fb, c->stream, pl); })))
         return rc;
@@ -1802,14 +1838,14 @@ int bdpt_render_host(bdpt_ctx* c, const bdpt_frame_params* p, float* fb_host) {
 
 int bdpt_render_layers_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_layers,
                             float* fb_layers_host) {
-    return render_bdpt_host(c, p, w, fb_layers_host, Planes{Planes::kLayers, n_layers});
+    return render_bdpt_host(c, p, w, fb_layers_host, Planes{&kLayerPlanes, n_layers});
 }
 
 int bdpt_strategies_sheet_host(bdpt_ctx* c, const float* planes, int32_t n_s, int32_t n_t, int32_t width, int32_t height,
                                const float* gains, float* out) {
     if (!c || !planes || !out) return fail(BDPT_ERR_INVALID, "null argument");
     // a shape the device form refuses: refused by it (its first checks, which read no pointer) before anything is staged
-    const bool shape_ok = n_s >= 1 && n_s <= kMaxStratS && n_t >= 1 && n_t <= kMaxStratT && width > 0 && height > 0 &&
+    const bool shape_ok = strategy_shape_ok(n_s, n_t) && width > 0 && height > 0 &&
                           static_cast<int64_t>(n_s) * n_t * width * height * 3 < (int64_t{1} << 31);
     if (!shape_ok) return bdpt_strategies_sheet(c, planes, n_s, n_t, width, height, gains, out, c->stream);
     HIP_TRY(hipSetDevice(c->device));
@@ -1830,7 +1866,7 @@ int bdpt_render_strategies_host(bdpt_ctx* c, const bdpt_frame_params* p, const b
 
 int bdpt_render_light_groups_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
                                   int32_t n_groups, const int32_t* group_of_emitter, float* fb_groups_host) {
-    return render_bdpt_host(c, p, w, fb_groups_host, Planes{Planes::kGroups, n_groups, group_of_emitter});
+    return render_bdpt_host(c, p, w, fb_groups_host, Planes{&kGroupPlanes, n_groups, group_of_emitter});
 }
 
 // Sample windows: the three integrators' frame entries with a window (null: the whole

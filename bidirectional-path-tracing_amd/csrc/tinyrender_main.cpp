@@ -38,6 +38,7 @@
 // A second render, so the main EXR is the same bytes with or without it. A bad value, a path / direct
 // scene or an rr_depth outside 1..28 is refused before any device is used; with several devices the
 // first renders the planes.
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -351,65 +352,64 @@ int main(int argc, char** argv) {
         }
         if (fctx != ctx) bdpt_ctx_destroy(fctx);
     }
-    if (layers) {
-        bdpt_ctx* lctx = ctx;  // several devices: the first renders the layers
-        if (!lctx && bdpt_ctx_create(scene, devices[0], &lctx) != BDPT_OK) return die("bdpt_ctx_create (layers)");
-        const size_t plane = static_cast<size_t>(cfg.width) * cfg.height * 3;
-        std::vector<float> planes(plane * layers, 0.f);
-        if (bdpt_render_layers_host(lctx, &p, win, layers, planes.data()) != BDPT_OK) return die("bdpt_render_layers_host");
-        for (int l = 0; l < layers; l++) {
-            char suffix[16];
-            std::snprintf(suffix, sizeof suffix, ".L%02d", l);
-            const std::string side = side_path(exr, suffix);
-            if (bdpt_save_exr(planes.data() + plane * l, cfg.width, cfg.height, side.c_str()) != BDPT_OK)
-                return die("saveEXR");
+    // --layers, --light-groups, --strategies: the frame again as n planes (on several devices the
+    // first renders them), one EXR per plane under suffix(plane index), optionally only the planes
+    // that are not all zero; then after(context, planes), for what follows the planes.
+    const size_t plane = static_cast<size_t>(cfg.width) * cfg.height * 3;
+    auto write_planes = [&](const char* ctx_what, const char* render_what, size_t n, auto render, auto suffix,
+                            bool skip_empty, auto after) -> int {
+        bdpt_ctx* pctx = ctx;
+        if (!pctx && bdpt_ctx_create(scene, devices[0], &pctx) != BDPT_OK) return die(ctx_what);
+        std::vector<float> planes(plane * n, 0.f);
+        if (render(pctx, planes.data()) != BDPT_OK) return die(render_what);
+        for (size_t k = 0; k < n; k++) {
+            const float* const px = planes.data() + plane * k;
+            if (skip_empty && std::all_of(px, px + plane, [](float v) { return v == 0.f; })) continue;
+            const std::string side = side_path(exr, suffix(static_cast<int>(k)).c_str());
+            if (bdpt_save_exr(px, cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
             std::printf("Saved EXR image to %s\n", side.c_str());
         }
-        if (lctx != ctx) bdpt_ctx_destroy(lctx);
+        if (const int rc = after(pctx, planes.data())) return rc;
+        if (pctx != ctx) bdpt_ctx_destroy(pctx);
+        return EXIT_SUCCESS;
+    };
+    auto numbered = [](const char* format, int a, int b = 0) {
+        char suffix[24];
+        std::snprintf(suffix, sizeof suffix, format, a, b);
+        return std::string(suffix);
+    };
+    auto nothing = [](bdpt_ctx*, const float*) { return EXIT_SUCCESS; };
+    if (layers) {
+        const int rc = write_planes(
+            "bdpt_ctx_create (layers)", "bdpt_render_layers_host", layers,
+            [&](bdpt_ctx* c, float* fb) { return bdpt_render_layers_host(c, &p, win, layers, fb); },
+            [&](int l) { return numbered(".L%02d", l); }, false, nothing);
+        if (rc) return rc;
     }
     if (light_groups) {
-        bdpt_ctx* gctx = ctx;  // several devices: the first renders the groups
-        if (!gctx && bdpt_ctx_create(scene, devices[0], &gctx) != BDPT_OK) return die("bdpt_ctx_create (light groups)");
-        const size_t plane = static_cast<size_t>(cfg.width) * cfg.height * 3;
-        std::vector<float> planes(plane * n_emitters, 0.f);
-        if (bdpt_render_light_groups_host(gctx, &p, win, n_emitters, nullptr, planes.data()) != BDPT_OK)
-            return die("bdpt_render_light_groups_host");
-        for (int e = 0; e < n_emitters; e++) {
-            char suffix[16];
-            std::snprintf(suffix, sizeof suffix, ".E%02d", e);
-            const std::string side = side_path(exr, suffix);
-            if (bdpt_save_exr(planes.data() + plane * e, cfg.width, cfg.height, side.c_str()) != BDPT_OK)
-                return die("saveEXR");
-            std::printf("Saved EXR image to %s\n", side.c_str());
-        }
-        if (gctx != ctx) bdpt_ctx_destroy(gctx);
+        const int rc = write_planes(
+            "bdpt_ctx_create (light groups)", "bdpt_render_light_groups_host", n_emitters,
+            [&](bdpt_ctx* c, float* fb) { return bdpt_render_light_groups_host(c, &p, win, n_emitters, nullptr, fb); },
+            [&](int e) { return numbered(".E%02d", e); }, false, nothing);
+        if (rc) return rc;
     }
     if (strategies >= 0) {
-        bdpt_ctx* sctx = ctx;  // several devices: the first renders the planes
-        if (!sctx && bdpt_ctx_create(scene, devices[0], &sctx) != BDPT_OK) return die("bdpt_ctx_create (strategies)");
-        const size_t plane = static_cast<size_t>(cfg.width) * cfg.height * 3, n = static_cast<size_t>(n_s) * n_t;
-        std::vector<float> planes(plane * n, 0.f);
-        if (bdpt_render_strategies_host(sctx, &p, win, n_s, n_t, strategies, planes.data()) != BDPT_OK)
-            return die("bdpt_render_strategies_host");
-        for (int s = 0; s < n_s; s++)
-            for (int t = 1; t <= n_t; t++) {
-                const float* const px = planes.data() + plane * (static_cast<size_t>(s) * n_t + (t - 1));
-                bool any = false;
-                for (size_t i = 0; i < plane && !any; i++) any = px[i] != 0.f;
-                if (!any) continue;
-                char suffix[24];
-                std::snprintf(suffix, sizeof suffix, ".S%02dT%02d", s, t);
-                const std::string side = side_path(exr, suffix);
-                if (bdpt_save_exr(px, cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
+        const size_t n = static_cast<size_t>(n_s) * n_t;
+        const int rc = write_planes(
+            "bdpt_ctx_create (strategies)", "bdpt_render_strategies_host", n,
+            [&](bdpt_ctx* c, float* fb) { return bdpt_render_strategies_host(c, &p, win, n_s, n_t, strategies, fb); },
+            [&](int k) { return numbered(".S%02dT%02d", k / n_t, k % n_t + 1); }, true,
+            [&](bdpt_ctx* c, const float* planes) {  // the contact sheet, after its planes
+                std::vector<float> sheet(plane * n);
+                if (bdpt_strategies_sheet_host(c, planes, n_s, n_t, cfg.width, cfg.height, nullptr, sheet.data()) != BDPT_OK)
+                    return die("bdpt_strategies_sheet_host");
+                const std::string side = side_path(exr, ".strategies");
+                if (bdpt_save_exr(sheet.data(), n_s * cfg.width, n_t * cfg.height, side.c_str()) != BDPT_OK)
+                    return die("saveEXR");
                 std::printf("Saved EXR image to %s\n", side.c_str());
-            }
-        std::vector<float> sheet(plane * n);
-        if (bdpt_strategies_sheet_host(sctx, planes.data(), n_s, n_t, cfg.width, cfg.height, nullptr, sheet.data()) != BDPT_OK)
-            return die("bdpt_strategies_sheet_host");
-        const std::string side = side_path(exr, ".strategies");
-        if (bdpt_save_exr(sheet.data(), n_s * cfg.width, n_t * cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
-        std::printf("Saved EXR image to %s\n", side.c_str());
-        if (sctx != ctx) bdpt_ctx_destroy(sctx);
+                return EXIT_SUCCESS;
+            });
+        if (rc) return rc;
     }
     if (multi) bdpt_multi_destroy(multi);
     if (ctx) bdpt_ctx_destroy(ctx);

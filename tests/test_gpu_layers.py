@@ -10,7 +10,6 @@ be the sequential float32 sum, and what the build does not serve must be refused
 
 Frames are at most 64 x 64 x 16 spp (one 64-pixel row at 64 spp for the windows). A layered
 render is made once per (case, n_layers) and shared."""
-import json
 import os
 import subprocess
 
@@ -19,53 +18,18 @@ import pytest
 
 import bdpt_amd
 import variants
-from conftest import REPO, gpu_available, load_golden
+from conftest import gpu_available, load_golden
+from plane_cases import (BDPT_CASE, CBOX_CASE, FRAMES, LT_CASE, PT_CASE, RING_CASE, STRATEGY, bound_of, dilate,
+                         golden_integrator, open_first_hits, open_integrator, plane_sum, refused, scene,  # noqa: F401
+                         unsupported_setups, worst_per_plane)
 from test_config_exr import decode_exr
 from test_gpu_parity import TOL, rel_l2
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a HIP device")]
 
-STRATEGY = {"bdpt": bdpt_amd.STRATEGY_BDPT, "lt": bdpt_amd.STRATEGY_LIGHT_TRACING, "pt": bdpt_amd.STRATEGY_PATH_TRACING}
-with open(os.path.join(REPO, "tests", "golden", "manifest.json")) as _f:
-    FRAMES = json.load(_f)["framebuffers"]
-
-
-def smallest(strategy):
-    """The smallest golden (by samples; the manifest's order breaks ties) of the strategy that
-    fits 64 x 64 x 16 spp in one shard. synth1m is left out: building its million triangles
-    takes longer than every render here together."""
-    fit = [(m["samples"], i, n) for i, (n, m) in enumerate(FRAMES.items())
-           if m.get("strategy", "bdpt") == strategy and m["width"] <= 64 and m["height"] <= 64 and m["spp"] <= 16
-           and m["row_stride"] == 1 and m["scene"] != "synth1m"]
-    return min(fit)[2]
-
-
-BDPT_CASE, LT_CASE, PT_CASE, CBOX_CASE = smallest("bdpt"), smallest("lt"), smallest("pt"), "G1_cbox_low_64x64_spp4"
-RING_CASE = "G2_caustic_64x64_spp16"  # glass (delta light vertices) and, at BDPT_TASK_CAP=64, refused pushes
 SUM_CASES = [BDPT_CASE, LT_CASE, PT_CASE, CBOX_CASE, RING_CASE]
 
-_scenes, _layers = {}, {}
-
-
-def scene(path):
-    if path not in _scenes:
-        _scenes[path] = bdpt_amd.Scene(path)
-    return _scenes[path]
-
-
-def golden_integrator(name, **kw):
-    m = FRAMES[name]
-    args = dict(camera=bdpt_amd.Camera(**variants.SCENES[m["scene"]]["camera"]), width=m["width"], height=m["height"],
-                spp=m["spp"], rr_depth=m["rr_depth"], strategy=STRATEGY[m.get("strategy", "bdpt")])
-    args.update(kw)
-    it = bdpt_amd.BDPTIntegrator(scene(variants.obj_path(m["scene"])), bdpt_amd.Config(**args))
-    it.init()
-    return it
-
-
-def bound_of(name):
-    m = FRAMES[name]
-    return bdpt_amd.layers_longest_path(m["rr_depth"], STRATEGY[m.get("strategy", "bdpt")])
+_layers = {}
 
 
 def layers_of(name, n_layers):
@@ -84,14 +48,6 @@ def layers_of(name, n_layers):
     return _layers[key]
 
 
-def layer_sum(layers):
-    return layers.astype(np.float64).sum(axis=0)
-
-
-def worst_per_layer(a, b):
-    return max(rel_l2(a[l], b[l]).max() for l in range(a.shape[0]))
-
-
 # ---------------------------------------------------------------- 1. the layers add up
 @pytest.mark.parametrize("which", ["bound+1", "3", "1"])
 @pytest.mark.parametrize("name", SUM_CASES)
@@ -99,7 +55,7 @@ def test_gpu_layers_sum_to_the_reference_frame(name, which):
     n = {"bound+1": bound_of(name) + 1, "3": 3, "1": 1}[which]
     layers = layers_of(name, n)
     ref = load_golden(name)
-    total = layers[0] if n == 1 else layer_sum(layers)  # n = 1: the layer itself is the frame
+    total = layers[0] if n == 1 else plane_sum(layers)  # n = 1: the layer itself is the frame
     worst = rel_l2(np.asarray(total), ref).max()
     print(f"{name} n_layers {n}: max per-pixel rel L2 of the layer sum {worst:.3g}; layer means "
           f"{[float(f'{x:.3g}') for x in layers.reshape(n, -1).mean(axis=1)]}")
@@ -111,54 +67,10 @@ def test_gpu_layers_sum_to_the_reference_frame(name, which):
         # the overflow bucket is in use: layers 0 and 1 are the long render's, the last its rest
         full = layers_of(name, bound_of(name) + 1)
         assert rel_l2(layers[0], full[0]).max() <= TOL and rel_l2(layers[1], full[1]).max() <= TOL
-        assert rel_l2(layers[2], layer_sum(full[2:])).max() <= TOL
+        assert rel_l2(layers[2], plane_sum(full[2:])).max() <= TOL
 
 
 # ------------------------------------------------- 2. the layer index in absolute terms
-OPEN_OBJ = os.path.join(REPO, "scenes", "kat", "layers_open.obj")
-OPEN_CAMERA = dict(eye=(0.0, 0.6, 3.0), at=(0.0, 0.6, 0.0), up=(0.0, 1.0, 0.0), fov=45.0)
-OPEN_W = OPEN_H = 48
-
-
-def open_integrator(spp, strategy=bdpt_amd.STRATEGY_BDPT):
-    cfg = bdpt_amd.Config(camera=bdpt_amd.Camera(**OPEN_CAMERA), width=OPEN_W, height=OPEN_H, spp=spp, rr_depth=5,
-                          strategy=strategy)
-    it = bdpt_amd.BDPTIntegrator(scene(OPEN_OBJ), cfg)
-    it.init()
-    return it
-
-
-def dilate(mask):
-    """The mask and the 8 neighbours of each of its pixels."""
-    p = np.pad(mask, 1)
-    out = np.zeros_like(mask)
-    for dy in range(3):
-        for dx in range(3):
-            out |= p[dy:dy + mask.shape[0], dx:dx + mask.shape[1]]
-    return out
-
-
-@pytest.fixture(scope="module")
-def open_first_hits():
-    """Per pixel, what the frame's own spp = 1 camera ray hits first: (emitter mask, floor mask)."""
-    it = open_integrator(1)
-    px = np.arange(OPEN_W * OPEN_H, dtype=np.uint32)
-    rec = np.stack([px, np.zeros_like(px), np.zeros_like(px)], axis=1)
-    d = it.debug_sampling("camera", rec).view(np.float32)
-    rays = np.zeros((px.size, 8), np.float32)
-    rays[:, 0:3] = OPEN_CAMERA["eye"]
-    rays[:, 3:6] = d
-    rays[:, 6], rays[:, 7] = 1.0, 1000.0  # the camera ray's range (renderer.cpp)
-    hit = it.intersect(rays)
-    got = hit["hit"] == 1
-    y = hit["p"][:, 1]  # the emitter quad lies at y = 1.3, the floor at y = 0
-    emitter = (got & (y > 0.5)).reshape(OPEN_H, OPEN_W)
-    floor = (got & (y <= 0.5)).reshape(OPEN_H, OPEN_W)
-    assert emitter.sum() >= 4 and floor.sum() >= 100 and not (emitter & floor).any()  # the camera sees both
-    assert not dilate(emitter)[floor].any()  # and they are apart in the image
-    return emitter, floor
-
-
 @pytest.mark.parametrize("strategy", ["bdpt", "lt", "pt"])
 @pytest.mark.parametrize("spp", [1, 8])
 def test_gpu_layer_index_is_absolute_on_the_open_scene(open_first_hits, spp, strategy):
@@ -181,7 +93,7 @@ def test_gpu_layer_index_is_absolute_on_the_open_scene(open_first_hits, spp, str
         assert np.allclose(layers[0][emitter], np.float32([17.0, 12.0, 4.0]), rtol=1e-6)
     # and the layers are the plain frame
     ref = open_integrator(spp, STRATEGY[strategy]).render_frame()
-    assert rel_l2(layer_sum(layers), ref).max() <= TOL
+    assert rel_l2(plane_sum(layers), ref).max() <= TOL
 
 
 # ------------------------------------------------------------ 3. the depth bound is tight
@@ -208,7 +120,7 @@ def test_gpu_row_shards_sum_to_the_full_layers():
     n = bound_of(CBOX_CASE) + 1
     full = layers_of(CBOX_CASE, n)
     parts = [golden_integrator(CBOX_CASE).render_layers(n, row_offset=o, row_stride=2) for o in (0, 1)]
-    worst = worst_per_layer(parts[0] + parts[1], full)
+    worst = worst_per_plane(parts[0] + parts[1], full)
     print(f"two interleaved row shards: worst per-layer per-pixel rel L2 {worst:.3g}")
     assert worst <= 1e-4
 
@@ -223,10 +135,10 @@ def test_gpu_sample_windows_sum_to_the_full_layers():
     a = golden_integrator(CBOX_CASE, spp=64).render_layers(n, window=bdpt_amd.SampleWindow(0, 1, 40), **row)
     b = golden_integrator(CBOX_CASE, spp=64).render_layers(n, window=bdpt_amd.SampleWindow(40, 1, 24), **row)
     assert full[0, 40].any() or full[1, 40].any()
-    worst = worst_per_layer(a + b, full)
+    worst = worst_per_plane(a + b, full)
     print(f"sample windows 40 + 24 of 64: worst per-layer per-pixel rel L2 {worst:.3g}")
     assert worst <= 1e-4
-    assert rel_l2(layer_sum(full), golden_integrator(CBOX_CASE, spp=64).render_frame(**row)).max() <= TOL
+    assert rel_l2(plane_sum(full), golden_integrator(CBOX_CASE, spp=64).render_frame(**row)).max() <= TOL
 
 
 # ----------------------------------------------------- 5. the ring-full path is layered
@@ -245,8 +157,8 @@ def test_gpu_ring_full_fallback_is_layered(name, monkeypatch):
     it = golden_integrator(name)
     small = it.render_layers(n)
     assert it.stats()["kernel"] == "bdpt_frame_kernel_layers" and it.stats()["schedule_errors"] == 0
-    worst_sum = rel_l2(layer_sum(small), load_golden(name)).max()
-    worst = worst_per_layer(small, default)
+    worst_sum = rel_l2(plane_sum(small), load_golden(name)).max()
+    worst = worst_per_plane(small, default)
     print(f"{name} at BDPT_TASK_CAP=64: layer sum vs golden {worst_sum:.3g}, per layer vs default ring {worst:.3g}")
     assert worst_sum <= TOL
     assert worst <= 1e-4
@@ -281,29 +193,10 @@ def test_gpu_compose_is_the_sequential_float32_sum():
 
 # ------------------------------------------------- 7. refusals and non-interference
 def test_gpu_layers_unsupported_and_invalid(monkeypatch):
-    def refused(fn, code, *words):
-        with pytest.raises(bdpt_amd.BdptError) as e:
-            fn()
-        assert e.value.code == code, str(e.value)
-        for w in words:
-            assert w in str(e.value), str(e.value)
-
     U, I = bdpt_amd.ERR_UNSUPPORTED, bdpt_amd.ERR_INVALID
     name = CBOX_CASE
-    refused(lambda: golden_integrator(name, russian_roulette=bdpt_amd.RR_LUMINANCE).render_layers(4), U, "layers")
-    refused(lambda: golden_integrator(name, rr_depth=29).render_layers(4), U, "layers", "rr_depth")
-    refused(lambda: golden_integrator(name).render_layers(4, flags=bdpt_amd.FLAG_COUNT), U, "layers", "flags")
-    with open(os.path.join(REPO, "tests", "golden", "tex_manifest.json")) as f:
-        tex = json.load(f)
-    tm = tex["frames"]["tex_T1_texbox_bdpt"]
-    cam = bdpt_amd.Camera(**{k: tuple(v) if isinstance(v, list) else v for k, v in tex["camera"].items()})
-    tcfg = bdpt_amd.Config(camera=cam, width=tm["width"], height=tm["height"], spp=tm["spp"], rr_depth=tm["rr_depth"])
-    refused(lambda: bdpt_amd.BDPTIntegrator(scene(os.path.join(REPO, "scenes", "tex", tm["obj"])), tcfg).render_layers(4),
-            U, "layers", "texture")
-    with monkeypatch.context() as mp:  # (the context reads it when it is created)
-        mp.setenv("BDPT_BSDF_IN_HBM", "1")
-        hbm = golden_integrator(name)
-    refused(lambda: hbm.render_layers(4), U, "layers", "HBM")
+    for bad, kw, word in unsupported_setups(name, monkeypatch):
+        refused(lambda: bad.render_layers(4, **kw), U, "layers", word)
     it = golden_integrator(name)
     refused(lambda: it.render_layers(0), I, "n_layers")
     refused(lambda: it.render_layers(65), I, "n_layers")
@@ -328,7 +221,7 @@ def test_gpu_plain_frames_around_a_layered_render_are_unchanged():
     assert k0 == k1 == "bdpt_frame_kernel", (k0, k1)
     assert rel_l2(after, before).max() <= 1e-4
     assert rel_l2(before, load_golden(RING_CASE)).max() <= TOL
-    assert rel_l2(layer_sum(layers), before).max() <= 1e-4
+    assert rel_l2(plane_sum(layers), before).max() <= 1e-4
     assert m["rr_depth"] == 8
 
 

@@ -24,13 +24,13 @@ import bdpt_amd
 import variants
 from conftest import REPO, gpu_available, load_golden
 from test_config_exr import decode_exr
-from test_gpu_layers import FRAMES, STRATEGY, golden_integrator, scene, smallest
+from plane_cases import (CBOX_CASE, EDGES_CASE, FRAMES, LT_CASE, PT_CASE, STRATEGY, golden_integrator, plane_sum, refused,
+                         scene, unsupported_setups, worst_per_plane)
 from test_gpu_parity import TOL, rel_l2
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a HIP device")]
 
-EDGES_CASE, CBOX_CASE, CAUSTIC_CASE = "G14_emit_edges_32x32_spp4", "G1_cbox_low_64x64_spp4", "G2_caustic_64x64_spp16"
-LT_CASE, PT_CASE = smallest("lt"), smallest("pt")
+CAUSTIC_CASE = "G2_caustic_64x64_spp16"
 SUM_CASES = [EDGES_CASE, CBOX_CASE, CAUSTIC_CASE, LT_CASE, PT_CASE]
 KERNEL = "bdpt_frame_kernel_groups"
 RELIT = np.load(os.path.join(REPO, "tests", "golden", "light_groups_emit_edges_relit.npz"))
@@ -57,14 +57,6 @@ def groups_of(name, group_map=None, n_groups=None, **kw):
         out.setflags(write=False)
         _groups[key] = out
     return _groups[key]
-
-
-def plane_sum(planes):
-    return planes.astype(np.float64).sum(axis=0)
-
-
-def worst_per_plane(a, b):
-    return max(rel_l2(a[g], b[g]).max() for g in range(a.shape[0]))
 
 
 def relight_model(planes, gains):
@@ -279,41 +271,17 @@ def test_gpu_relight_errors():
 
 # ------------------------------------------------- 7. refusals and non-interference
 def test_gpu_light_groups_unsupported_and_invalid(monkeypatch):
-    def refused(it, fn, code, *words):
-        it.render_frame()  # (so that the context has stats of a call that launched)
-        before = it.stats()["launches"]
-        with pytest.raises(bdpt_amd.BdptError) as e:
-            fn(it)
-        assert e.value.code == code, str(e.value)
-        for w in words:
-            assert w in str(e.value), str(e.value)
-        assert it.stats()["launches"] == before, "a refused call launched"
-
     U, I = bdpt_amd.ERR_UNSUPPORTED, bdpt_amd.ERR_INVALID
     name = EDGES_CASE
-    G = "light groups"
-    refused(golden_integrator(name, russian_roulette=bdpt_amd.RR_LUMINANCE), lambda it: it.render_light_groups(), U, G,
-            "Russian roulette")
-    refused(golden_integrator(name, rr_depth=29), lambda it: it.render_light_groups(), U, G, "rr_depth")
-    refused(golden_integrator(name), lambda it: it.render_light_groups(flags=bdpt_amd.FLAG_COUNT), U, G, "flags")
-    with open(os.path.join(REPO, "tests", "golden", "tex_manifest.json")) as f:
-        tex = json.load(f)
-    tm = tex["frames"]["tex_T1_texbox_bdpt"]
-    cam = bdpt_amd.Camera(**{k: tuple(v) if isinstance(v, list) else v for k, v in tex["camera"].items()})
-    tcfg = bdpt_amd.Config(camera=cam, width=tm["width"], height=tm["height"], spp=tm["spp"], rr_depth=tm["rr_depth"])
-    refused(bdpt_amd.BDPTIntegrator(scene(os.path.join(REPO, "scenes", "tex", tm["obj"])), tcfg),
-            lambda it: it.render_light_groups(), U, G, "texture")
-    with monkeypatch.context() as mp:  # (the context reads it when it is created)
-        mp.setenv("BDPT_BSDF_IN_HBM", "1")
-        hbm = golden_integrator(name)
-    refused(hbm, lambda it: it.render_light_groups(), U, G, "HBM")
+    for bad, kw, word in unsupported_setups(name, monkeypatch):
+        refused(lambda: bad.render_light_groups(**kw), U, "light groups", word, launched=bad)
     it = golden_integrator(name)
-    refused(it, lambda it: it.render_light_groups([0] * 5, 0), I, "n_groups")
-    refused(it, lambda it: it.render_light_groups([0] * 5, 65), I, "n_groups")
-    refused(it, lambda it: it.render_light_groups(None, 4), I, "n_groups", "emitter count")
-    refused(it, lambda it: it.render_light_groups(None, 6), I, "n_groups", "emitter count")
-    refused(it, lambda it: it.render_light_groups([0, 1, 2, 3, 5], 5), I, "group_of_emitter[4]")
-    refused(it, lambda it: it.render_light_groups([0, -1, 2, 3, 4], 5), I, "group_of_emitter[1]")
+    refused(lambda: it.render_light_groups([0] * 5, 0), I, "n_groups", launched=it)
+    refused(lambda: it.render_light_groups([0] * 5, 65), I, "n_groups", launched=it)
+    refused(lambda: it.render_light_groups(None, 4), I, "n_groups", "emitter count", launched=it)
+    refused(lambda: it.render_light_groups(None, 6), I, "n_groups", "emitter count", launched=it)
+    refused(lambda: it.render_light_groups([0, 1, 2, 3, 5], 5), I, "group_of_emitter[4]", launched=it)
+    refused(lambda: it.render_light_groups([0, -1, 2, 3, 4], 5), I, "group_of_emitter[1]", launched=it)
     # n_groups * W * H >= 2^30, in the params only: refused before anything is allocated
     big = golden_integrator(name)
     big.render_frame()

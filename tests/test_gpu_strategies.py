@@ -13,7 +13,6 @@ not serve must be refused.
 
 Frames are at most 64 x 64 x 16 spp (one 64-pixel row at 64 spp for the windows). A render is made
 once per (case, shape, weighting) and shared."""
-import json
 import os
 import subprocess
 
@@ -22,15 +21,16 @@ import pytest
 
 import bdpt_amd
 import variants
-from conftest import REPO, gpu_available, load_golden
+from conftest import gpu_available, load_golden
+from plane_cases import (BDPT_CASE, CBOX_CASE, EDGES_CASE, FRAMES, LT_CASE, OPEN_H, OPEN_W, PT_CASE, RING_CASE, STRATEGY,  # noqa: F401
+                         bound_of, dilate, golden_integrator, open_first_hits, open_integrator, plane_sum, refused, scene,
+                         unsupported_setups, worst_per_plane)
 from test_config_exr import decode_exr
-from test_gpu_layers import (BDPT_CASE, CBOX_CASE, FRAMES, LT_CASE, OPEN_H, OPEN_W, PT_CASE, RING_CASE, STRATEGY, bound_of,
-                             dilate, golden_integrator, layers_of, open_first_hits, open_integrator, scene)  # noqa: F401
+from test_gpu_layers import layers_of
 from test_gpu_parity import TOL, rel_l2
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a HIP device")]
 
-EDGES_CASE = "G14_emit_edges_32x32_spp4"
 CAUSTIC_CASE, HARDLIGHT_CASE = RING_CASE, "G3_hardlight_64x64_spp16"  # G2, G3: the BDPT twins of G9, G11
 KERNEL = {False: "bdpt_frame_kernel_strat", True: "bdpt_frame_kernel_strat_unweighted"}
 
@@ -61,14 +61,6 @@ def planes_of(name, shape=None, unweighted=False):
 
 def P(planes, s, t):
     return planes[s, t - 1]
-
-
-def plane_sum(planes):
-    return planes.astype(np.float64).sum(axis=(0, 1))
-
-
-def worst_per_plane(a, b):
-    return max(rel_l2(a[s, r], b[s, r]).max() for s in range(a.shape[0]) for r in range(a.shape[1]))
 
 
 def means(planes):
@@ -307,63 +299,36 @@ def test_gpu_sheet_rejects_bad_inputs():
     it = golden_integrator(CBOX_CASE)
     I = bdpt_amd.ERR_INVALID
 
-    def refused(fn, *words):
-        with pytest.raises(bdpt_amd.BdptError) as e:
-            fn()
-        assert e.value.code == I, str(e.value)
-        for w in words:
-            assert w in str(e.value), str(e.value)
-
     d = torch.zeros(2 * 2 * 2 * 4 * 4 * 3, dtype=torch.float32, device="cuda")  # planes, then room for the sheet
     n = 2 * 2 * 4 * 4 * 3
     p, o = d.data_ptr(), d.data_ptr() + 4 * n
     it.strategies_sheet_device(p, 2, 2, 4, 4, None, o)  # the good call
     it.synchronize()
     # a sheet of 2^31 floats or more, from the arguments alone (no such buffer exists; refused before any launch)
-    refused(lambda: it.strategies_sheet_device(p, 29, 28, 1024, 1024, None, o), "2^31")
-    refused(lambda: it.strategies_sheet_device(p, 4, 4, 8192, 8192, None, o), "2^31")
-    refused(lambda: it.strategies_sheet_device(p, 2, 2, 4, 4, None, p), "overlaps")
-    refused(lambda: it.strategies_sheet_device(p, 2, 2, 4, 4, None, p + 4 * (n - 1)), "overlaps")
-    refused(lambda: it.strategies_sheet_device(p + 4 * (n - 1), 2, 2, 4, 4, None, p), "overlaps")
+    refused(lambda: it.strategies_sheet_device(p, 29, 28, 1024, 1024, None, o), I, "2^31")
+    refused(lambda: it.strategies_sheet_device(p, 4, 4, 8192, 8192, None, o), I, "2^31")
+    refused(lambda: it.strategies_sheet_device(p, 2, 2, 4, 4, None, p), I, "overlaps")
+    refused(lambda: it.strategies_sheet_device(p, 2, 2, 4, 4, None, p + 4 * (n - 1)), I, "overlaps")
+    refused(lambda: it.strategies_sheet_device(p + 4 * (n - 1), 2, 2, 4, 4, None, p), I, "overlaps")
     bad = np.ones((4, 3), np.float32)
     for v in (np.nan, np.inf, -np.inf):
         bad[2, 1] = v
-        refused(lambda: it.strategies_sheet_device(p, 2, 2, 4, 4, bad, o), "gains[2][1]", "finite")
-    refused(lambda: it.strategies_sheet_device(p, 0, 2, 4, 4, None, o), "n_s")
-    refused(lambda: it.strategies_sheet_device(p, 30, 2, 4, 4, None, o), "n_s")
-    refused(lambda: it.strategies_sheet_device(p, 2, 29, 4, 4, None, o), "n_t")
-    refused(lambda: it.strategies_sheet_device(p, 2, 2, 0, 4, None, o), "width")
-    refused(lambda: it.strategies_sheet_device(0, 2, 2, 4, 4, None, o), "null")
+        refused(lambda: it.strategies_sheet_device(p, 2, 2, 4, 4, bad, o), I, "gains[2][1]", "finite")
+    refused(lambda: it.strategies_sheet_device(p, 0, 2, 4, 4, None, o), I, "n_s")
+    refused(lambda: it.strategies_sheet_device(p, 30, 2, 4, 4, None, o), I, "n_s")
+    refused(lambda: it.strategies_sheet_device(p, 2, 29, 4, 4, None, o), I, "n_t")
+    refused(lambda: it.strategies_sheet_device(p, 2, 2, 0, 4, None, o), I, "width")
+    refused(lambda: it.strategies_sheet_device(0, 2, 2, 4, 4, None, o), I, "null")
 
 
 # ------------------------------------------------- 10. refusals and non-interference
 def test_gpu_strategies_unsupported_and_invalid(monkeypatch):
-    def refused(fn, code, *words):
-        with pytest.raises(bdpt_amd.BdptError) as e:
-            fn()
-        assert e.value.code == code, str(e.value)
-        for w in words:
-            assert w in str(e.value), str(e.value)
-
     U, I = bdpt_amd.ERR_UNSUPPORTED, bdpt_amd.ERR_INVALID
     name = CBOX_CASE
-    for unweighted in (False, True):
-        kw = dict(unweighted=unweighted)
-        refused(lambda: golden_integrator(name, russian_roulette=bdpt_amd.RR_LUMINANCE).render_strategies(**kw), U,
-                "strategies", "roulette")
-        refused(lambda: golden_integrator(name, rr_depth=29).render_strategies(4, 4, **kw), U, "strategies", "rr_depth")
-        refused(lambda: golden_integrator(name).render_strategies(flags=bdpt_amd.FLAG_COUNT, **kw), U, "strategies", "flags")
-    with open(os.path.join(REPO, "tests", "golden", "tex_manifest.json")) as f:
-        tex = json.load(f)
-    tm = tex["frames"]["tex_T1_texbox_bdpt"]
-    cam = bdpt_amd.Camera(**{k: tuple(v) if isinstance(v, list) else v for k, v in tex["camera"].items()})
-    tcfg = bdpt_amd.Config(camera=cam, width=tm["width"], height=tm["height"], spp=tm["spp"], rr_depth=tm["rr_depth"])
-    refused(lambda: bdpt_amd.BDPTIntegrator(scene(os.path.join(REPO, "scenes", "tex", tm["obj"])), tcfg).render_strategies(),
-            U, "strategies", "texture")
-    with monkeypatch.context() as mp:  # (the context reads it when it is created)
-        mp.setenv("BDPT_BSDF_IN_HBM", "1")
-        hbm = golden_integrator(name)
-    refused(lambda: hbm.render_strategies(), U, "strategies", "HBM")
+    for bad, kw, word in unsupported_setups(name, monkeypatch):
+        shape = (4, 4) if word == "rr_depth" else ()  # (the default shape of rr_depth 29 is refused earlier)
+        for unweighted in (False, True):
+            refused(lambda: bad.render_strategies(*shape, unweighted=unweighted, **kw), U, "strategies", word)
     it = golden_integrator(name)
     refused(lambda: it.render_strategies(0, 2), I, "n_s")
     refused(lambda: it.render_strategies(30, 2), I, "n_s")
