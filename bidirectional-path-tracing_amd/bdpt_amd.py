@@ -22,6 +22,11 @@ Mirrors the reference's plugin surface for the BDPT path
                                        the BDPT frame split by sampling strategy (s, t), with or without the
                                        MIS weights, and its contact sheet (bdpt_render_strategies,
                                        bdpt_strategies_sheet; no counterpart)
+    .render_group_layers(n) / .render_group_strategies(n_s, n_t) / .combine_group_planes(planes, gains, weights)
+                                       the BDPT frame split by emitter AND by path length or strategy, a plane per
+                                       (group, layer) / (group, s, t), recombined with per-group RGB gains and
+                                       per-inner-plane weights (bdpt_render_group_layers,
+                                       bdpt_render_group_strategies, bdpt_group_planes_combine; no counterpart)
   Sampler(seed)                        Sampler              src/core/math.h:63-76 (seed + draw count)
   Ray(o, d, min_t, max_t)              Ray                  src/core/core.h:117-122
   load_toml(path) -> SceneConfig       loadTOML             src/main.cpp:22-116
@@ -333,6 +338,13 @@ def lib():
         L.bdpt_render_strategies_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, i32, i32, vp]
         L.bdpt_strategies_shape.argtypes = [i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
         L.bdpt_strategies_sheet.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
+        gl = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), vp, i32, i32]
+        L.bdpt_render_group_layers.argtypes = gl + [vp, vp]
+        L.bdpt_render_group_layers_host.argtypes = gl + [vp]
+        L.bdpt_render_group_strategies.argtypes = gl + [i32, i32, vp, vp]
+        L.bdpt_render_group_strategies_host.argtypes = gl + [i32, i32, vp]
+        L.bdpt_group_planes_combine.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+        L.bdpt_group_planes_combine_host.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
         L.bdpt_synchronize.argtypes = [vp]
         L.bdpt_config_load_toml.argtypes = [ctypes.c_char_p, ctypes.POINTER(_Config)]
         L.bdpt_render_path.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_PathParams), vp, vp]
@@ -871,6 +883,63 @@ def strategies_sheet_numpy(planes, gains=None) -> np.ndarray:
     return out
 
 
+GROUP_INNER_MAX = STRATEGIES_MAX_S * STRATEGIES_MAX_T  # bdpt_group_planes_combine's most planes per group
+
+
+def _group_planes_args(planes, gains, weights):
+    """combine_group_planes' arguments checked as bdpt_group_planes_combine checks them (before anything
+    is copied): planes (n_groups, n_layers, H, W, 3) or (n_groups, n_s, n_t, H, W, 3) within the limits,
+    gains None or finite (n_groups, 3) / (n_groups,), weights None or finite with the inner axes' shape
+    or flat. -> (float32 (n_groups, n_inner, H, W, 3) planes, (n_groups, 3) gains or None, (n_inner,)
+    weights or None)."""
+    shape = np.shape(planes)
+    if len(shape) not in (5, 6) or shape[-1] != 3:
+        raise BdptError("combine_group_planes: planes must be (n_groups, n_layers, H, W, 3) or "
+                        f"(n_groups, n_s, n_t, H, W, 3), got {shape}")
+    n, inner, (H, W) = shape[0], shape[1:-3], shape[-3:-1]
+    n_inner = math.prod(inner)
+    if not 1 <= n <= GROUPS_MAX or not 1 <= n_inner <= GROUP_INNER_MAX or H < 1 or W < 1:
+        raise BdptError(f"combine_group_planes: n_groups must be in [1, {GROUPS_MAX}], the planes per group in "
+                        f"[1, {GROUP_INNER_MAX}], H and W > 0, got {shape}")
+    if n * n_inner * H * W >= PLANE_PIXELS_MAX:
+        raise BdptError("combine_group_planes: n_groups * n_inner * W * H must be below 2^30")
+    g = w = None
+    if gains is not None:
+        g = np.asarray(gains, np.float32)
+        if g.shape == (n,):
+            g = np.repeat(g[:, None], 3, axis=1)
+        if g.shape != (n, 3):
+            raise BdptError(f"combine_group_planes: gains must be ({n}, 3) or ({n},), got {g.shape}")
+        g = np.ascontiguousarray(g)
+        if not np.isfinite(g).all():
+            raise BdptError("combine_group_planes: a gain is not finite")
+    if weights is not None:
+        w = np.asarray(weights, np.float32)
+        if w.shape not in (tuple(inner), (n_inner,)):
+            raise BdptError(f"combine_group_planes: weights must be {tuple(inner)} or ({n_inner},), got {w.shape}")
+        w = np.ascontiguousarray(w.reshape(n_inner))
+        if not np.isfinite(w).all():
+            raise BdptError("combine_group_planes: a weight is not finite")
+    return np.ascontiguousarray(planes, np.float32).reshape(n, n_inner, H, W, 3), g, w
+
+
+def combine_group_planes_numpy(planes, gains=None, weights=None) -> np.ndarray:
+    """What bdpt_group_planes_combine computes, as the obvious loop on the host: with acc the first
+    term, for g ascending and within it j ascending t = weights[j] * planes[g, j]; t = gains[g] * t;
+    acc = acc + t, every operation a float32 rounding of its own (None: ones, multiplied like any)."""
+    a, g, w = _group_planes_args(planes, gains, weights)
+    n, n_inner = a.shape[:2]
+    g = np.ones((n, 3), np.float32) if g is None else g
+    w = np.ones(n_inner, np.float32) if w is None else w
+    acc = None
+    for i in range(n):
+        for j in range(n_inner):
+            t = g[i][None, None, :] * (w[j] * a[i, j])
+            acc = t if acc is None else acc + t
+    assert acc.dtype == np.float32
+    return acc
+
+
 class BDPTIntegrator:
     """GPU BDPT integrator with the reference's Integrator interface."""
 
@@ -1128,7 +1197,7 @@ class BDPTIntegrator:
                                      ctypes.c_void_p(stream_ptr)))
 
     def _render_planes(self, entry, args, planes, ok, window, row_offset, row_stride, flags, fb_ptr=None, stream_ptr=0):
-        """One plane render (layers, light groups, strategies): entry(ctx, params, window, *args, fb[, stream]).
+        """One plane render (layers, light groups, strategies, the crossed kinds): entry(ctx, params, window, *args, fb[, stream]).
         planes None: the device entry, ADDED to fb_ptr. Otherwise the host entry into a new planes + (H, W, 3)
         array, which is returned; a count the library refuses (ok false) or a size it refuses, both before it
         touches the buffer, is not allocated here."""
@@ -1176,7 +1245,7 @@ class BDPTIntegrator:
         return m
 
     def _combine(self, a, out_shape, call) -> np.ndarray:
-        """The round trip of compose_layers, relight and strategies_sheet: the contiguous float32 planes go to
+        """The round trip of compose_layers, relight, strategies_sheet and combine_group_planes: the contiguous float32 planes go to
         the device, call(planes pointer, out pointer) runs the device form on them, the result comes back."""
         import torch
 
@@ -1215,7 +1284,7 @@ class BDPTIntegrator:
                                          ctypes.c_uint64(mask), ctypes.c_void_p(out_ptr),
                                          ctypes.c_void_p(stream_ptr)))
 
-    def _group_map(self, group_of_emitter, n_groups):
+    def _group_map(self, group_of_emitter, n_groups, entry="render_light_groups"):
         """(int32 array or None, n_groups) as bdpt_render_light_groups takes them: no map is the
         identity, whose plane count defaults to the emitter count; with a map it defaults to
         max(map) + 1."""
@@ -1224,7 +1293,7 @@ class BDPTIntegrator:
             return None, n
         m = np.ascontiguousarray(group_of_emitter, np.int32).reshape(-1)
         if m.size != len(self.scene.emitters()):
-            raise BdptError(f"render_light_groups: group_of_emitter has {m.size} entries, the scene "
+            raise BdptError(f"{entry}: group_of_emitter has {m.size} entries, the scene "
                             f"{len(self.scene.emitters())} emitters")
         return m, (int(m.max()) + 1 if n_groups is None else int(n_groups))
 
@@ -1315,6 +1384,75 @@ class BDPTIntegrator:
         _check(lib().bdpt_strategies_sheet(self._h, ctypes.c_void_p(planes_ptr), int(n_s), int(n_t), int(width),
                                            int(height), None if g is None else g.ctypes.data,
                                            ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream_ptr)))
+
+    def render_group_layers(self, n_layers: int, group_of_emitter=None, n_groups: int | None = None,
+                            window: SampleWindow | None = None, row_offset: int = 0, row_stride: int = 1,
+                            flags: int = 0) -> np.ndarray:
+        """bdpt_render_group_layers_host: the BDPT frame split by emitter and by path length at once, a
+        new (n_groups, n_layers, H, W, 3) array. out[g, l] holds the contributions of the paths of l + 1
+        edges (the last layer: everything longer) that end on an emitter of group g; summed over l it is
+        render_light_groups(), summed over g render_layers(n_layers)."""
+        m, n = self._group_map(group_of_emitter, n_groups, "render_group_layers")
+        n_layers = int(n_layers)
+        return self._render_planes(lib().bdpt_render_group_layers_host, (None if m is None else m.ctypes.data, n, n_layers),
+                                   (n, n_layers), 1 <= n <= GROUPS_MAX and 1 <= n_layers <= LAYERS_MAX, window,
+                                   row_offset, row_stride, flags)
+
+    def render_group_layers_device(self, n_layers: int, fb_ptr: int, group_of_emitter=None, n_groups: int | None = None,
+                                   stream_ptr: int = 0, window: SampleWindow | None = None, row_offset: int = 0,
+                                   row_stride: int = 1) -> None:
+        """bdpt_render_group_layers: asynchronous, ADDED to a device buffer of n_groups * n_layers * H * W * 3 floats."""
+        m, n = self._group_map(group_of_emitter, n_groups, "render_group_layers")
+        self._render_planes(lib().bdpt_render_group_layers, (None if m is None else m.ctypes.data, n, int(n_layers)), None,
+                            True, window, row_offset, row_stride, 0, fb_ptr, stream_ptr)
+
+    def render_group_strategies(self, n_s: int | None = None, n_t: int | None = None, unweighted: bool = False,
+                                group_of_emitter=None, n_groups: int | None = None, window: SampleWindow | None = None,
+                                row_offset: int = 0, row_stride: int = 1, flags: int = 0) -> np.ndarray:
+        """bdpt_render_group_strategies_host: the BDPT frame split by emitter and by sampling strategy at
+        once, a new (n_groups, n_s, n_t, H, W, 3) array. out[g] is render_strategies(n_s, n_t, unweighted)
+        of the light that ends on group g's emitters; summed over g it is that render, summed over (s, t)
+        of a weighted render it is render_light_groups()."""
+        m, n = self._group_map(group_of_emitter, n_groups, "render_group_strategies")
+        n_s, n_t = self._strategies_shape(n_s, n_t)
+        return self._render_planes(lib().bdpt_render_group_strategies_host,
+                                   (None if m is None else m.ctypes.data, n, n_s, n_t, int(unweighted)), (n, n_s, n_t),
+                                   1 <= n <= GROUPS_MAX and 1 <= n_s <= STRATEGIES_MAX_S and 1 <= n_t <= STRATEGIES_MAX_T,
+                                   window, row_offset, row_stride, flags)
+
+    def render_group_strategies_device(self, fb_ptr: int, n_s: int | None = None, n_t: int | None = None,
+                                       unweighted: bool = False, group_of_emitter=None, n_groups: int | None = None,
+                                       stream_ptr: int = 0, window: SampleWindow | None = None, row_offset: int = 0,
+                                       row_stride: int = 1) -> None:
+        """bdpt_render_group_strategies: asynchronous, ADDED to a device buffer of n_groups * n_s * n_t * H * W * 3 floats."""
+        m, n = self._group_map(group_of_emitter, n_groups, "render_group_strategies")
+        n_s, n_t = self._strategies_shape(n_s, n_t)
+        self._render_planes(lib().bdpt_render_group_strategies,
+                            (None if m is None else m.ctypes.data, n, n_s, n_t, int(unweighted)), None, True, window,
+                            row_offset, row_stride, 0, fb_ptr, stream_ptr)
+
+    def combine_group_planes(self, planes, gains=None, weights=None) -> np.ndarray:
+        """bdpt_group_planes_combine on the device: the (H, W, 3) float32 frame sum_g sum_j gains[g] *
+        weights[j] * planes[g, j] of render_group_layers' or render_group_strategies' planes (gains:
+        (n_groups, 3) RGB or (n_groups,) grey; weights: the inner axes' shape or flat; None: ones). The
+        bits of combine_group_planes_numpy. The planes go to the device and the frame comes back."""
+        a, g, w = _group_planes_args(planes, gains, weights)
+        n, n_inner, H, W = a.shape[:4]
+        return self._combine(a, (H, W, 3),
+                             lambda d_in, d_out: self.combine_group_planes_device(d_in, n, n_inner, W, H, g, w, d_out))
+
+    def combine_group_planes_device(self, planes_ptr: int, n_groups: int, n_inner: int, width: int, height: int, gains,
+                                    weights, out_ptr: int, stream_ptr: int = 0) -> None:
+        """bdpt_group_planes_combine: asynchronous, on device buffers; gains: None or host n_groups x 3
+        float32, weights: None or host n_inner float32."""
+        g = None if gains is None else self._gains("combine_group_planes_device", gains, int(n_groups), n_groups)
+        w = None if weights is None else np.ascontiguousarray(weights, np.float32)
+        if w is not None and w.size != int(n_inner):
+            raise BdptError(f"combine_group_planes_device: weights must hold {n_inner} floats, got {w.size}")
+        _check(lib().bdpt_group_planes_combine(self._h, ctypes.c_void_p(planes_ptr), int(n_groups), int(n_inner),
+                                               int(width), int(height), None if g is None else g.ctypes.data,
+                                               None if w is None else w.ctypes.data, ctypes.c_void_p(out_ptr),
+                                               ctypes.c_void_p(stream_ptr)))
 
     def denoise(self, rgb=None, aov=None, samples_done: int | None = None, **params) -> np.ndarray:
         """bdpt_denoise_host of rgb (default self.rgb) guided by aov (default self.aov): a new

@@ -237,6 +237,58 @@ __global__ __launch_bounds__(256) void relight_kernel(const float* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------ crossed planes
+// The two-axis form of the relight kernel and the layer compose (bdpt_render_group_layers /
+// bdpt_render_group_strategies: n_groups * n_inner planes of n = W * H * 3 floats, plane
+// g * n_inner + j). With acc the first term, for g ascending and within it j ascending:
+//   t = weights[j] * plane[g * n_inner + j][p][c];  t = gains[g][c] * t;  acc = acc + t
+// float32, each of the three operations rounded on its own (the build's -ffp-contract=off),
+// every plane multiplied whatever its gain or weight, no atomics: the same bits every run and
+// the bits of that loop on the host. The gains are a kernel argument as in relight_kernel;
+// weights is a device table of n_inner floats (wave-uniform reads). Lanes and UNIT as there.
+template <int UNIT>
+__global__ __launch_bounds__(256) void group_planes_combine_kernel(const float* __restrict__ planes, size_t n,
+                                                                   int n_groups, int n_inner, RelightGains gains,
+                                                                   const float* __restrict__ weights,
+                                                                   float* __restrict__ out) {
+    constexpr int kF = 3 * UNIT;  // floats per lane and step
+    const size_t units = n / kF;
+    for (size_t u = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; u < units; u += static_cast<size_t>(gridDim.x) * 256) {
+        float acc[kF];
+        for (int g = 0; g < n_groups; g++) {  // (wave-uniform, as the inner loop)
+            for (int i = 0; i < n_inner; i++) {
+                const float* src = planes + (static_cast<size_t>(g) * n_inner + i) * n + u * kF;
+                const float w = weights[i];
+                float v[kF];
+                if (UNIT == 4) {
+#pragma unroll
+                    for (int q = 0; q < 3; q++) {
+                        const float4 t = gld4(reinterpret_cast<const float4*>(src) + q);
+                        v[4 * q] = t.x, v[4 * q + 1] = t.y, v[4 * q + 2] = t.z, v[4 * q + 3] = t.w;
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < kF; j++) v[j] = gld1(src + j);
+                }
+#pragma unroll
+                for (int j = 0; j < kF; j++) {
+                    const float t = gains.g[g][j % 3] * (w * v[j]);
+                    acc[j] = (g | i) == 0 ? t : acc[j] + t;
+                }
+            }
+        }
+        float* dst = out + u * kF;
+        if (UNIT == 4) {
+#pragma unroll
+            for (int q = 0; q < 3; q++)
+                gst4(reinterpret_cast<float4*>(dst) + q, make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]));
+        } else {
+#pragma unroll
+            for (int j = 0; j < kF; j++) gst1(dst + j, acc[j]);
+        }
+    }
+}
+
 // ------------------------------------------------------------ strategy images
 // The contact sheet of a strategy render (bdpt_render_strategies: n_s * n_t planes of W x H x 3
 // floats, plane s * n_t + t - 1): one image of n_s columns by n_t rows of W x H tiles, the tile
@@ -285,6 +337,24 @@ hipError_t launch_relight(const float* planes, size_t n, int n_groups, const flo
     const unsigned blocks = static_cast<unsigned>(std::min<size_t>((units + 255) / 256, 4096));
     if (vec) hipLaunchKernelGGL(dev::relight_kernel<4>, dim3(blocks), dim3(256), 0, st, planes, n, n_groups, k, out);
     else hipLaunchKernelGGL(dev::relight_kernel<1>, dim3(blocks), dim3(256), 0, st, planes, n, n_groups, k, out);
+    return hipGetLastError();
+}
+
+// gains: n_groups x 3 floats (host); weights: a device table of n_inner floats. n is a multiple of 3.
+hipError_t launch_group_planes_combine(const float* planes, size_t n, int n_groups, int n_inner, const float* gains,
+                                       const float* weights, float* out, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    dev::RelightGains k{};
+    std::memcpy(k.g, gains, sizeof(float) * 3 * static_cast<size_t>(n_groups));
+    const bool vec = n % 12 == 0 && (reinterpret_cast<uintptr_t>(planes) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
+    const size_t units = n / (vec ? 12 : 3);
+    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((units + 255) / 256, 4096));
+    if (vec)
+        hipLaunchKernelGGL(dev::group_planes_combine_kernel<4>, dim3(blocks), dim3(256), 0, st, planes, n, n_groups,
+                           n_inner, k, weights, out);
+    else
+        hipLaunchKernelGGL(dev::group_planes_combine_kernel<1>, dim3(blocks), dim3(256), 0, st, planes, n, n_groups,
+                           n_inner, k, weights, out);
     return hipGetLastError();
 }
 

@@ -22,7 +22,8 @@
 namespace bdpt {
 // The builds of the BDPT frame kernel (bdpt_kernels_<x>.hip; FrameBuild: bdpt_device.hpp)
 extern FrameBuild frame_build, frame_build_tex, frame_build_rr, frame_build_rrc, frame_build_deep,
-    frame_build_hbm, frame_build_split, frame_build_ng, frame_build_layers, frame_build_groups, frame_build_strat, frame_build_strat_unweighted;
+    frame_build_hbm, frame_build_split, frame_build_ng, frame_build_layers, frame_build_groups, frame_build_strat, frame_build_strat_unweighted,
+    frame_build_groups_layers, frame_build_groups_strat, frame_build_groups_strat_unweighted;
 // sample_state.hip: the single-sample kernels (the caller's std::mt19937 state at sc.mt_ring)
 hipError_t launch_sample(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf, uint2* gstack,
                          const dev::Ray& ray, float* out, hipStream_t stream);
@@ -75,6 +76,10 @@ hipError_t launch_denoise_iter(int W, int H, int step, float inv_c, float inv_n,
 hipError_t launch_layers_compose(const float* layers, size_t n, uint64_t mask, float* out, hipStream_t st);
 // aov_kernels.hip: light-group planes (n floats each) recombined with per-group RGB gains (host, n_groups x 3)
 hipError_t launch_relight(const float* planes, size_t n, int n_groups, const float* gains, float* out, hipStream_t st);
+// aov_kernels.hip: n_groups * n_inner crossed planes (n floats each) recombined with per-group RGB gains (host,
+// n_groups x 3) and per-inner-plane weights (a device table of n_inner floats)
+hipError_t launch_group_planes_combine(const float* planes, size_t n, int n_groups, int n_inner, const float* gains,
+                                       const float* weights, float* out, hipStream_t st);
 // aov_kernels.hip: the contact sheet of n_s x n_t strategy planes (gains: a device table of n_s * n_t x 3 floats, or null)
 hipError_t launch_strategies_sheet(const float* planes, int n_s, int n_t, int W, int H, const float* gains, float* out,
                                    hipStream_t st);
@@ -390,9 +395,10 @@ static int stage_host(bdpt_ctx* c, float* host, size_t n, Run run) {
 }
 
 // The device part of a combine entry (bdpt_layers_compose, bdpt_light_groups_relight,
-// bdpt_strategies_sheet) once its arguments are accepted: one launch on the call's stream, timed
-// as a call of its own. table (null: none): the sheet's ntable gains, which reach the device in
-// stream order from the context's own host copy; launch(device table or null, stream).
+// bdpt_strategies_sheet, bdpt_group_planes_combine) once its arguments are accepted: one launch on
+// the call's stream, timed as a call of its own. table (null: none): the sheet's ntable gains or the
+// crossed combine's ntable weights, which reach the device in stream order from the context's own
+// host copy; launch(device table or null, stream).
 template <class Launch>
 static int combine_planes(bdpt_ctx* c, void* hip_stream, const float* table, size_t ntable, Launch launch) {
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
@@ -1130,16 +1136,33 @@ struct PlaneKind {
     int max;                      // the most planes
     const char* phrase;           // "<phrase> are not built <with what>"
     const FrameBuild* build[2];   // the builds, by Planes::weighting (one build: twice)
-    bool shaped;                  // the count is an (n_s, n_t) shape with a weighting
+    bool shaped;                  // an (n_s, n_t) shape with a weighting comes with the call
     bool mapped;                  // a map from emitters to planes comes with the call
+    // a crossed kind: count and max are its outer axis, the groups', and each group
+    // holds the planes of this kind, whose count's name, limit or shape the inner axis takes
+    const PlaneKind* inner;
 };
 static const PlaneKind kLayerPlanes = {"bdpt_render_layers", "n_layers", kMaxLayers, "path-length layers",
-                                       {&frame_build_layers, &frame_build_layers}, false, false};
+                                       {&frame_build_layers, &frame_build_layers}, false, false, nullptr};
 static const PlaneKind kGroupPlanes = {"bdpt_render_light_groups", "n_groups", kMaxGroups, "light groups",
-                                       {&frame_build_groups, &frame_build_groups}, false, true};
+                                       {&frame_build_groups, &frame_build_groups}, false, true, nullptr};
 static const PlaneKind kStrategyPlanes = {"bdpt_render_strategies", "n_s * n_t", kMaxStratS * kMaxStratT,
                                           "strategies (per-(s, t) images)",
-                                          {&frame_build_strat, &frame_build_strat_unweighted}, true, false};
+                                          {&frame_build_strat, &frame_build_strat_unweighted}, true, false, nullptr};
+static const PlaneKind kGroupLayerPlanes = {"bdpt_render_group_layers", "n_groups", kMaxGroups, "light groups x layers",
+                                            {&frame_build_groups_layers, &frame_build_groups_layers}, false, true,
+                                            &kLayerPlanes};
+static const PlaneKind kGroupStrategyPlanes = {"bdpt_render_group_strategies", "n_groups", kMaxGroups,
+                                               "light groups x strategies",
+                                               {&frame_build_groups_strat, &frame_build_groups_strat_unweighted}, true, true,
+                                               &kStrategyPlanes};
+// what bdpt_group_planes_combine takes: the planes of either crossed kind (n_inner up to the larger limit)
+static const PlaneKind kAnyInnerPlanes = {nullptr, "n_inner", std::max(kMaxLayers, kMaxStratS * kMaxStratT), "", {}, false, false, nullptr};
+static const PlaneKind kCrossedPlanes = {"bdpt_group_planes_combine", "n_groups", kMaxGroups, "", {}, false, true, &kAnyInnerPlanes};
+// the name of a kind's whole plane count
+static std::string planes_name(const PlaneKind& k) {
+    return k.inner ? std::string(k.count) + " * " + k.inner->count : std::string(k.count);
+}
 
 static int check_strategy_shape(const std::string& entry, int32_t n_s, int32_t n_t) {
     if (n_s < 1 || n_s > kMaxStratS) return fail(BDPT_ERR_INVALID, entry + "n_s" + in_range(kMaxStratS));
@@ -1153,23 +1176,39 @@ static bool strategy_shape_ok(int32_t n_s, int32_t n_t) {
 // One call's planes: its kind (null: the plain frame) and what came with the call.
 struct Planes {
     const PlaneKind* kind = nullptr;
-    int n = 1;                                  // planes in the framebuffer
+    int n = 1;                                  // planes along the kind's own axis (a crossed kind: groups)
     const int32_t* group_of_emitter = nullptr;  // mapped kinds: the caller's host map (null: identity)
-    int n_s = 0, n_t = 0, weighting = 0;        // shaped kinds: n = n_s * n_t, BDPT_STRATEGIES_*
+    int n_s = 0, n_t = 0, weighting = 0;        // shaped kinds: n_s * n_t planes, BDPT_STRATEGIES_*
+    int n_inner = 1;                            // crossed kinds: planes per group (n_layers, n_s * n_t)
 
+    // planes in the framebuffer (sized by it only after check_planes has accepted the counts)
+    size_t planes() const { return static_cast<size_t>(n) * n_inner; }
     const FrameBuild& build() const { return *kind->build[weighting == BDPT_STRATEGIES_UNWEIGHTED]; }
-    // the kind's DevFrame words (emitter_group: the context's table, uploaded for this call)
+    // the kind's DevFrame words (emitter_group: the context's table, uploaded for this call); the
+    // map's word and the count's or shape's lie in different unions, so a crossed kind sets both
     void fill(dev::DevFrame& fr, const int32_t* emitter_group) const {
+        if (kind->mapped) fr.emitter_group = emitter_group;
         if (kind->shaped) fr.strat_shape = n_s << 8 | n_t;  // (shares n_layers' word)
-        else if (kind->mapped) fr.emitter_group = emitter_group;
-        else fr.n_layers = n;
+        else if (kind->inner) fr.n_layers = n_inner;
+        else if (!kind->mapped) fr.n_layers = n;
     }
 };
+// (a shape check_planes refuses keeps one plane: nothing is sized by it)
+static int strategy_plane_count(int32_t n_s, int32_t n_t) { return strategy_shape_ok(n_s, n_t) ? n_s * n_t : 1; }
 static Planes strategy_planes(int32_t n_s, int32_t n_t, int32_t weighting) {
-    Planes pl{&kStrategyPlanes};
+    Planes pl{&kStrategyPlanes, strategy_plane_count(n_s, n_t)};
     pl.n_s = n_s, pl.n_t = n_t, pl.weighting = weighting;
-    // (a shape check_planes refuses keeps n = 1: nothing is sized by it)
-    if (strategy_shape_ok(n_s, n_t)) pl.n = n_s * n_t;
+    return pl;
+}
+static Planes group_layer_planes(const int32_t* group_of_emitter, int32_t n_groups, int32_t n_layers) {
+    Planes pl{&kGroupLayerPlanes, n_groups, group_of_emitter};
+    pl.n_inner = n_layers;
+    return pl;
+}
+static Planes group_strategy_planes(const int32_t* group_of_emitter, int32_t n_groups, int32_t n_s, int32_t n_t,
+                                    int32_t weighting) {
+    Planes pl{&kGroupStrategyPlanes, n_groups, group_of_emitter};
+    pl.n_s = n_s, pl.n_t = n_t, pl.weighting = weighting, pl.n_inner = strategy_plane_count(n_s, n_t);
     return pl;
 }
 
@@ -1178,16 +1217,19 @@ static Planes strategy_planes(int32_t n_s, int32_t n_t, int32_t weighting) {
 static int check_planes(const bdpt_ctx* c, const bdpt_frame_params* p, const Planes& pl) {
     const PlaneKind& k = *pl.kind;
     const std::string entry = std::string(k.entry) + ": ";
+    // the kind's own axis is a count unless it is the shape; then the shape, or the inner axis's count
+    if ((!k.shaped || k.inner) && (pl.n < 1 || pl.n > k.max))
+        return fail(BDPT_ERR_INVALID, entry + k.count + in_range(k.max));
     if (k.shaped) {
         if (int rc = check_strategy_shape(entry, pl.n_s, pl.n_t)) return rc;
         if (pl.weighting != BDPT_STRATEGIES_WEIGHTED && pl.weighting != BDPT_STRATEGIES_UNWEIGHTED)
             return fail(BDPT_ERR_INVALID, entry + "weighting must be BDPT_STRATEGIES_WEIGHTED (0) or "
                                                   "BDPT_STRATEGIES_UNWEIGHTED (1)");
-    } else if (pl.n < 1 || pl.n > k.max) {
-        return fail(BDPT_ERR_INVALID, entry + k.count + in_range(k.max));
+    } else if (k.inner && (pl.n_inner < 1 || pl.n_inner > k.inner->max)) {
+        return fail(BDPT_ERR_INVALID, entry + k.inner->count + in_range(k.inner->max));
     }
-    if (static_cast<int64_t>(pl.n) * p->width * p->height >= kMaxPlanePixels)
-        return fail(BDPT_ERR_INVALID, entry + k.count + " * W * H must be " + kBelowPlanePixels +
+    if (static_cast<int64_t>(pl.planes()) * p->width * p->height >= kMaxPlanePixels)
+        return fail(BDPT_ERR_INVALID, entry + planes_name(k) + " * W * H must be " + kBelowPlanePixels +
                                           " (the shadow-ray task record's pixel field)");
     if (k.mapped) {
         const int nemit = c->sc.nemit;
@@ -1212,7 +1254,7 @@ static int check_planes(const bdpt_ctx* c, const bdpt_frame_params* p, const Pla
 }
 
 // bdpt_render and the BDPT form of bdpt_render_window (w null: every sample); with planes:
-// the plane kinds' render entries (fb is pl.n planes, the kind's build; check_planes refuses
+// the plane kinds' render entries (fb is pl.planes() planes, the kind's build; check_planes refuses
 // what it does not serve).
 static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, float* fb,
                        void* hip_stream, const Planes& pl = Planes{}) {
@@ -1347,6 +1389,19 @@ int bdpt_render_strategies(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_s
     return render_bdpt(c, p, w, fb_planes, hip_stream, strategy_planes(n_s, n_t, weighting));
 }
 
+int bdpt_render_group_layers(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                             const int32_t* group_of_emitter, int32_t n_groups, int32_t n_layers, float* fb_planes,
+                             void* hip_stream) {
+    return render_bdpt(c, p, w, fb_planes, hip_stream, group_layer_planes(group_of_emitter, n_groups, n_layers));
+}
+
+int bdpt_render_group_strategies(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                                 const int32_t* group_of_emitter, int32_t n_groups, int32_t n_s, int32_t n_t,
+                                 int32_t weighting, float* fb_planes, void* hip_stream) {
+    return render_bdpt(c, p, w, fb_planes, hip_stream,
+                       group_strategy_planes(group_of_emitter, n_groups, n_s, n_t, weighting));
+}
+
 int bdpt_strategies_shape(int32_t rr_depth, int32_t strategy, int32_t* n_s, int32_t* n_t) {
     if (!n_s || !n_t) return fail(BDPT_ERR_INVALID, "null argument");
     if (rr_depth < 1 || rr_depth > kLazyRrDepth)
@@ -1373,12 +1428,16 @@ static bool overlap(const float* a, size_t a_floats, const float* b, size_t b_fl
     const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
     return pb < pa + a_floats * sizeof(float) && pa < pb + b_floats * sizeof(float);
 }
-// n planes of kind k (its count's name and limit) combined into one width x height frame
-static int check_combine_shape(const char* entry, const PlaneKind& k, int32_t n, int32_t width, int32_t height) {
+// n planes of kind k (its count's name and limit; a crossed kind: n groups of n_inner planes)
+// combined into one width x height frame
+static int check_combine_shape(const char* entry, const PlaneKind& k, int32_t n, int32_t width, int32_t height,
+                               int32_t n_inner = 1) {
     if (n < 1 || n > k.max) return fail(BDPT_ERR_INVALID, std::string(entry) + ": " + k.count + in_range(k.max));
-    if (width <= 0 || height <= 0 || static_cast<int64_t>(n) * width * height >= kMaxPlanePixels)
-        return fail(BDPT_ERR_INVALID, std::string(entry) + ": width/height must be > 0 and " + k.count + " * W * H " +
-                                          kBelowPlanePixels);
+    if (k.inner && (n_inner < 1 || n_inner > k.inner->max))
+        return fail(BDPT_ERR_INVALID, std::string(entry) + ": " + k.inner->count + in_range(k.inner->max));
+    if (width <= 0 || height <= 0 || static_cast<int64_t>(n) * n_inner * width * height >= kMaxPlanePixels)
+        return fail(BDPT_ERR_INVALID, std::string(entry) + ": width/height must be > 0 and " + planes_name(k) +
+                                          " * W * H " + kBelowPlanePixels);
     return BDPT_OK;
 }
 
@@ -1408,6 +1467,26 @@ int bdpt_light_groups_relight(bdpt_ctx* c, const float* fb_groups, int32_t n_gro
     if (overlap(fb_groups, n * n_groups, out, n)) return fail(BDPT_ERR_INVALID, std::string(entry) + ": out overlaps the planes");
     return combine_planes(c, hip_stream, nullptr, 0, [&](const float*, hipStream_t st) {  // (the gains are a kernel argument)
         return launch_relight(fb_groups, n, n_groups, gains, out, st);
+    });
+}
+
+int bdpt_group_planes_combine(bdpt_ctx* c, const float* planes, int32_t n_groups, int32_t n_inner, int32_t width,
+                              int32_t height, const float* gains, const float* weights, float* out, void* hip_stream) {
+    const char* const entry = kCrossedPlanes.entry;
+    if (!c || !planes || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    if (int rc = check_combine_shape(entry, kCrossedPlanes, n_groups, width, height, n_inner)) return rc;
+    if (int rc = check_gains_finite(entry, gains, n_groups)) return rc;
+    for (int j = 0; weights && j < n_inner; j++)
+        if (!std::isfinite(weights[j]))
+            return fail(BDPT_ERR_INVALID, std::string(entry) + ": weights[" + std::to_string(j) + "] is not finite");
+    const size_t n = static_cast<size_t>(width) * height * 3;
+    if (overlap(planes, n * n_groups * n_inner, out, n))
+        return fail(BDPT_ERR_INVALID, std::string(entry) + ": out overlaps the planes");
+    // null gains and weights are ones: the kernel multiplies by them like any other (x * 1 is x)
+    const std::vector<float> ones(std::max<size_t>(3 * static_cast<size_t>(n_groups), n_inner), 1.f);
+    const float* const g = gains ? gains : ones.data();
+    return combine_planes(c, hip_stream, weights ? weights : ones.data(), n_inner, [&](const float* dweights, hipStream_t st) {
+        return launch_group_planes_combine(planes, n, n_groups, n_inner, g, dweights, out, st);
     });
 }
 
@@ -1814,7 +1893,7 @@ static int render_bdpt_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_
     if (rc) return rc;
     if ((rc = check_window(p, w))) return rc;
     if (pl.kind && (rc = check_planes(c, p, pl))) return rc;  // before the planes are staged
-    if ((rc = stage_host(c, fb_host, static_cast<size_t>(p->width) * p->height * 3 * pl.n,
+    if ((rc = stage_host(c, fb_host, static_cast<size_t>(p->width) * p->height * 3 * pl.planes(),
                          [&](float* fb) { return render_bdpt(c, p, w, fb, c->stream, pl); })))
         return rc;
     {
@@ -1857,6 +1936,38 @@ int bdpt_strategies_sheet_host(bdpt_ctx* c, const float* planes, int32_t n_s, in
     HIP_TRY(hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BDPT_OK;
+}
+
+// both arrays staged in tmp_fb, as bdpt_strategies_sheet_host stages its two
+int bdpt_group_planes_combine_host(bdpt_ctx* c, const float* planes, int32_t n_groups, int32_t n_inner, int32_t width,
+                                   int32_t height, const float* gains, const float* weights, float* out) {
+    if (!c || !planes || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    // a shape the device form refuses: refused by it (its first checks, which read no pointer) before anything is staged
+    if (check_combine_shape(kCrossedPlanes.entry, kCrossedPlanes, n_groups, width, height, n_inner))
+        return bdpt_group_planes_combine(c, planes, n_groups, n_inner, width, height, gains, weights, out, c->stream);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = static_cast<size_t>(width) * height * 3, nin = n * n_groups * n_inner;
+    HIP_TRY(c->tmp_fb.reserve((nin + n) * sizeof(float)));
+    float *din = c->tmp_fb, *dout = c->tmp_fb + nin;
+    HIP_TRY(hipMemcpyAsync(din, planes, nin * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (int rc = bdpt_group_planes_combine(c, din, n_groups, n_inner, width, height, gains, weights, dout, c->stream))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+int bdpt_render_group_layers_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                                  const int32_t* group_of_emitter, int32_t n_groups, int32_t n_layers,
+                                  float* fb_planes_host) {
+    return render_bdpt_host(c, p, w, fb_planes_host, group_layer_planes(group_of_emitter, n_groups, n_layers));
+}
+
+int bdpt_render_group_strategies_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w,
+                                      const int32_t* group_of_emitter, int32_t n_groups, int32_t n_s, int32_t n_t,
+                                      int32_t weighting, float* fb_planes_host) {
+    return render_bdpt_host(c, p, w, fb_planes_host,
+                            group_strategy_planes(group_of_emitter, n_groups, n_s, n_t, weighting));
 }
 
 int bdpt_render_strategies_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, int32_t n_s,

@@ -107,9 +107,10 @@ __device__ __forceinline__ float rr_probability(const DevFrame& fr, int depth, f
 #define BDPT_UNWEIGHTED 0
 #endif
 #define BDPT_PLANES (BDPT_LAYERS || BDPT_GROUPS || BDPT_STRATS)  // the framebuffer is several planes; no per-sample sum
+#define BDPT_CROSSED (BDPT_GROUPS && (BDPT_LAYERS || BDPT_STRATS))  // a plane per (group, layer) or (group, s, t)
 #if BDPT_PLANES
-#if BDPT_RR || (defined(BDPT_SAMPLER_STATE) && BDPT_SAMPLER_STATE) || (BDPT_LAYERS + BDPT_GROUPS + BDPT_STRATS != 1)
-#error "BDPT_LAYERS / BDPT_GROUPS / BDPT_STRATS: one of them, in the frame kernel without Russian roulette only"
+#if BDPT_RR || (defined(BDPT_SAMPLER_STATE) && BDPT_SAMPLER_STATE) || (BDPT_LAYERS && BDPT_STRATS)
+#error "BDPT_LAYERS / BDPT_GROUPS / BDPT_STRATS: one of them, or the groups with one of the others, in the frame kernel without Russian roulette only"
 #endif
 #endif
 #if BDPT_UNWEIGHTED && !BDPT_STRATS
@@ -120,15 +121,24 @@ __device__ __forceinline__ float mis_factor(float mis) { return BDPT_UNWEIGHTED 
 // BDPT_PLANE_PX(fr, k, g, s, pixel): the index a contribution of a k-edge path lit by group g and
 // formed with s light-subpath vertices is added at (each build reads what it files by; the plain
 // builds nothing).
-// BDPT_LV_TAG(rr, depth, g): a stored light vertex's rr word.
+// BDPT_LV_TAG(rr, depth, g): a stored light vertex's rr word; BDPT_LV_DEPTH(rr) / BDPT_LV_GROUP(rr)
+// read it back at the connections (a build that files by one of the two stores that one as the
+// whole word; its other reader feeds a BDPT_PLANE_PX argument that build ignores).
+//
+// Crossed planes (BDPT_GROUPS with BDPT_LAYERS or BDPT_STRATS: bdpt_kernels_groups_layers.hip,
+// bdpt_kernels_groups_strat*.hip): the group is the outer axis, plane = g * n_inner +
+// inner with inner and n_inner the layer or strategy build's own (layer_plane / strat_plane, same
+// clamps). Both DevFrame words are set (emitter_group and n_layers / strat_shape lie in different
+// unions), and a stored light vertex carries its depth and its subpath's group together
+// (lv_tag: depth <= 28 in bits 0..7, g < 64 above).
 #if BDPT_LAYERS
+__device__ __forceinline__ int layer_plane(const DevFrame& fr, int k) { return max(0, min(k - 1, fr.n_layers - 1)); }
 __device__ __forceinline__ int layer_index(const DevFrame& fr, int k, int pixel) {
-    const int plane = max(0, min(k - 1, fr.n_layers - 1));
+    const int plane = layer_plane(fr, k);
     return plane * (fr.W * fr.H) + pixel;  // < 2^30 (bdpt_render_layers checks n_layers * W * H)
 }
-#define BDPT_PLANE_PX(fr, k, g, s, pixel) layer_index(fr, k, pixel)
-#define BDPT_LV_TAG(rr, depth, g) __int_as_float(depth)
-#elif BDPT_GROUPS
+#endif
+#if BDPT_GROUPS
 // emitter_group holds one entry in [0, n_groups) per emitter (bdpt_render_light_groups checks);
 // a hit shape that is no emitter (e < 0: its contribution is zero) reads nothing.
 __device__ __forceinline__ int group_of_emitter(const DevFrame& fr, int e) {
@@ -141,22 +151,53 @@ __device__ __forceinline__ int prim_emitter(const DevScene& sc, int tri) {
 __device__ __forceinline__ int group_index(const DevFrame& fr, int g, int pixel) {
     return g * (fr.W * fr.H) + pixel;  // < 2^30 (bdpt_render_light_groups checks n_groups * W * H)
 }
-#define BDPT_PLANE_PX(fr, k, g, s, pixel) group_index(fr, g, pixel)
-#define BDPT_LV_TAG(rr, depth, g) __int_as_float(g)
 #define BDPT_GROUP_OF(fr, e) group_of_emitter(fr, e)
 #define BDPT_LIGHT_GROUP(L) static_cast<int>((L).c.pure)  // the light subpath's group, during its walk
-#elif BDPT_STRATS
+#endif
+#if BDPT_STRATS
 // strat_shape = n_s << 8 | n_t (bdpt_render_strategies checks n_s <= 29, n_t <= 28); s >= 0, t >= 1
-__device__ __forceinline__ int strat_index(const DevFrame& fr, int s, int t, int pixel) {
+__device__ __forceinline__ int strat_planes(const DevFrame& fr) { return (fr.strat_shape >> 8) * (fr.strat_shape & 0xff); }
+__device__ __forceinline__ int strat_plane(const DevFrame& fr, int s, int t) {
     const int n_s = fr.strat_shape >> 8, n_t = fr.strat_shape & 0xff;
-    const int plane = min(s, n_s - 1) * n_t + (max(1, min(t, n_t)) - 1);
+    return min(s, n_s - 1) * n_t + (max(1, min(t, n_t)) - 1);
+}
+__device__ __forceinline__ int strat_index(const DevFrame& fr, int s, int t, int pixel) {
+    const int plane = strat_plane(fr, s, t);
     return plane * (fr.W * fr.H) + pixel;  // < 2^30 (bdpt_render_strategies checks n_s * n_t * W * H)
 }
+#endif
+#if BDPT_CROSSED
+// < 2^30 (bdpt_render_group_layers / bdpt_render_group_strategies check n_groups * n_inner * W * H)
+__device__ __forceinline__ int crossed_index(const DevFrame& fr, int g, int n_inner, int inner, int pixel) {
+    return (g * n_inner + inner) * (fr.W * fr.H) + pixel;
+}
+__device__ __forceinline__ float lv_tag(int depth, int g) { return __int_as_float(depth | g << 8); }
+__device__ __forceinline__ int lv_tag_depth(float rr) { return __float_as_int(rr) & 0xff; }
+__device__ __forceinline__ int lv_tag_group(float rr) { return __float_as_int(rr) >> 8; }
+#if BDPT_LAYERS
+#define BDPT_PLANE_PX(fr, k, g, s, pixel) crossed_index(fr, g, (fr).n_layers, layer_plane(fr, k), pixel)
+#else
+#define BDPT_PLANE_PX(fr, k, g, s, pixel) crossed_index(fr, g, strat_planes(fr), strat_plane(fr, s, (k) + 1 - (s)), pixel)
+#endif
+#define BDPT_LV_TAG(rr, depth, g) lv_tag(depth, g)
+#define BDPT_LV_DEPTH(rr) lv_tag_depth(rr)
+#define BDPT_LV_GROUP(rr) lv_tag_group(rr)
+#else
+#define BDPT_LV_DEPTH(rr) __float_as_int(rr)
+#define BDPT_LV_GROUP(rr) __float_as_int(rr)
+#if BDPT_LAYERS
+#define BDPT_PLANE_PX(fr, k, g, s, pixel) layer_index(fr, k, pixel)
+#define BDPT_LV_TAG(rr, depth, g) __int_as_float(depth)
+#elif BDPT_GROUPS
+#define BDPT_PLANE_PX(fr, k, g, s, pixel) group_index(fr, g, pixel)
+#define BDPT_LV_TAG(rr, depth, g) __int_as_float(g)
+#elif BDPT_STRATS
 #define BDPT_PLANE_PX(fr, k, g, s, pixel) strat_index(fr, s, (k) + 1 - (s), pixel)
 #define BDPT_LV_TAG(rr, depth, g) __int_as_float(depth)
 #else
 #define BDPT_PLANE_PX(fr, k, g, s, pixel) (pixel)
 #define BDPT_LV_TAG(rr, depth, g) (rr)
+#endif
 #endif
 
 // Light-vertex scratch, one contiguous record per lane: vertex v of slot s is
@@ -515,7 +556,7 @@ __device__ __forceinline__ bool task_push(const LaneCold&, const DevFrame&, f3, 
 constexpr bool kTasks = BDPT_HELP && !BDPT_SAMPLER_STATE;
 
 // An eye-estimate addition for the pixel: the wave's slot when it holds the pixel, else the framebuffer.
-// BDPT_PLANES: `pixel` is a plane index (layer_index / group_index / strat_index). A plane-0 index equals the plain pixel
+// BDPT_PLANES: `pixel` is a plane index (layer_index / group_index / strat_index / crossed_index). A plane-0 index equals the plain pixel
 // and uses the slot as before (the slot's flush, eye_slot_reset, writes plane 0); an index of
 // another plane matches no slot (slots hold pixels < W * H) and goes to the framebuffer.
 __device__ __forceinline__ void eye_add(float* __restrict__ fb, int pixel, f3 add) {
@@ -941,8 +982,8 @@ __device__ uint32_t advance(Lane& L, uint32_t act, const DevScene& sc, const Dev
             const float eyeWeight = eyePathRev_a * (L.c.vcm + eyePrevRev * L.c.vc);
             const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
             const Ray sr = shadow_ray(L.h.p, V.p);
-            // s >= 2, t >= 2: k = depth_eye + depth_light + 1, s = depth_light + 1 (the stored vertex's depth or group: BDPT_LV_TAG)
-            const int px = BDPT_PLANE_PX(fr, L.c.depth + __float_as_int(V.rr) + 1, __float_as_int(V.rr), __float_as_int(V.rr) + 1, L.c.pixel);
+            // s >= 2, t >= 2: k = depth_eye + depth_light + 1, s = depth_light + 1 (the stored vertex's depth and group: BDPT_LV_TAG)
+            const int px = BDPT_PLANE_PX(fr, L.c.depth + BDPT_LV_DEPTH(V.rr) + 1, BDPT_LV_GROUP(V.rr), BDPT_LV_DEPTH(V.rr) + 1, L.c.pixel);
             if (kTasks && task_push(L.c, fr, L.h.p, V.p, vertex_nocull(L, sr.d), (Li * mis_factor(mis)) * fr.inv_spp, px, false, cnt)) {
                 L.c.ci++;  // a helper walks it; the next light vertex now
                 continue;
@@ -1056,7 +1097,7 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
         const float mis = rcp_w(lightWeight + 1.f + eyeWeight);
         const Ray sr = shadow_ray(hp, V.p);
         task_push(L.c, fr, hp, V.p, graze_exempt(sr.d, hn, hshape), (Li * mis_factor(mis)) * fr.inv_spp,
-                  BDPT_PLANE_PX(fr, oc.depth + __float_as_int(V.rr) + 1, __float_as_int(V.rr), __float_as_int(V.rr) + 1, oc.pixel), false, cnt);
+                  BDPT_PLANE_PX(fr, oc.depth + BDPT_LV_DEPTH(V.rr) + 1, BDPT_LV_GROUP(V.rr), BDPT_LV_DEPTH(V.rr) + 1, oc.pixel), false, cnt);
     }
     if (k > 0) L.c.ci = L.c.nl;
 }

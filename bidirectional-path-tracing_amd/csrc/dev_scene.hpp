@@ -208,7 +208,9 @@ struct DevFrame {
     // is n_groups consecutive W x H x 3 planes and a contribution goes to plane emitter_group[e]
     // of the emitter e its path ends on (one int32 per emitter, each in [0, n_groups)). It shares
     // row_cost's word, so the record and every other build's code stay as they were: a grouped
-    // render is never a counting pass (flags are refused) and no other build reads it.
+    // render is never a counting pass (flags are refused) and no other build reads it. The crossed
+    // builds (bdpt_kernels_groups_layers.hip, bdpt_kernels_groups_strat*.hip) read it together with
+    // n_layers / strat_shape below, which lie in another union: both are set in one launch.
     union {
         unsigned long long* row_cost;
         const int32_t* emitter_group;

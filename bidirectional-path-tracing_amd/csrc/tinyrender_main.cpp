@@ -38,6 +38,12 @@
 // A second render, so the main EXR is the same bytes with or without it. A bad value, a path / direct
 // scene or an rr_depth outside 1..28 is refused before any device is used; with several devices the
 // first renders the planes.
+// --cross (with --light-groups and exactly one of --layers N / --strategies[=unweighted]) writes the
+// product of the two splits instead of the two sets of files: <out stem>.E<ee>L<ll>.exr, a plane per
+// (emitter, layer) (bdpt_render_group_layers_host), or <out stem>.E<ee>S<ss>T<tt>.exr for every
+// (emitter, s, t) plane that is not all zero (bdpt_render_group_strategies_host; no contact sheet).
+// Without --cross the two flags keep writing their two independent sets. Refusals and devices as for
+// the single flags.
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
@@ -93,7 +99,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Syntax: %s <scene.toml> [nogui] [--width W --height H --spp N --rr D --device K "
                              "--out FILE.exr --seed S --gpus N --devices a,b,... --shard samples|rows "
-                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted]]\n", argv[0]);
+                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted] --cross]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string toml = argv[1];
@@ -109,6 +115,7 @@ int main(int argc, char** argv) {
     int layers = 0;  // --layers N (0: none)
     bool light_groups = false;  // --light-groups
     int strategies = -1;        // --strategies[=unweighted]: BDPT_STRATEGIES_* (-1: none)
+    bool cross = false;         // --cross: the groups crossed with the layers or the strategies
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -172,6 +179,8 @@ int main(int argc, char** argv) {
             layers = static_cast<int>(n);
         } else if (a == "--light-groups") {
             light_groups = true;
+        } else if (a == "--cross") {
+            cross = true;
         } else if (a == "--strategies" || a == "--strategies=weighted") {
             strategies = BDPT_STRATEGIES_WEIGHTED;
         } else if (a == "--strategies=unweighted") {
@@ -223,6 +232,10 @@ int main(int argc, char** argv) {
     const bool direct = std::strcmp(cfg.integrator, "direct") == 0;
     if (!path && !direct && std::strcmp(cfg.integrator, "bdpt") != 0) {
         std::fprintf(stderr, "integrator type \"%s\" is not part of the MI355X BDPT path\n", cfg.integrator);
+        return EXIT_FAILURE;
+    }
+    if (cross && (!light_groups || (layers != 0) == (strategies >= 0))) {
+        std::fprintf(stderr, "--cross takes --light-groups and exactly one of --layers N / --strategies[=unweighted]\n");
         return EXIT_FAILURE;
     }
     if (layers && (path || direct)) {
@@ -373,27 +386,46 @@ int main(int argc, char** argv) {
         if (pctx != ctx) bdpt_ctx_destroy(pctx);
         return EXIT_SUCCESS;
     };
-    auto numbered = [](const char* format, int a, int b = 0) {
-        char suffix[24];
-        std::snprintf(suffix, sizeof suffix, format, a, b);
+    auto numbered = [](const char* format, auto... v) {
+        char suffix[32];
+        std::snprintf(suffix, sizeof suffix, format, v...);
         return std::string(suffix);
     };
     auto nothing = [](bdpt_ctx*, const float*) { return EXIT_SUCCESS; };
-    if (layers) {
+    if (cross && layers) {  // group the outer axis, as the library lays the planes out
+        const int rc = write_planes(
+            "bdpt_ctx_create (light groups x layers)", "bdpt_render_group_layers_host",
+            static_cast<size_t>(n_emitters) * layers,
+            [&](bdpt_ctx* c, float* fb) { return bdpt_render_group_layers_host(c, &p, win, nullptr, n_emitters, layers, fb); },
+            [&](int k) { return numbered(".E%02dL%02d", k / layers, k % layers); }, false, nothing);
+        if (rc) return rc;
+    }
+    if (cross && strategies >= 0) {
+        const int n = n_s * n_t;
+        const int rc = write_planes(
+            "bdpt_ctx_create (light groups x strategies)", "bdpt_render_group_strategies_host",
+            static_cast<size_t>(n_emitters) * n,
+            [&](bdpt_ctx* c, float* fb) {
+                return bdpt_render_group_strategies_host(c, &p, win, nullptr, n_emitters, n_s, n_t, strategies, fb);
+            },
+            [&](int k) { return numbered(".E%02dS%02dT%02d", k / n, k % n / n_t, k % n_t + 1); }, true, nothing);
+        if (rc) return rc;
+    }
+    if (layers && !cross) {
         const int rc = write_planes(
             "bdpt_ctx_create (layers)", "bdpt_render_layers_host", layers,
             [&](bdpt_ctx* c, float* fb) { return bdpt_render_layers_host(c, &p, win, layers, fb); },
             [&](int l) { return numbered(".L%02d", l); }, false, nothing);
         if (rc) return rc;
     }
-    if (light_groups) {
+    if (light_groups && !cross) {
         const int rc = write_planes(
             "bdpt_ctx_create (light groups)", "bdpt_render_light_groups_host", n_emitters,
             [&](bdpt_ctx* c, float* fb) { return bdpt_render_light_groups_host(c, &p, win, n_emitters, nullptr, fb); },
             [&](int e) { return numbered(".E%02d", e); }, false, nothing);
         if (rc) return rc;
     }
-    if (strategies >= 0) {
+    if (strategies >= 0 && !cross) {
         const size_t n = static_cast<size_t>(n_s) * n_t;
         const int rc = write_planes(
             "bdpt_ctx_create (strategies)", "bdpt_render_strategies_host", n,

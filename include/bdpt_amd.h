@@ -625,6 +625,56 @@ int bdpt_strategies_sheet(bdpt_ctx* ctx, const float* planes_device, int32_t n_s
 int bdpt_strategies_sheet_host(bdpt_ctx* ctx, const float* planes_host, int32_t n_s, int32_t n_t, int32_t width,
                                int32_t height, const float* gains, float* out_host);
 
+/* ---- crossed planes: light groups x path-length layers, light groups x strategies ---- */
+/* (new) Not in the reference. One BDPT frame split along two of the axes above at once: a plane per
+ * (group, layer) or per (group, s, t). The group and layer planes of two renders are two marginals of
+ * the same contributions; these entries keep the joint, so one traced frame can be relit per lamp AND
+ * per bounce count (a lamp's indirect light only), or show which strategy carries which lamp's light.
+ * fb_planes is n_groups * n_inner consecutive width * height * 3 planes, the group the outer axis:
+ * plane g * n_inner + inner with n_inner = n_layers and inner as bdpt_render_layers files it, or
+ * n_inner = n_s * n_t and inner as bdpt_render_strategies files it (same clamps, same weighting).
+ * Summed over the inner axis the planes are bdpt_render_light_groups', summed over the groups the
+ * single-kind entry's (up to the order of the float additions). group_of_emitter as in
+ * bdpt_render_light_groups: a HOST array of one int32 per emitter, copied before the call returns,
+ * NULL = the identity. window NULL = the whole frame; row shards and bdpt_set_row_order as in bdpt_render.
+ * BDPT_ERR_INVALID (the message names the field): n_groups outside 1..64, n_layers outside 1..64, n_s
+ * outside 1..29, n_t outside 1..28, a weighting other than the two, n_groups * n_inner * width * height
+ * >= 2^30, a map entry outside [0, n_groups), a NULL map with n_groups other than the emitter count.
+ * BDPT_ERR_UNSUPPORTED (the message says "light groups x layers" / "light groups x strategies"),
+ * before any launch: flags != 0, Russian roulette, rr_depth > 28, a scene with bitmap textures, BSDF
+ * records in HBM. bdpt_last_kernel afterwards: "bdpt_frame_kernel_groups_layers",
+ * "bdpt_frame_kernel_groups_strat" or "bdpt_frame_kernel_groups_strat_unweighted". Asynchronous on
+ * `hip_stream` like bdpt_render; the host forms stage the caller's planes and are synchronous. */
+int bdpt_render_group_layers(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                             const int32_t* group_of_emitter, int32_t n_groups, int32_t n_layers,
+                             float* fb_planes_device, void* hip_stream);
+int bdpt_render_group_layers_host(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                                  const int32_t* group_of_emitter, int32_t n_groups, int32_t n_layers,
+                                  float* fb_planes_host);
+int bdpt_render_group_strategies(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                                 const int32_t* group_of_emitter, int32_t n_groups, int32_t n_s, int32_t n_t,
+                                 int32_t weighting, float* fb_planes_device, void* hip_stream);
+int bdpt_render_group_strategies_host(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                                      const int32_t* group_of_emitter, int32_t n_groups, int32_t n_s, int32_t n_t,
+                                      int32_t weighting, float* fb_planes_host);
+/* (new) The two-axis form of bdpt_light_groups_relight and bdpt_layers_compose. With acc the first
+ * term, for g ascending and within it j ascending:
+ *   t = weights[j] * plane[g * n_inner + j][p][c];  t = gains[g][c] * t;  acc = acc + t
+ * float32, each operation rounded on its own (no fma), every plane multiplied whatever its gain or
+ * weight, no atomics - the bits of that loop, the same every run. `gains` is a HOST array of
+ * n_groups x 3 floats (NULL: ones) and travels as a kernel argument; `weights` is a HOST array of n_inner
+ * floats (NULL: ones), copied before the call returns into a table the context owns. The planes and out
+ * are device pointers, out is width * height * 3 floats and must not overlap the planes.
+ * BDPT_ERR_INVALID: n_groups outside 1..64, n_inner outside 1..812 (29 * 28), n_groups * n_inner *
+ * width * height >= 2^30, overlap, a gain or weight that is not finite. Asynchronous on `hip_stream`;
+ * the host form stages both arrays and is synchronous. */
+int bdpt_group_planes_combine(bdpt_ctx* ctx, const float* planes_device, int32_t n_groups, int32_t n_inner,
+                              int32_t width, int32_t height, const float* gains, const float* weights,
+                              float* out_device, void* hip_stream);
+int bdpt_group_planes_combine_host(bdpt_ctx* ctx, const float* planes_host, int32_t n_groups, int32_t n_inner,
+                                   int32_t width, int32_t height, const float* gains, const float* weights,
+                                   float* out_host);
+
 /* ---- several HIP devices in one process ---- */
 /* The reference fans the offline loop out over host threads (parallel_for,
  * src/core/parallelfor.h:25-65, renderer.cpp:157); here every device gets one

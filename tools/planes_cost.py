@@ -1,4 +1,5 @@
-"""Cost of keeping a frame as planes: python tools/planes_cost.py layers | groups | strategies.
+"""Cost of keeping a frame as planes: python tools/planes_cost.py layers | groups | strategies |
+group-layers | group-strategies.
 Kernel time by HIP events (stats()["kernel_ms"]), 512^2 x 64, 2 warm-up + 7 alternating rounds per
 scene, medians; one JSON line per table.
   layers      Caustic: the plain frame vs n_layers 1 / 4 / 8 / 16, and composing 8 layers.
@@ -9,7 +10,13 @@ scene, medians; one JSON line per table.
               helper's full shape, and the contact sheet. Then, on scenes/kat/layers_open.obj
               (diffuse, no delta surface), the frame means of the unweighted planes (0, 3), (1, 2)
               and (2, 1) at a few spp: three unbiased estimators of one direct-light image
-              (printed, not compared)."""
+              (printed, not compared).
+  group-layers      Caustic (one emitter) and emit_edges (five): the plain frame, the grouped render,
+              16 layers and the crossed (group, layer) render at 16 layers; then the combine kernel
+              on the crossed planes just rendered.
+  group-strategies  The same two scenes: the plain frame, the grouped render, the weighted and
+              unweighted strategies at the shape helper's full shape, the crossed (group, s, t)
+              renders of both weightings, and the combine kernel on the crossed planes."""
 import json
 import os
 import statistics
@@ -145,8 +152,55 @@ def strategies():
     print(json.dumps({"layers_open_unweighted_k2_frame_means_rgb": rows}))
 
 
+def crossed(inner):
+    """inner(it) -> (planes per group, {label: single-kind call(fb)}, {label: crossed call(fb)}); one JSON line."""
+    out = {"frame": f"{W}x{H}x{SPP}", "rounds": ROUNDS}
+    res = torch.zeros(W * H * 3, dtype=torch.float32, device=DEV)
+    for name in ("caustic", "emit_edges"):
+        it = integrator(name)
+        n_groups = len(it.scene.emitters())
+        n_inner, single, cross = inner(it)
+        fb = torch.zeros(n_groups * n_inner * W * H * 3, dtype=torch.float32, device=DEV)
+        torch.cuda.synchronize()
+        calls = {"plain": lambda: it.render_device(fb.data_ptr()), "grouped": lambda: it.render_light_groups_device(fb.data_ptr())}
+        calls.update({k: (lambda f=f: f(fb.data_ptr())) for k, f in {**single, **cross}.items()})
+        gains = np.linspace(0.25, 4.0, 3 * n_groups, dtype=np.float32).reshape(n_groups, 3)
+        weights = np.linspace(0.5, 2.0, n_inner, dtype=np.float32)
+        calls["combine"] = lambda: it.combine_group_planes_device(fb.data_ptr(), n_groups, n_inner, W, H, gains, weights,
+                                                                  res.data_ptr())
+        series, kernels = alternate(it, calls)
+        med = {k: statistics.median(v) for k, v in series.items()}
+        parents = ["grouped"] + list(single)
+        out[name] = {"emitters": n_groups, "planes_per_group": n_inner, "kernels": kernels, "series_ms": rounded(series),
+                     "median_ms": {k: round(v, 3) for k, v in med.items()},
+                     "range_ms": {k: [round(min(v), 3), round(max(v), 3)] for k, v in series.items()},
+                     "ratio_vs_plain": {k: round(med[k] / med["plain"], 4) for k in parents + list(cross)},
+                     "crossed_over_dearer_parent": {k: round(med[k] / max(med[q] for q in parents), 4) for k in cross},
+                     "combine_bytes": (n_groups * n_inner + 1) * W * H * 3 * 4}
+        del fb
+    print(json.dumps(out))
+
+
+def group_layers():
+    n = 16
+    crossed(lambda it: (n, {f"layers{n}": lambda fb: it.render_layers_device(n, fb)},
+                        {"crossed": lambda fb: it.render_group_layers_device(n, fb)}))
+
+
+def group_strategies():
+    def inner(it):
+        n_s, n_t = bdpt_amd.strategies_shape(it.config.rr_depth, it.config.strategy)
+        return (n_s * n_t,
+                {"weighted": lambda fb: it.render_strategies_device(fb, n_s, n_t),
+                 "unweighted": lambda fb: it.render_strategies_device(fb, n_s, n_t, unweighted=True)},
+                {"crossed_weighted": lambda fb: it.render_group_strategies_device(fb, n_s, n_t),
+                 "crossed_unweighted": lambda fb: it.render_group_strategies_device(fb, n_s, n_t, unweighted=True)})
+    crossed(inner)
+
+
 if __name__ == "__main__":
-    modes = {"layers": layers, "groups": groups, "strategies": strategies}
+    modes = {"layers": layers, "groups": groups, "strategies": strategies, "group-layers": group_layers,
+             "group-strategies": group_strategies}
     if len(sys.argv) != 2 or sys.argv[1] not in modes:
         sys.exit("usage: planes_cost.py " + " | ".join(modes))
     modes[sys.argv[1]]()
