@@ -27,6 +27,9 @@ Mirrors the reference's plugin surface for the BDPT path
                                        (group, layer) / (group, s, t), recombined with per-group RGB gains and
                                        per-inner-plane weights (bdpt_render_group_layers,
                                        bdpt_render_group_strategies, bdpt_group_planes_combine; no counterpart)
+    .denoise_planes(planes, aov, mode, guide)
+                                       the filter for the planes of any of those splits, with weights of their own or
+                                       one set for all, under which they still add up (bdpt_denoise_planes; no counterpart)
   Sampler(seed)                        Sampler              src/core/math.h:63-76 (seed + draw count)
   Ray(o, d, min_t, max_t)              Ray                  src/core/core.h:117-122
   load_toml(path) -> SceneConfig       loadTOML             src/main.cpp:22-116
@@ -326,6 +329,8 @@ def lib():
         L.bdpt_render_aov_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), vp]
         L.bdpt_denoise.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.POINTER(_DenoiseParams), vp]
         L.bdpt_denoise_host.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.POINTER(_DenoiseParams)]
+        L.bdpt_denoise_planes.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(_DenoiseParams), vp, vp, vp]
+        L.bdpt_denoise_planes_host.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(_DenoiseParams), vp, vp]
         L.bdpt_render_layers.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp, vp]
         L.bdpt_render_layers_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp]
         L.bdpt_layers_compose.argtypes = [vp, vp, i32, i32, i32, ctypes.c_uint64, vp, vp]
@@ -940,6 +945,93 @@ def combine_group_planes_numpy(planes, gains=None, weights=None) -> np.ndarray:
     return acc
 
 
+DENOISE_PLANES_OWN, DENOISE_PLANES_SHARED = 0, 1  # bdpt_denoise_planes' mode (BDPT_DENOISE_PLANES_*)
+
+
+def _denoise_planes_mode(mode) -> int:
+    """"own" / "shared" or a DENOISE_PLANES_* value (any other int reaches the library as it is)."""
+    if isinstance(mode, str):
+        if mode not in ("own", "shared"):
+            raise BdptError(f"denoise_planes: mode must be 'own' or 'shared', got {mode!r}")
+        return DENOISE_PLANES_SHARED if mode == "shared" else DENOISE_PLANES_OWN
+    return int(mode)
+
+
+def denoise_planes_numpy(planes, aov, mode="shared", guide=None, settings=None, norm=1.0, dt=np.float64):
+    """What bdpt_denoise_planes computes, as the header states it, every operation in `dt`: planes of any
+    leading shape (..., H, W, 3) filtered with weights of their own ("own") or with the weights of one colour
+    guide G ("shared": `guide`, or the planes' sequential float32 sum). -> (filtered planes in planes' shape,
+    filtered guide or None in own mode), both in dt. The guide rides along as one more plane whose colour
+    forms the weights, so its update is the planes' formula."""
+    f = dt
+    d = settings or DenoiseSettings()
+    shared = _denoise_planes_mode(mode) == DENOISE_PLANES_SHARED
+    a = np.asarray(planes, np.float32)
+    H, W = a.shape[-3:-1]
+    flat = a.reshape((-1, H, W, 3))
+    n = flat.shape[0]
+    if not shared and guide is not None:
+        raise BdptError("denoise_planes: guide must be None in own mode")
+    img = flat.astype(dt) * f(norm)
+    if shared:
+        if guide is None:
+            G = flat[0].copy()
+            for k in range(1, n):
+                G = G + flat[k]  # float32, ascending
+        else:
+            G = np.asarray(guide, np.float32).reshape(H, W, 3)
+        img = np.concatenate([img, (G.astype(dt) * f(norm))[None]])
+    if d.iterations == 0:
+        return img[:n].reshape(a.shape), (img[n] if shared else None)
+    av = np.asarray(aov, np.float32).reshape(H, W, 8).astype(dt) * f(norm)
+    cov = av[..., 7]
+    hit = cov > 0
+    safe = np.where(hit, cov, f(1))
+    alb = np.where(hit[..., None], av[..., 0:3] / safe[..., None], f(1))
+    N = np.where(hit[..., None], av[..., 3:6] / safe[..., None], f(0))
+    z = np.where(hit, av[..., 6] / safe, f(0))
+    m = np.maximum(alb, f(1e-3))
+    if d.demodulate:
+        img = img / m
+    kern = np.array([1, 4, 6, 4, 1], dt) / f(16)
+    zs = f(d.sigma_depth) * np.maximum(z, f(1e-6))
+    for i in range(d.iterations):
+        s = 1 << i
+        sc = f(d.sigma_color) * f(2.0 ** -i)
+        num = np.zeros_like(img)
+        den = np.zeros((1 if shared else n, H, W), dt)
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                oy, ox = dy * s, dx * s
+                py = slice(max(0, -oy), min(H, H - oy))
+                px = slice(max(0, -ox), min(W, W - ox))
+                if py.start >= py.stop or px.start >= px.stop:
+                    continue
+                qy = slice(py.start + oy, py.stop + oy)
+                qx = slice(px.start + ox, px.stop + ox)
+                h = kern[dy + 2] * kern[dx + 2]
+                src = img[n:] if shared else img  # whose colour forms the weights
+                if dx == 0 and dy == 0:
+                    w = np.ones((src.shape[0], H, W), dt)
+                else:
+                    dc = src[:, py, px] - src[:, qy, qx]
+                    dn = N[py, px] - N[qy, qx]
+                    dz = z[py, px] - z[qy, qx]
+                    wc = np.exp(-np.minimum(((dc[..., 0] ** 2 + dc[..., 1] ** 2) + dc[..., 2] ** 2) / (sc * sc), f(80)))
+                    wn = np.exp(-np.minimum(((dn[..., 0] ** 2 + dn[..., 1] ** 2) + dn[..., 2] ** 2)
+                                            / (f(d.sigma_normal) * f(d.sigma_normal)), f(80)))
+                    wz = np.exp(-np.minimum((dz * dz) / (zs[py, px] * zs[py, px]), f(80)))
+                    w = np.where(hit[py, px] == hit[qy, qx], (wc * wn) * wz, f(0))
+                hw = h * w
+                num[:, py, px] += hw[..., None] * img[:, qy, qx]
+                den[:, py, px] += hw
+        img = num / den[..., None]
+    if d.demodulate:
+        img = img * m
+    assert img.dtype == dt
+    return img[:n].reshape(a.shape), (img[n] if shared else None)
+
+
 class BDPTIntegrator:
     """GPU BDPT integrator with the reference's Integrator interface."""
 
@@ -1483,6 +1575,50 @@ class BDPTIntegrator:
         _check(lib().bdpt_denoise(self._h, self.config.width, self.config.height, ctypes.c_void_p(rgb_ptr),
                                   ctypes.c_void_p(aov_ptr), ctypes.c_void_p(out_ptr), ctypes.byref(d),
                                   ctypes.c_void_p(stream_ptr)))
+
+    def denoise_planes(self, planes, aov=None, mode="shared", guide=None, samples_done: int | None = None,
+                       return_guide: bool = False, **params):
+        """bdpt_denoise_planes_host of a split frame's planes, any leading shape (n, H, W, 3), (n_groups,
+        n_inner, H, W, 3), ...: a new array of that shape, guided by aov (default self.aov). mode "own":
+        every plane as denoise() filters it; "shared": every plane with the weights of one colour guide
+        (guide, an (H, W, 3) image, or None: the planes' sum), so that the filtered planes still add up and
+        relight. return_guide: also the filtered guide, (planes, guide). samples_done and params as denoise()."""
+        H, W = self.config.height, self.config.width
+        settings = params.pop("settings", None) or DenoiseSettings()
+        if params:
+            from dataclasses import replace
+            settings = replace(settings, **params)
+        if samples_done is not None and samples_done < 1:
+            raise ValueError("denoise_planes: samples_done must be >= 1")
+        norm = 1.0 if samples_done is None else self.config.spp / samples_done
+        p = np.ascontiguousarray(planes, np.float32)
+        if p.ndim < 4 or p.shape[-3:] != (H, W, 3):
+            raise BdptError(f"denoise_planes: planes must be (..., {H}, {W}, 3), got {p.shape}")
+        a = np.ascontiguousarray(self.aov if aov is None else aov, np.float32)
+        g = None if guide is None else np.ascontiguousarray(guide, np.float32)
+        if a.size != W * H * 8 or (g is not None and g.size != W * H * 3):
+            raise BdptError(f"denoise_planes: aov / guide must hold {W * H * 8} / {W * H * 3} floats")
+        n = math.prod(p.shape[:-3])
+        ok = n >= 1 and n * W * H < PLANE_PIXELS_MAX  # (what the library refuses before it touches a buffer)
+        out = np.zeros(p.shape if ok else (1,), np.float32)
+        out_guide = np.zeros((H, W, 3), np.float32) if return_guide else None
+        d = settings.c(norm)
+        _check(lib().bdpt_denoise_planes_host(self._h, W, H, n, p.ctypes.data, a.ctypes.data,
+                                              None if g is None else g.ctypes.data, _denoise_planes_mode(mode),
+                                              ctypes.byref(d), out.ctypes.data,
+                                              None if out_guide is None else out_guide.ctypes.data))
+        return (out, out_guide) if return_guide else out
+
+    def denoise_planes_device(self, planes_ptr: int, n_planes: int, aov_ptr: int, out_ptr: int, mode="shared",
+                              guide_ptr: int = 0, out_guide_ptr: int = 0, stream_ptr: int = 0, norm: float = 1.0,
+                              settings: "DenoiseSettings | None" = None) -> None:
+        """bdpt_denoise_planes: asynchronous, on device buffers (0: no guide given / no filtered guide wanted)."""
+        d = (settings or DenoiseSettings()).c(norm)
+        _check(lib().bdpt_denoise_planes(self._h, self.config.width, self.config.height, int(n_planes),
+                                         ctypes.c_void_p(planes_ptr), ctypes.c_void_p(aov_ptr),
+                                         ctypes.c_void_p(guide_ptr or None), _denoise_planes_mode(mode), ctypes.byref(d),
+                                         ctypes.c_void_p(out_ptr), ctypes.c_void_p(out_guide_ptr or None),
+                                         ctypes.c_void_p(stream_ptr)))
 
     def stats(self) -> dict:
         s = _Stats()

@@ -169,6 +169,135 @@ __global__ __launch_bounds__(kDnX* kDnY) void denoise_iter_kernel(int W, int H, 
     }
 }
 
+// --------------------------------------------------------- filter, many planes
+// bdpt_denoise_planes (bdpt_amd.h): the planes of one frame filtered kDnP at a
+// time. A lane still owns one pixel of a 32 x 8 block, and per tap it loads the two guide
+// vectors of q and forms wn and wz once for the kDnP planes it carries; the planes' colours are
+// kDnP float4 images (plane k of the chunk at src + k * W * H), so a tap is 2 + kDnP loads of 16
+// bytes (3 + kDnP in SHARED mode) where kDnP single-plane calls take 3 kDnP. The expressions
+// are denoise_iter_kernel's, restated so that kernel's device code stays what it was; a plane of
+// OWN mode gets the bits of that kernel.
+constexpr int kDnP = 4;
+
+// out[i] = (planes[i] + planes[n + i] + ... in ascending plane order, starting from plane 0's
+// value) * scale: float32, no atomics, the bits of that loop on the host (layers_compose_kernel
+// with every bit set, for any plane count). scale 1 leaves the sum's bits.
+__global__ __launch_bounds__(256) void planes_sum_kernel(const float* __restrict__ planes, size_t n, int n_planes,
+                                                         float scale, float* __restrict__ out) {
+    for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * 256) {
+        float acc = gld1(planes + i);
+        for (int k = 1; k < n_planes; k++) acc += gld1(planes + static_cast<size_t>(k) * n + i);  // (wave-uniform)
+        gst1(out + i, acc * scale);
+    }
+}
+
+// I_0 of the chunk's cnt <= kDnP planes (planes: the chunk's first, W * H * 3 floats each): c =
+// plane * norm, divided by max(alb, 1e-3) of the packed guides when demodulated — the albedo
+// denoise_prepare_kernel stored, so the quotient it forms.
+__global__ __launch_bounds__(kDnX* kDnY) void denoise_planes_prepare_kernel(int W, int H, const float* __restrict__ planes,
+                                                                            int cnt, float norm, int demodulate,
+                                                                            const float4* __restrict__ guide,
+                                                                            float4* __restrict__ img) {
+    const int x = blockIdx.x * kDnX + threadIdx.x, y = blockIdx.y * kDnY + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t px = static_cast<size_t>(W) * H, p = static_cast<size_t>(y) * W + x;
+    const float4 g0 = gld4(guide + 2 * p);
+    for (int k = 0; k < cnt; k++) {  // (wave-uniform)
+        const float* src = planes + 3 * (k * px + p);
+        f3 c = mk(gld1(src) * norm, gld1(src + 1) * norm, gld1(src + 2) * norm);
+        if (demodulate) c = mk(c.x / fmaxf(g0.x, 1e-3f), c.y / fmaxf(g0.y, 1e-3f), c.z / fmaxf(g0.z, 1e-3f));
+        gst4(img + k * px + p, make_float4(c.x, c.y, c.z, 0.f));
+    }
+}
+
+// One a-trous iteration of a chunk. SHARED: the colour weight comes from the guide's image B_i
+// (b: the trajectory bdpt_denoise_planes keeps), so w and the weight sum are the pixel's, one
+// expf per tap beyond wn and wz whatever kDnP. Otherwise each plane has its own wc and weight
+// sum from its own colour, the product kept as (wc * wn) * wz. Planes at or beyond cnt (the last
+// chunk) are neither loaded nor stored. LAST: out is the chunk's first output plane.
+template <bool SHARED, bool LAST>
+__global__ __launch_bounds__(kDnX* kDnY) void denoise_planes_iter_kernel(int W, int H, int s, float inv_c, float inv_n,
+                                                                         float sigma_z, int demodulate, int cnt,
+                                                                         const float4* __restrict__ guide,
+                                                                         const float4* __restrict__ b,
+                                                                         const float4* __restrict__ src,
+                                                                         float4* __restrict__ dst, float* __restrict__ out) {
+    const int x = blockIdx.x * kDnX + threadIdx.x, y = blockIdx.y * kDnY + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t px = static_cast<size_t>(W) * H, p = static_cast<size_t>(y) * W + x;
+    const float4 g0 = gld4(guide + 2 * p), g1 = gld4(guide + 2 * p + 1);
+    const float zs = sigma_z * fmaxf(g0.w, 1e-6f);
+    const float inv_z = 1.f / (zs * zs);
+    float4 ip[kDnP];  // the centre colours: B_i(p) in [0] when SHARED, the planes' own otherwise
+    if (SHARED) {
+        ip[0] = gld4(b + p);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kDnP; k++) ip[k] = k < cnt ? gld4(src + k * px + p) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float sr[kDnP], sg[kDnP], sb[kDnP], sw[kDnP];
+#pragma unroll
+    for (int k = 0; k < kDnP; k++) sr[k] = sg[k] = sb[k] = sw[k] = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + dy * s;
+        if (qy < 0 || qy >= H) continue;
+        const float hy = (dy == 0 ? 6.f : (dy == -1 || dy == 1 ? 4.f : 1.f)) * 0.0625f;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + dx * s;
+            if (qx < 0 || qx >= W) continue;
+            const float hx = (dx == 0 ? 6.f : (dx == -1 || dx == 1 ? 4.f : 1.f)) * 0.0625f;
+            const size_t q = static_cast<size_t>(qy) * W + qx;
+            float4 iq[kDnP];
+#pragma unroll
+            for (int k = 0; k < kDnP; k++) iq[k] = k < cnt ? gld4(src + k * px + q) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const bool centre = dx == 0 && dy == 0;
+            float wn = 1.f, wz = 1.f;
+            bool same = true;
+            float4 bq = ip[0];
+            if (!centre) {
+                const float4 h0 = gld4(guide + 2 * q), h1 = gld4(guide + 2 * q + 1);
+                if (SHARED) bq = gld4(b + q);
+                const float nx = g1.x - h1.x, ny = g1.y - h1.y, nz = g1.z - h1.z;
+                const float dz = g0.w - h0.w;
+                wn = expf(-fminf(((nx * nx + ny * ny) + nz * nz) * inv_n, 80.f));
+                wz = expf(-fminf((dz * dz) * inv_z, 80.f));
+                same = g1.w == h1.w;
+            }
+            float hw = 0.f;  // SHARED: plane 0's turn forms the tap's one weight, the others reuse it
+#pragma unroll
+            for (int k = 0; k < kDnP; k++) {
+                if (!SHARED || k == 0) {
+                    float w = 1.f;
+                    if (!centre) {
+                        const float4 cq = SHARED ? bq : iq[k];
+                        const float cr = ip[k].x - cq.x, cg = ip[k].y - cq.y, cb = ip[k].z - cq.z;
+                        const float wc = expf(-fminf(((cr * cr + cg * cg) + cb * cb) * inv_c, 80.f));
+                        w = same ? (wc * wn) * wz : 0.f;
+                    }
+                    hw = (hy * hx) * w;
+                    sw[k] += hw;
+                }
+                sr[k] += hw * iq[k].x, sg[k] += hw * iq[k].y, sb[k] += hw * iq[k].z;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kDnP; k++) {
+        if (k >= cnt) break;
+        const float den = sw[SHARED ? 0 : k];
+        float r = sr[k] / den, g = sg[k] / den, bl = sb[k] / den;
+        if (LAST) {
+            if (demodulate) r *= fmaxf(g0.x, 1e-3f), g *= fmaxf(g0.y, 1e-3f), bl *= fmaxf(g0.z, 1e-3f);
+            float* o = out + 3 * (k * px + p);
+            gst1(o, r), gst1(o + 1, g), gst1(o + 2, bl);
+        } else {
+            gst4(dst + k * px + p, make_float4(r, g, bl, 0.f));
+        }
+    }
+}
+
 // ------------------------------------------------------------ path-length layers
 // out[i] = the sum over the layers l in `mask` of layers[l * n + i] (n = W * H * 3 floats per
 // plane, bdpt_render_layers), float32 additions in ascending layer order starting from the
@@ -402,6 +531,34 @@ hipError_t launch_denoise_iter(int W, int H, int step, float inv_c, float inv_n,
         hipLaunchKernelGGL(dev::denoise_iter_kernel<false>, dn_grid(W, H), dim3(dev::kDnX, dev::kDnY), 0, st, W, H,
                            step, inv_c, inv_n, sigma_z, demodulate, static_cast<const float4*>(guide),
                            static_cast<const float4*>(src), static_cast<float4*>(dst), out);
+    return hipGetLastError();
+}
+
+int denoise_planes_chunk() { return dev::kDnP; }
+
+hipError_t launch_planes_sum(const float* planes, size_t n, int n_planes, float scale, float* out, hipStream_t st) {
+    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((n + 255) / 256, 4096));
+    hipLaunchKernelGGL(dev::planes_sum_kernel, dim3(blocks), dim3(256), 0, st, planes, n, n_planes, scale, out);
+    return hipGetLastError();
+}
+// planes: the chunk's first plane; cnt planes (1 .. denoise_planes_chunk()) go to img.
+hipError_t launch_denoise_planes_prepare(int W, int H, const float* planes, int cnt, float norm, int demodulate,
+                                         const void* guide, void* img, hipStream_t st) {
+    hipLaunchKernelGGL(dev::denoise_planes_prepare_kernel, dn_grid(W, H), dim3(dev::kDnX, dev::kDnY), 0, st, W, H, planes,
+                       cnt, norm, demodulate, static_cast<const float4*>(guide), static_cast<float4*>(img));
+    return hipGetLastError();
+}
+// b: the guide's image of this iteration (shared weights), or null (every plane its own).
+hipError_t launch_denoise_planes_iter(int W, int H, int step, float inv_c, float inv_n, float sigma_z, int demodulate,
+                                      int cnt, const void* guide, const void* b, const void* src, void* dst, float* out,
+                                      bool last, hipStream_t st) {
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dn_grid(W, H), dim3(dev::kDnX, dev::kDnY), 0, st, W, H, step, inv_c, inv_n, sigma_z,
+                           demodulate, cnt, static_cast<const float4*>(guide), static_cast<const float4*>(b),
+                           static_cast<const float4*>(src), static_cast<float4*>(dst), out);
+    };
+    if (b) last ? go(dev::denoise_planes_iter_kernel<true, true>) : go(dev::denoise_planes_iter_kernel<true, false>);
+    else last ? go(dev::denoise_planes_iter_kernel<false, true>) : go(dev::denoise_planes_iter_kernel<false, false>);
     return hipGetLastError();
 }
 

@@ -72,6 +72,14 @@ hipError_t launch_denoise_prepare(int W, int H, const float* color, const float*
 hipError_t launch_denoise_scale(size_t n, const float* color, float norm, float* out, hipStream_t st);
 hipError_t launch_denoise_iter(int W, int H, int step, float inv_c, float inv_n, float sigma_z, int demodulate,
                                const void* guide, const void* src, void* dst, float* out, bool last, hipStream_t st);
+// aov_kernels.hip: the filter for many planes, denoise_planes_chunk() planes per launch
+int denoise_planes_chunk();
+hipError_t launch_planes_sum(const float* planes, size_t n, int n_planes, float scale, float* out, hipStream_t st);
+hipError_t launch_denoise_planes_prepare(int W, int H, const float* planes, int cnt, float norm, int demodulate,
+                                         const void* guide, void* img, hipStream_t st);
+hipError_t launch_denoise_planes_iter(int W, int H, int step, float inv_c, float inv_n, float sigma_z, int demodulate,
+                                      int cnt, const void* guide, const void* b, const void* src, void* dst, float* out,
+                                      bool last, hipStream_t st);
 // aov_kernels.hip: a masked sum of path-length layers (planes of n floats)
 hipError_t launch_layers_compose(const float* layers, size_t n, uint64_t mask, float* out, hipStream_t st);
 // aov_kernels.hip: light-group planes (n floats each) recombined with per-group RGB gains (host, n_groups x 3)
@@ -328,6 +336,9 @@ struct bdpt_ctx : CtxStream {
     // per pixel each), reserved together at first use and when a larger frame comes
     DevBuf<void> dn_guide, dn_img[2];
     size_t dn_pixels = 0;  // the frame all three hold (0 after a failed reserve)
+    // filter for many planes (bdpt_denoise_planes): packed guides, the guide's images B_0 .. B_7
+    // (SHARED mode) and the ping-pong pair of the planes in flight; each grows on its own
+    DevBuf<void> dnp_guide, dnp_traj, dnp_img[2];
     // stats of the last render
     bool pending_timing = false;
     bdpt_stats stats{};
@@ -2292,17 +2303,23 @@ int bdpt_render_aov_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sam
                       [&](float* aov) { return bdpt_render_aov(c, p, w, aov, c->stream); });
 }
 
+// The frame size and the parameter fields, for bdpt_denoise and bdpt_denoise_planes (entry: whose message).
+static int check_denoise_fields(const std::string& entry, int32_t width, int32_t height, const bdpt_denoise_params* d) {
+    if (width <= 0 || height <= 0 || static_cast<int64_t>(width) * height >= (1ll << 31))
+        return fail(BDPT_ERR_INVALID, entry + ": width/height must be > 0 and W*H fit int32");
+    if (d->iterations < 0 || d->iterations > 8) return fail(BDPT_ERR_INVALID, entry + ": iterations must be in [0, 8]");
+    if (!(d->sigma_color > 0.f)) return fail(BDPT_ERR_INVALID, entry + ": sigma_color must be > 0");
+    if (!(d->sigma_normal > 0.f)) return fail(BDPT_ERR_INVALID, entry + ": sigma_normal must be > 0");
+    if (!(d->sigma_depth > 0.f)) return fail(BDPT_ERR_INVALID, entry + ": sigma_depth must be > 0");
+    if (d->demodulate != 0 && d->demodulate != 1) return fail(BDPT_ERR_INVALID, entry + ": demodulate must be 0 or 1");
+    if (!(d->norm > 0.f) || !std::isfinite(d->norm)) return fail(BDPT_ERR_INVALID, entry + ": norm must be > 0");
+    return BDPT_OK;
+}
+
 static int check_denoise(int32_t width, int32_t height, const float* color, const float* aov, const float* out,
                          const bdpt_denoise_params* d) {
     if (!color || !aov || !out || !d) return fail(BDPT_ERR_INVALID, "null argument");
-    if (width <= 0 || height <= 0 || static_cast<int64_t>(width) * height >= (1ll << 31))
-        return fail(BDPT_ERR_INVALID, "bdpt_denoise: width/height must be > 0 and W*H fit int32");
-    if (d->iterations < 0 || d->iterations > 8) return fail(BDPT_ERR_INVALID, "bdpt_denoise: iterations must be in [0, 8]");
-    if (!(d->sigma_color > 0.f)) return fail(BDPT_ERR_INVALID, "bdpt_denoise: sigma_color must be > 0");
-    if (!(d->sigma_normal > 0.f)) return fail(BDPT_ERR_INVALID, "bdpt_denoise: sigma_normal must be > 0");
-    if (!(d->sigma_depth > 0.f)) return fail(BDPT_ERR_INVALID, "bdpt_denoise: sigma_depth must be > 0");
-    if (d->demodulate != 0 && d->demodulate != 1) return fail(BDPT_ERR_INVALID, "bdpt_denoise: demodulate must be 0 or 1");
-    if (!(d->norm > 0.f) || !std::isfinite(d->norm)) return fail(BDPT_ERR_INVALID, "bdpt_denoise: norm must be > 0");
+    if (int rc = check_denoise_fields("bdpt_denoise", width, height, d)) return rc;
     const size_t px = static_cast<size_t>(width) * height;
     auto overlaps = [&](const float* a, size_t na) {
         const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + px * 3 * sizeof(float);
@@ -2359,6 +2376,149 @@ int bdpt_denoise_host(bdpt_ctx* c, int32_t width, int32_t height, const float* c
     HIP_TRY(hipMemcpyAsync(da, aov, px * 8 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if ((rc = bdpt_denoise(c, width, height, dc, da, dout, d, c->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(out, dout, px * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+// OWN mode filters frames of up to this many pixels in chunks and larger ones plane by plane: measured
+// (DESIGN.md §7h), the chunks are 1.4 to 1.8 x the loop at 512^2 and 0.91 to 1.05 x at 1024^2.
+constexpr size_t kDenoisePlanesOwnChunkPixels = 512 * 512;
+
+static int check_denoise_planes(int32_t width, int32_t height, int32_t n_planes, const float* planes, const float* aov,
+                                const float* guide_color, int32_t mode, const bdpt_denoise_params* d,
+                                const float* out_planes, const float* out_guide) {
+    const std::string entry = "bdpt_denoise_planes";
+    if (!planes || !aov || !out_planes || !d) return fail(BDPT_ERR_INVALID, "null argument");
+    if (int rc = check_denoise_fields(entry, width, height, d)) return rc;
+    if (n_planes < 1) return fail(BDPT_ERR_INVALID, entry + ": n_planes must be >= 1");
+    const size_t px = static_cast<size_t>(width) * height;
+    if (static_cast<uint64_t>(n_planes) * px >= (1ull << 30))
+        return fail(BDPT_ERR_INVALID, entry + ": n_planes * width * height must be below 2^30");
+    if (mode != BDPT_DENOISE_PLANES_OWN && mode != BDPT_DENOISE_PLANES_SHARED)
+        return fail(BDPT_ERR_INVALID, entry + ": mode must be BDPT_DENOISE_PLANES_OWN or BDPT_DENOISE_PLANES_SHARED");
+    if (mode == BDPT_DENOISE_PLANES_OWN && guide_color)
+        return fail(BDPT_ERR_INVALID, entry + ": guide_color must be NULL in OWN mode");
+    if (mode == BDPT_DENOISE_PLANES_OWN && out_guide)
+        return fail(BDPT_ERR_INVALID, entry + ": out_guide must be NULL in OWN mode");
+    struct Span {
+        const char* name;
+        const float* p;
+        size_t floats;
+    };
+    const Span in[] = {{"planes", planes, n_planes * px * 3}, {"aov", aov, px * 8}, {"guide_color", guide_color, px * 3}};
+    const Span outs[] = {{"out_planes", out_planes, n_planes * px * 3}, {"out_guide", out_guide, px * 3}};
+    auto overlap = [](const Span& a, const Span& b) {
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
+        return a.p && b.p && a0 < b0 + b.floats * sizeof(float) && b0 < a0 + a.floats * sizeof(float);
+    };
+    for (const Span& o : outs)
+        for (const Span& i : in)
+            if (overlap(o, i)) return fail(BDPT_ERR_INVALID, entry + ": " + o.name + " overlaps " + i.name);
+    if (overlap(outs[1], outs[0])) return fail(BDPT_ERR_INVALID, entry + ": out_guide overlaps out_planes");
+    return BDPT_OK;
+}
+
+int bdpt_denoise_planes(bdpt_ctx* c, int32_t width, int32_t height, int32_t n_planes, const float* planes,
+                        const float* aov, const float* guide_color, int32_t mode, const bdpt_denoise_params* d,
+                        float* out_planes, float* out_guide, void* hip_stream) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_denoise_planes(width, height, n_planes, planes, aov, guide_color, mode, d, out_planes, out_guide);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    const size_t px = static_cast<size_t>(width) * height, plane = px * 3;
+    const bool shared = mode == BDPT_DENOISE_PLANES_SHARED;
+    const int P = denoise_planes_chunk(), it = d->iterations;
+    if ((rc = begin_use(c, st))) return rc;
+    if (it > 0) {
+        HIP_TRY(c->dnp_guide.reserve(px * 32));
+        if (shared) HIP_TRY(c->dnp_traj.reserve(px * 16 * 8));
+        HIP_TRY(c->dnp_img[0].reserve(px * 16 * P));
+        HIP_TRY(c->dnp_img[1].reserve(px * 16 * P));
+    }
+    if ((rc = begin_timed(c, st))) return rc;
+    int64_t launches = 0;
+    if (it == 0) {
+        HIP_TRY(launch_denoise_scale(plane * n_planes, planes, d->norm, out_planes, st));
+        launches++;
+        if (out_guide) {
+            if (guide_color) HIP_TRY(launch_denoise_scale(plane, guide_color, d->norm, out_guide, st));
+            else HIP_TRY(launch_planes_sum(planes, plane, n_planes, d->norm, out_guide, st));
+            launches++;
+        }
+        return end_timed(c, st, 0, launches);
+    }
+    // sigma_color of iteration i, squared and inverted as bdpt_denoise does
+    auto inv_c = [&](int i) {
+        const float sc_i = d->sigma_color * std::ldexp(1.f, -i);
+        return 1.f / (sc_i * sc_i);
+    };
+    const float inv_n = 1.f / (d->sigma_normal * d->sigma_normal);
+    float4* const traj = static_cast<float4*>(c->dnp_traj.get());  // B_i at traj + i * px
+    if (shared) {
+        // The guides and the guide's own filter, with bdpt_denoise's kernels: B_0 .. B_{it-1} stay in traj, the
+        // last update goes to out_guide if anyone wants it. A summed G waits in B_1's place until B_0 is formed.
+        const float* g = guide_color;
+        if (!g) {
+            float* sum = reinterpret_cast<float*>(traj + px);
+            HIP_TRY(launch_planes_sum(planes, plane, n_planes, 1.f, sum, st));
+            launches++;
+            g = sum;
+        }
+        HIP_TRY(launch_denoise_prepare(width, height, g, aov, d->norm, d->demodulate, c->dnp_guide, traj, st));
+        const int guide_its = out_guide ? it : it - 1;
+        for (int i = 0; i < guide_its; i++)
+            HIP_TRY(launch_denoise_iter(width, height, 1 << i, inv_c(i), inv_n, d->sigma_depth, d->demodulate, c->dnp_guide,
+                                        traj + i * px, traj + (i + 1 < it ? i + 1 : 0) * px, out_guide, i + 1 == it, st));
+        launches += 1 + guide_its;
+    } else if (px > kDenoisePlanesOwnChunkPixels) {
+        // a large frame: bdpt_denoise's launches per plane, which the chunks do not beat there
+        for (int j = 0; j < n_planes; j++) {
+            HIP_TRY(launch_denoise_prepare(width, height, planes + j * plane, aov, d->norm, d->demodulate, c->dnp_guide,
+                                           c->dnp_img[0], st));
+            for (int i = 0; i < it; i++)
+                HIP_TRY(launch_denoise_iter(width, height, 1 << i, inv_c(i), inv_n, d->sigma_depth, d->demodulate,
+                                            c->dnp_guide, c->dnp_img[i & 1], c->dnp_img[(i + 1) & 1], out_planes + j * plane,
+                                            i + 1 == it, st));
+        }
+        return end_timed(c, st, 0, static_cast<int64_t>(n_planes) * (1 + it));
+    } else {
+        // only the packed guides are wanted; the image this writes is overwritten by the first chunk
+        HIP_TRY(launch_denoise_prepare(width, height, planes, aov, d->norm, d->demodulate, c->dnp_guide, c->dnp_img[0], st));
+        launches++;
+    }
+    for (int first = 0; first < n_planes; first += P) {
+        const int cnt = std::min(P, n_planes - first);
+        HIP_TRY(launch_denoise_planes_prepare(width, height, planes + first * plane, cnt, d->norm, d->demodulate,
+                                              c->dnp_guide, c->dnp_img[0], st));
+        for (int i = 0; i < it; i++)
+            HIP_TRY(launch_denoise_planes_iter(width, height, 1 << i, inv_c(i), inv_n, d->sigma_depth, d->demodulate, cnt,
+                                               c->dnp_guide, shared ? traj + i * px : nullptr, c->dnp_img[i & 1],
+                                               c->dnp_img[(i + 1) & 1], out_planes + first * plane, i + 1 == it, st));
+        launches += 1 + it;
+    }
+    return end_timed(c, st, 0, launches);
+}
+
+int bdpt_denoise_planes_host(bdpt_ctx* c, int32_t width, int32_t height, int32_t n_planes, const float* planes,
+                             const float* aov, const float* guide_color, int32_t mode, const bdpt_denoise_params* d,
+                             float* out_planes, float* out_guide) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_denoise_planes(width, height, n_planes, planes, aov, guide_color, mode, d, out_planes, out_guide);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t px = static_cast<size_t>(width) * height, all = px * 3 * n_planes;
+    HIP_TRY(c->tmp_fb.reserve((2 * all + px * 14) * sizeof(float)));
+    // planes, out_planes, aov, guide_color, out_guide (16-byte aligned or not: scalar loads and stores)
+    float *dp = c->tmp_fb, *dout = dp + all, *da = dout + all, *dg = da + px * 8, *dog = dg + px * 3;
+    HIP_TRY(hipMemcpyAsync(dp, planes, all * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(da, aov, px * 8 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (guide_color) HIP_TRY(hipMemcpyAsync(dg, guide_color, px * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((rc = bdpt_denoise_planes(c, width, height, n_planes, dp, da, guide_color ? dg : nullptr, mode, d, dout,
+                                  out_guide ? dog : nullptr, c->stream)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out_planes, dout, all * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out_guide) HIP_TRY(hipMemcpyAsync(out_guide, dog, px * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BDPT_OK;
 }

@@ -44,6 +44,13 @@
 // (emitter, s, t) plane that is not all zero (bdpt_render_group_strategies_host; no contact sheet).
 // Without --cross the two flags keep writing their two independent sets. Refusals and devices as for
 // the single flags.
+// --denoise-planes[=own|shared] (default shared; with at least one of the plane flags above) filters
+// every plane set those flags write with bdpt_denoise_planes_host (the header's defaults, --denoise=ITER's
+// iteration count if that flag is given too) and writes, next to each plane file, one with _denoised
+// appended to its stem. In shared mode the first set also writes the filtered sum of its planes to
+// <out>_denoised.exr, unless --denoise is given, whose file that is. The planes' own files are the same
+// bytes with or without it. Without a plane flag, with another value or with an empty --sample-window it
+// is refused before any device is used.
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
@@ -99,7 +106,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Syntax: %s <scene.toml> [nogui] [--width W --height H --spp N --rr D --device K "
                              "--out FILE.exr --seed S --gpus N --devices a,b,... --shard samples|rows "
-                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted] --cross]\n", argv[0]);
+                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted] --cross --denoise-planes[=own|shared]]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string toml = argv[1];
@@ -116,6 +123,7 @@ int main(int argc, char** argv) {
     bool light_groups = false;  // --light-groups
     int strategies = -1;        // --strategies[=unweighted]: BDPT_STRATEGIES_* (-1: none)
     bool cross = false;         // --cross: the groups crossed with the layers or the strategies
+    int denoise_planes = -1;    // --denoise-planes[=own|shared]: BDPT_DENOISE_PLANES_* (-1: none)
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -168,6 +176,13 @@ int main(int argc, char** argv) {
             }
             want_denoise = true;
             denoise_iterations = static_cast<int>(n);
+        } else if (a == "--denoise-planes" || a == "--denoise-planes=shared") {
+            denoise_planes = BDPT_DENOISE_PLANES_SHARED;
+        } else if (a == "--denoise-planes=own") {
+            denoise_planes = BDPT_DENOISE_PLANES_OWN;
+        } else if (a.rfind("--denoise-planes", 0) == 0) {
+            std::fprintf(stderr, "%s: --denoise-planes takes no value, =own or =shared\n", a.c_str());
+            return EXIT_FAILURE;
         } else if (a == "--layers") {
             const char* v = next("--layers");
             char* end = nullptr;
@@ -211,6 +226,14 @@ int main(int argc, char** argv) {
     }
     if (want_denoise && windowed && window.count == 0) {
         std::fprintf(stderr, "--denoise of an empty --sample-window (count 0): there is no sample to normalise by\n");
+        return EXIT_FAILURE;
+    }
+    if (denoise_planes >= 0 && !layers && !light_groups && strategies < 0) {
+        std::fprintf(stderr, "--denoise-planes filters the planes of --layers N, --light-groups or --strategies: give one of them\n");
+        return EXIT_FAILURE;
+    }
+    if (denoise_planes >= 0 && windowed && window.count == 0) {
+        std::fprintf(stderr, "--denoise-planes of an empty --sample-window (count 0): there is no sample to normalise by\n");
         return EXIT_FAILURE;
     }
     if (shard_given && devices.empty()) {
@@ -367,8 +390,10 @@ int main(int argc, char** argv) {
     }
     // --layers, --light-groups, --strategies: the frame again as n planes (on several devices the
     // first renders them), one EXR per plane under suffix(plane index), optionally only the planes
-    // that are not all zero; then after(context, planes), for what follows the planes.
+    // that are not all zero; then after(context, planes), for what follows the planes. --denoise-planes:
+    // the set filtered in one call, each written plane's filtered one beside it.
     const size_t plane = static_cast<size_t>(cfg.width) * cfg.height * 3;
+    bool guide_written = want_denoise;  // <out>_denoised.exr: --denoise's, else the first shared set's
     auto write_planes = [&](const char* ctx_what, const char* render_what, size_t n, auto render, auto suffix,
                             bool skip_empty, auto after) -> int {
         bdpt_ctx* pctx = ctx;
@@ -381,6 +406,31 @@ int main(int argc, char** argv) {
             const std::string side = side_path(exr, suffix(static_cast<int>(k)).c_str());
             if (bdpt_save_exr(px, cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
             std::printf("Saved EXR image to %s\n", side.c_str());
+        }
+        if (denoise_planes >= 0) {
+            bdpt_denoise_params d = {denoise_iterations, BDPT_DENOISE_SIGMA_COLOR, BDPT_DENOISE_SIGMA_NORMAL,
+                                     BDPT_DENOISE_SIGMA_DEPTH, BDPT_DENOISE_DEMODULATE, 1.f};
+            if (windowed) d.norm = static_cast<float>(cfg.spp) / static_cast<float>(window.count);
+            std::vector<float> aov(plane / 3 * 8, 0.f), den(plane * n), guide;
+            if (bdpt_render_aov_host(pctx, &p, win, aov.data()) != BDPT_OK) return die("bdpt_render_aov_host");
+            if (denoise_planes == BDPT_DENOISE_PLANES_SHARED && !guide_written) guide.resize(plane);
+            if (bdpt_denoise_planes_host(pctx, cfg.width, cfg.height, static_cast<int32_t>(n), planes.data(), aov.data(),
+                                         nullptr, denoise_planes, &d, den.data(),
+                                         guide.empty() ? nullptr : guide.data()) != BDPT_OK)
+                return die("bdpt_denoise_planes_host");
+            for (size_t k = 0; k < n; k++) {
+                const float* const px = planes.data() + plane * k;
+                if (skip_empty && std::all_of(px, px + plane, [](float v) { return v == 0.f; })) continue;
+                const std::string side = side_path(exr, (suffix(static_cast<int>(k)) + "_denoised").c_str());
+                if (bdpt_save_exr(den.data() + plane * k, cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
+                std::printf("Saved EXR image to %s\n", side.c_str());
+            }
+            if (!guide.empty()) {
+                const std::string side = side_path(exr, "_denoised");
+                if (bdpt_save_exr(guide.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
+                std::printf("Saved EXR image to %s\n", side.c_str());
+                guide_written = true;
+            }
         }
         if (const int rc = after(pctx, planes.data())) return rc;
         if (pctx != ctx) bdpt_ctx_destroy(pctx);

@@ -42,6 +42,8 @@
  *   bdpt_render_aov          (no counterpart) the primary query of every camera sample of that loop
  *                            (renderer.cpp:162-192, accel.h:125-172) as albedo / normal / depth / coverage
  *   bdpt_denoise             (no counterpart) an edge-avoiding filter of a low-spp frame on the device
+ *   bdpt_denoise_planes      (no counterpart) that filter for the planes of a split frame, with weights
+ *                            of their own or one set for all, under which the planes still add up
  *
  * Conventions: plain C types only; status 0 = OK, < 0 = error (message from
  * bdpt_last_error(), thread-local). A context is bound to one HIP device and is
@@ -518,6 +520,44 @@ int bdpt_denoise(bdpt_ctx* ctx, int32_t width, int32_t height, const float* colo
                  float* out_dev, const bdpt_denoise_params* params, void* hip_stream);
 int bdpt_denoise_host(bdpt_ctx* ctx, int32_t width, int32_t height, const float* color_host, const float* aov_host,
                       float* out_host, const bdpt_denoise_params* params);
+
+/* (new) The filter for the planes of a split frame (bdpt_render_layers, _light_groups, _strategies,
+ * _group_layers, _group_strategies): planes and out_planes are n_planes consecutive width * height * 3
+ * planes, aov and params are bdpt_denoise's. The guides alb, N, z, cov and m = max(alb, 1e-3) come from
+ * aov * norm exactly as there; for plane j, c_j = plane_j * norm and I^j_0 = demodulate ? c_j / m : c_j.
+ *   BDPT_DENOISE_PLANES_OWN: every plane runs bdpt_denoise's recurrence on its own colour: out_planes[j]
+ *   has the bits of bdpt_denoise(plane_j, aov, params). guide_color and out_guide must be NULL. One call,
+ *   and, for frames of up to 512 x 512 pixels, the guide work of a tap (two of its three loads, two of
+ *   its three exp) done once per 4 planes; larger frames run bdpt_denoise's launches plane by plane.
+ *   BDPT_DENOISE_PLANES_SHARED: one colour guide G for all planes: guide_color (width * height * 3
+ *   floats) if given, else the planes' float32 sum in ascending plane order starting from plane 0's
+ *   value (for n_planes <= 64 the bits of bdpt_layers_compose with every bit set). B_0 is formed from G
+ *   as bdpt_denoise forms I_0 from color; in iteration i, w(p, q) is bdpt_denoise's weight with I_i := B_i
+ *   and B_{i+1} its update, and every plane uses those weights:
+ *     I^j_{i+1}(p) = (sum_q hw I^j_i(q)) / (sum_q hw),   hw = (h_y h_x) w(p, q),
+ *   taps in bdpt_denoise's order (dy outer, dx inner, outside taps skipped, the centre w = 1), each
+ *   product and each sum rounded on its own, the division last. The filter is then linear in the planes:
+ *   up to float32 rounding the filtered planes sum to the filtered G, and a relight of the filtered
+ *   planes is the filter of the relit planes under the same guide. out_guide (NULL: not wanted)
+ *   receives the bits of bdpt_denoise(G, aov, params).
+ * Both: out_planes[j] = I^j_iterations * (demodulate ? m : 1); iterations == 0 copies plane * norm, and
+ * G * norm to out_guide. No atomics and a fixed order: two runs give the same bits; a plane that is all
+ * zero comes out all zero. BDPT_ERR_INVALID, the field named in the message, for bdpt_denoise's own
+ * parameter checks, n_planes < 1, n_planes * width * height >= 2^30, another mode, guide_color or
+ * out_guide in OWN mode, and out_planes or out_guide overlapping an input or each other. The context
+ * owns the scratch, allocated at first use and grown with the frame: 288 bytes per pixel whatever
+ * n_planes (packed guides 32, the guide's images B_0 .. B_7 128 - SHARED mode only -, and the ping-pong
+ * pair of the 4 planes in flight 2 x 4 x 16). bdpt_get_stats afterwards: kernel_ms and launches of this
+ * call. Asynchronous on `hip_stream`; the host form stages the buffers and is synchronous. */
+#define BDPT_DENOISE_PLANES_OWN 0
+#define BDPT_DENOISE_PLANES_SHARED 1
+int bdpt_denoise_planes(bdpt_ctx* ctx, int32_t width, int32_t height, int32_t n_planes, const float* planes_device,
+                        const float* aov_device, const float* guide_color_device, int32_t mode,
+                        const bdpt_denoise_params* params, float* out_planes_device, float* out_guide_device,
+                        void* hip_stream);
+int bdpt_denoise_planes_host(bdpt_ctx* ctx, int32_t width, int32_t height, int32_t n_planes, const float* planes_host,
+                             const float* aov_host, const float* guide_color_host, int32_t mode,
+                             const bdpt_denoise_params* params, float* out_planes_host, float* out_guide_host);
 
 /* ---- path-length layers: one BDPT frame split by bounce count ---- */
 /* (new) Not in the reference. Every contribution the BDPT frame kernel forms belongs to a full path
