@@ -331,6 +331,10 @@ def lib():
         L.bdpt_denoise_host.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.POINTER(_DenoiseParams)]
         L.bdpt_denoise_planes.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(_DenoiseParams), vp, vp, vp]
         L.bdpt_denoise_planes_host.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(_DenoiseParams), vp, vp]
+        L.bdpt_batch_moments.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+        L.bdpt_batch_moments_host.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+        L.bdpt_denoise_var.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(_DenoiseParams), vp]
+        L.bdpt_denoise_var_host.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(_DenoiseParams)]
         L.bdpt_render_layers.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp, vp]
         L.bdpt_render_layers_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp]
         L.bdpt_layers_compose.argtypes = [vp, vp, i32, i32, i32, ctypes.c_uint64, vp, vp]
@@ -1032,6 +1036,117 @@ def denoise_planes_numpy(planes, aov, mode="shared", guide=None, settings=None, 
     return img[:n].reshape(a.shape), (img[n] if shared else None)
 
 
+BATCHES_MIN, BATCHES_MAX = 2, 64  # bdpt_batch_moments' n_batches
+
+
+def batch_windows(spp: int, n_batches: int, window: "SampleWindow | None" = None) -> list:
+    """The sample windows of render_batches: with window (first, stride, count) (None: the whole spp), batch b
+    takes (first + b * stride, stride * n_batches, count / n_batches), so the batches interleave, partition the
+    window and are equally large (what bdpt_batch_moments' variance formula assumes). ValueError, the argument
+    named, for n_batches outside 2..64 or a count that is not a positive multiple of n_batches."""
+    n_batches = int(n_batches)
+    if not BATCHES_MIN <= n_batches <= BATCHES_MAX:
+        raise ValueError(f"render_batches: n_batches must be in [{BATCHES_MIN}, {BATCHES_MAX}], got {n_batches}")
+    w = window if window is not None else SampleWindow(0, 1, int(spp))
+    if w.count < 1 or w.count % n_batches:
+        raise ValueError(f"render_batches: count ({w.count}: the window's, or the spp) must be a positive multiple "
+                         f"of n_batches = {n_batches}")
+    return [SampleWindow(w.first + b * w.stride, w.stride * n_batches, w.count // n_batches) for b in range(n_batches)]
+
+
+def batch_moments_numpy(planes, dt=np.float32):
+    """What bdpt_batch_moments computes, as the header states it, every operation in `dt`: planes (K, ...) ->
+    (sum, var) in dt. In float32 the loop below is the kernel's, operation for operation."""
+    a = np.asarray(planes, np.float32).astype(dt)
+    K = a.shape[0]
+    if not BATCHES_MIN <= K <= BATCHES_MAX:
+        raise ValueError(f"batch_moments: n_batches must be in [{BATCHES_MIN}, {BATCHES_MAX}], got {K}")
+    S = a[0].copy()
+    for b in range(1, K):
+        S = S + a[b]
+    mu = S / dt(K)
+    Q = None
+    for b in range(K):
+        d = a[b] - mu
+        Q = d * d if Q is None else Q + d * d
+    var = Q * dt(np.float32(K) / np.float32(K - 1))
+    assert S.dtype == dt and var.dtype == dt
+    return S, var
+
+
+def denoise_var_settings() -> "DenoiseSettings":
+    """bdpt_denoise_var's defaults: the header's BDPT_DENOISE_VAR_ITERATIONS / _SIGMA_COLOR, the other fields
+    DenoiseSettings' own."""
+    return DenoiseSettings(iterations=3, sigma_color=4.0)
+
+
+def denoise_var_numpy(color, var, aov, settings=None, norm=1.0, dt=np.float64):
+    """What bdpt_denoise_var computes, as the header states it, every operation in `dt`: color and var (H, W, 3),
+    aov (H, W, 8) -> (out (H, W, 3), out_var (H, W)) in dt."""
+    f = dt
+    d = settings or denoise_var_settings()
+    c = np.asarray(color, np.float32).astype(dt) * f(norm)
+    H, W = c.shape[:2]
+    v = np.asarray(var, np.float32).reshape(H, W, 3).astype(dt) * (f(norm) * f(norm))
+    av = np.asarray(aov, np.float32).reshape(H, W, 8).astype(dt) * f(norm)
+    cov = av[..., 7]
+    hit = cov > 0
+    safe = np.where(hit, cov, f(1))
+    alb = np.where(hit[..., None], av[..., 0:3] / safe[..., None], f(1))
+    N = np.where(hit[..., None], av[..., 3:6] / safe[..., None], f(0))
+    z = np.where(hit, av[..., 6] / safe, f(0))
+    m = np.maximum(alb, f(1e-3))
+    img = c / m if d.demodulate else c
+    u = v / (m * m) if d.demodulate else v
+    U = (u[..., 0] + u[..., 1]) + u[..., 2]
+
+    def taps(radius, s):
+        for dy in range(-radius, radius + 1):
+            for dx in range(-radius, radius + 1):
+                oy, ox = dy * s, dx * s
+                py, px = slice(max(0, -oy), min(H, H - oy)), slice(max(0, -ox), min(W, W - ox))
+                if py.start < py.stop and px.start < px.stop:
+                    yield dy, dx, py, px, slice(py.start + oy, py.stop + oy), slice(px.start + ox, px.stop + ox)
+
+    k3 = np.array([1, 2, 1], dt) / f(4)
+    num, den = np.zeros((H, W), dt), np.zeros((H, W), dt)
+    for dy, dx, py, px, qy, qx in taps(1, 1):
+        k = k3[dy + 1] * k3[dx + 1]
+        num[py, px] += k * U[qy, qx]
+        den[py, px] += k
+    V = num / den
+    if d.iterations == 0:
+        return c, V
+    kern = np.array([1, 4, 6, 4, 1], dt) / f(16)
+    zs = f(d.sigma_depth) * np.maximum(z, f(1e-6))
+    sc2 = f(d.sigma_color) * f(d.sigma_color)
+    for i in range(d.iterations):
+        num, numv, den = np.zeros_like(img), np.zeros((H, W), dt), np.zeros((H, W), dt)
+        for dy, dx, py, px, qy, qx in taps(2, 1 << i):
+            h = kern[dy + 2] * kern[dx + 2]
+            if dx == 0 and dy == 0:
+                w = np.ones((H, W), dt)
+            else:
+                dc = img[py, px] - img[qy, qx]
+                dn = N[py, px] - N[qy, qx]
+                dz = z[py, px] - z[qy, qx]
+                wc = np.exp(-np.minimum(((dc[..., 0] ** 2 + dc[..., 1] ** 2) + dc[..., 2] ** 2)
+                                        / (sc2 * V[py, px] + f(1e-10)), f(80)))
+                wn = np.exp(-np.minimum(((dn[..., 0] ** 2 + dn[..., 1] ** 2) + dn[..., 2] ** 2)
+                                        / (f(d.sigma_normal) * f(d.sigma_normal)), f(80)))
+                wz = np.exp(-np.minimum((dz * dz) / (zs[py, px] * zs[py, px]), f(80)))
+                w = np.where(hit[py, px] == hit[qy, qx], (wc * wn) * wz, f(0))
+            hw = h * w
+            num[py, px] += hw[..., None] * img[qy, qx]
+            numv[py, px] += (hw * hw) * V[qy, qx]
+            den[py, px] += hw
+        img, V = num / den[..., None], numv / (den * den)
+    if d.demodulate:
+        img = img * m
+    assert img.dtype == dt and V.dtype == dt
+    return img, V
+
+
 class BDPTIntegrator:
     """GPU BDPT integrator with the reference's Integrator interface."""
 
@@ -1044,6 +1159,8 @@ class BDPTIntegrator:
         self._h = h
         self.rgb = None
         self.aov = None
+        self.batches = None  # render_batches' last planes
+        self.var = None      # batch_moments' last variance
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -1268,6 +1385,63 @@ class BDPTIntegrator:
             self.render_frame(window=SampleWindow(done, 1, n))
             done += n
             yield done, (self.rgb if done == spp else self.rgb * np.float32(spp / done))
+
+    def render_batches(self, n_batches: int, window: SampleWindow | None = None, row_offset: int = 0,
+                       row_stride: int = 1) -> np.ndarray:
+        """The frame (or the window's samples of it) as n_batches complete, independent estimates: a new
+        (n_batches, H, W, 3) array, plane b bdpt_render_window_host of batch_windows()[b] into zeros, with this
+        integrator's settings as render_frame passes them. The planes sum to render_frame(window=window) up to
+        the order of the float additions; batch_moments() turns them into that sum and its per-pixel variance.
+        Kept in self.batches."""
+        wins = batch_windows(self.config.spp, n_batches, window)
+        H, W = self.config.height, self.config.width
+        p = self.params(row_offset, row_stride, 0)
+        pp, dp = self._integrator_params()
+        out = np.zeros((len(wins), H, W, 3), np.float32)
+        for b, win in enumerate(wins):
+            w = win.c()
+            _check(lib().bdpt_render_window_host(self._h, ctypes.byref(p), ctypes.byref(w), pp and ctypes.byref(pp),
+                                                 dp and ctypes.byref(dp), out[b].ctypes.data))
+        self.batches = out
+        return out
+
+    def render_batches_device(self, n_batches: int, planes_ptr: int, stream_ptr: int = 0,
+                              window: SampleWindow | None = None, row_offset: int = 0, row_stride: int = 1) -> None:
+        """render_batches with bdpt_render_window: asynchronous, plane b ADDED to the b-th H * W * 3 floats of a
+        device buffer (zero it first)."""
+        wins = batch_windows(self.config.spp, n_batches, window)
+        p = self.params(row_offset, row_stride, 0)
+        pp, dp = self._integrator_params()
+        plane_bytes = self.config.height * self.config.width * 3 * 4
+        for b, win in enumerate(wins):
+            w = win.c()
+            _check(lib().bdpt_render_window(self._h, ctypes.byref(p), ctypes.byref(w), pp and ctypes.byref(pp),
+                                            dp and ctypes.byref(dp), ctypes.c_void_p(planes_ptr + b * plane_bytes),
+                                            ctypes.c_void_p(stream_ptr)))
+
+    def batch_moments(self, planes=None):
+        """bdpt_batch_moments_host of (K, H, W, 3) batch planes (default self.batches, render_batches' last):
+        (sum, var), both (H, W, 3): the frame of the batches' samples and the estimated variance of each of its
+        values. Also sets self.rgb = sum and self.var = var, what denoise_var() reads by default."""
+        if planes is None:
+            planes = getattr(self, "batches", None)
+            if planes is None:
+                raise BdptError("batch_moments: no planes given and render_batches has not run")
+        a = np.ascontiguousarray(planes, np.float32)
+        if a.ndim != 4 or a.shape[3] != 3:
+            raise BdptError(f"batch_moments: planes must be (n_batches, H, W, 3), got {a.shape}")
+        K, H, W = a.shape[:3]
+        s, v = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.float32)
+        _check(lib().bdpt_batch_moments_host(self._h, W, H, K, a.ctypes.data, s.ctypes.data, v.ctypes.data))
+        self.rgb, self.var = s, v
+        return s, v
+
+    def batch_moments_device(self, planes_ptr: int, n_batches: int, width: int, height: int, sum_ptr: int, var_ptr: int,
+                             stream_ptr: int = 0) -> None:
+        """bdpt_batch_moments: asynchronous, on device buffers (sum_ptr 0: the sum is not wanted)."""
+        _check(lib().bdpt_batch_moments(self._h, int(width), int(height), int(n_batches), ctypes.c_void_p(planes_ptr),
+                                        ctypes.c_void_p(sum_ptr or None), ctypes.c_void_p(var_ptr),
+                                        ctypes.c_void_p(stream_ptr)))
 
     def render_aov(self, row_offset: int = 0, row_stride: int = 1, window: SampleWindow | None = None) -> np.ndarray:
         """bdpt_render_aov_host: the first-hit feature buffers of the (sharded, windowed) frame
@@ -1575,6 +1749,44 @@ class BDPTIntegrator:
         _check(lib().bdpt_denoise(self._h, self.config.width, self.config.height, ctypes.c_void_p(rgb_ptr),
                                   ctypes.c_void_p(aov_ptr), ctypes.c_void_p(out_ptr), ctypes.byref(d),
                                   ctypes.c_void_p(stream_ptr)))
+
+    def denoise_var(self, rgb=None, var=None, aov=None, samples_done: int | None = None, return_variance: bool = False,
+                    **params):
+        """bdpt_denoise_var_host of rgb (default self.rgb) with its per-pixel variance var (default self.var,
+        batch_moments' last) guided by aov (default self.aov): a new (H, W, 3) array; return_variance: (filtered,
+        residual variance (H, W)). samples_done as denoise(); params: DenoiseSettings fields over
+        denoise_var_settings(), or settings=DenoiseSettings(...)."""
+        H, W = self.config.height, self.config.width
+        settings = params.pop("settings", None) or denoise_var_settings()
+        if params:
+            from dataclasses import replace
+            settings = replace(settings, **params)
+        if samples_done is not None and samples_done < 1:
+            raise ValueError("denoise_var: samples_done must be >= 1")
+        norm = 1.0 if samples_done is None else self.config.spp / samples_done
+        if var is None and getattr(self, "var", None) is None:
+            raise BdptError("denoise_var: no var given and batch_moments has not run")
+        c = np.ascontiguousarray(self.rgb if rgb is None else rgb, np.float32)
+        v = np.ascontiguousarray(self.var if var is None else var, np.float32)
+        a = np.ascontiguousarray(self.aov if aov is None else aov, np.float32)
+        if c.size != W * H * 3 or v.size != W * H * 3 or a.size != W * H * 8:
+            raise BdptError(f"denoise_var: rgb / var / aov have {c.size} / {v.size} / {a.size} floats, expected "
+                            f"{W * H * 3} / {W * H * 3} / {W * H * 8}")
+        out = np.zeros((H, W, 3), np.float32)
+        out_var = np.zeros((H, W), np.float32) if return_variance else None
+        d = settings.c(norm)
+        _check(lib().bdpt_denoise_var_host(self._h, W, H, c.ctypes.data, v.ctypes.data, a.ctypes.data, out.ctypes.data,
+                                           None if out_var is None else out_var.ctypes.data, ctypes.byref(d)))
+        return (out, out_var) if return_variance else out
+
+    def denoise_var_device(self, rgb_ptr: int, var_ptr: int, aov_ptr: int, out_ptr: int, out_var_ptr: int = 0,
+                           stream_ptr: int = 0, norm: float = 1.0, settings: "DenoiseSettings | None" = None) -> None:
+        """bdpt_denoise_var: asynchronous, on device buffers (out_var_ptr 0: the residual variance is not wanted)."""
+        d = (settings or denoise_var_settings()).c(norm)
+        _check(lib().bdpt_denoise_var(self._h, self.config.width, self.config.height, ctypes.c_void_p(rgb_ptr),
+                                      ctypes.c_void_p(var_ptr), ctypes.c_void_p(aov_ptr), ctypes.c_void_p(out_ptr),
+                                      ctypes.c_void_p(out_var_ptr or None), ctypes.byref(d),
+                                      ctypes.c_void_p(stream_ptr)))
 
     def denoise_planes(self, planes, aov=None, mode="shared", guide=None, samples_done: int | None = None,
                        return_guide: bool = False, **params):

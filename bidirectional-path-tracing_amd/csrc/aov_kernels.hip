@@ -298,6 +298,186 @@ __global__ __launch_bounds__(kDnX* kDnY) void denoise_planes_iter_kernel(int W, 
     }
 }
 
+// ------------------------------------------------------------ batch moments
+// bdpt_batch_moments (bdpt_amd.h): K planes of n = W * H * 3 floats, each a complete
+// estimate of the frame from its own samples. Per float, every operation float32 and rounded on its
+// own (the build's -ffp-contract=off; a true division):
+//   S = plane_0 + plane_1 + ...  (ascending: planes_sum_kernel's loop, so layers_compose_kernel's bits)
+//   mu = S / K;   Q = d_0 d_0 + d_1 d_1 + ...  (ascending, d_b = plane_b - mu);   var = Q * c
+// with c = K / (K - 1) formed on the host. No atomics: the same bits every run and the bits of that
+// loop on the host. The planes are read twice (the second pass from L2) rather than kept in a
+// runtime-indexed register array. A lane owns UNIT consecutive floats: UNIT 4 reads and writes 16
+// bytes (n a multiple of 4 and 16-byte aligned pointers: launch_batch_moments decides), UNIT 1 dwords.
+// sum: null = not wanted.
+template <int UNIT>
+__global__ __launch_bounds__(256) void batch_moments_kernel(const float* __restrict__ planes, size_t n, int K, float Kf,
+                                                            float c, float* __restrict__ sum, float* __restrict__ var) {
+    const size_t units = n / UNIT;
+    for (size_t u = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; u < units; u += static_cast<size_t>(gridDim.x) * 256) {
+        float v[UNIT], S[UNIT], mu[UNIT], Q[UNIT];
+        auto load = [&](int b) {
+            const float* src = planes + static_cast<size_t>(b) * n + u * UNIT;
+            if constexpr (UNIT == 4) {
+                const float4 t = gld4(reinterpret_cast<const float4*>(src));
+                v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+            } else {
+                v[0] = gld1(src);
+            }
+        };
+        for (int b = 0; b < K; b++) {  // (wave-uniform, as the second pass)
+            load(b);
+#pragma unroll
+            for (int j = 0; j < UNIT; j++) S[j] = b == 0 ? v[j] : S[j] + v[j];
+        }
+#pragma unroll
+        for (int j = 0; j < UNIT; j++) mu[j] = S[j] / Kf;
+        for (int b = 0; b < K; b++) {
+            load(b);
+#pragma unroll
+            for (int j = 0; j < UNIT; j++) {
+                const float d = v[j] - mu[j];
+                Q[j] = b == 0 ? d * d : Q[j] + d * d;
+            }
+        }
+        if constexpr (UNIT == 4) {
+            if (sum) gst4(reinterpret_cast<float4*>(sum + u * UNIT), make_float4(S[0], S[1], S[2], S[3]));
+            gst4(reinterpret_cast<float4*>(var + u * UNIT),
+                 make_float4(Q[0] * c, Q[1] * c, Q[2] * c, Q[3] * c));
+        } else {
+            if (sum) gst1(sum + u, S[0]);
+            gst1(var + u, Q[0] * c);
+        }
+    }
+}
+
+// ------------------------------------------------- filter, variance-normalised
+// bdpt_denoise_var (bdpt_amd.h): the a-trous filter whose colour weight measures a
+// difference in standard deviations of the centre pixel, the variance carried in .w of the float4
+// images and filtered with the squared weights. The shape is denoise_iter_kernel's (one lane per
+// pixel, 32 x 8 blocks, three 16-byte loads per tap) and the guide expressions are restated from it
+// and from denoise_prepare_kernel, so those kernels' device code stays what it was.
+
+// Guides and I_0 as denoise_prepare_kernel forms them; img.w = U, the channel-summed variance of the
+// pixel in the filter's domain: v = var * norm^2, divided by m^2 per channel when demodulated.
+__global__ __launch_bounds__(kDnX* kDnY) void denoise_var_prepare_kernel(int W, int H, const float* __restrict__ color,
+                                                                         const float* __restrict__ var,
+                                                                         const float* __restrict__ aov, float norm,
+                                                                         int demodulate, float4* __restrict__ guide,
+                                                                         float4* __restrict__ img) {
+    const int x = blockIdx.x * kDnX + threadIdx.x, y = blockIdx.y * kDnY + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t p = static_cast<size_t>(y) * W + x;
+    float a[kAovChannels];
+#pragma unroll
+    for (int c = 0; c < kAovChannels; c++) a[c] = gld1(aov + kAovChannels * p + c) * norm;
+    const float cov = a[7];
+    f3 alb = mk(1.f, 1.f, 1.f), n = mk(0.f, 0.f, 0.f);
+    float z = 0.f;
+    if (cov > 0.f) {
+        alb = mk(a[0] / cov, a[1] / cov, a[2] / cov);
+        n = mk(a[3] / cov, a[4] / cov, a[5] / cov);
+        z = a[6] / cov;
+    }
+    const float n2 = norm * norm;
+    f3 c = mk(gld1(color + 3 * p) * norm, gld1(color + 3 * p + 1) * norm, gld1(color + 3 * p + 2) * norm);
+    f3 v = mk(gld1(var + 3 * p) * n2, gld1(var + 3 * p + 1) * n2, gld1(var + 3 * p + 2) * n2);
+    if (demodulate) {
+        const f3 m = mk(fmaxf(alb.x, 1e-3f), fmaxf(alb.y, 1e-3f), fmaxf(alb.z, 1e-3f));
+        c = mk(c.x / m.x, c.y / m.y, c.z / m.z);
+        v = mk(v.x / (m.x * m.x), v.y / (m.y * m.y), v.z / (m.z * m.z));
+    }
+    gst4(guide + 2 * p, make_float4(alb.x, alb.y, alb.z, z));
+    gst4(guide + 2 * p + 1, make_float4(n.x, n.y, n.z, cov > 0.f ? 1.f : 0.f));
+    gst4(img + p, make_float4(c.x, c.y, c.z, (v.x + v.y) + v.z));
+}
+
+// V_0 = the 3 x 3 blur of U with the outer product of [1, 2, 1] / 4, renormalised over the taps inside
+// the image (dy outer, dx inner): dst = (I_0, V_0). A single pixel's variance from K batches is itself
+// noisy; its neighbourhood's is what the weights divide by. out_var (iterations == 0): V_0, or null.
+__global__ __launch_bounds__(kDnX* kDnY) void denoise_var_blur_kernel(int W, int H, const float4* __restrict__ src,
+                                                                      float4* __restrict__ dst,
+                                                                      float* __restrict__ out_var) {
+    const int x = blockIdx.x * kDnX + threadIdx.x, y = blockIdx.y * kDnY + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t p = static_cast<size_t>(y) * W + x;
+    const float4 ip = gld4(src + p);
+    float su = 0.f, sk = 0.f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+        const int qy = y + dy;
+        if (qy < 0 || qy >= H) continue;
+        const float ky = (dy == 0 ? 2.f : 1.f) * 0.25f;
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            const int qx = x + dx;
+            if (qx < 0 || qx >= W) continue;
+            const float k = ky * ((dx == 0 ? 2.f : 1.f) * 0.25f);
+            su += k * gld1(&src[static_cast<size_t>(qy) * W + qx].w), sk += k;
+        }
+    }
+    const float v0 = su / sk;
+    gst4(dst + p, make_float4(ip.x, ip.y, ip.z, v0));
+    if (out_var) gst1(out_var + p, v0);
+}
+
+// One iteration with step s: denoise_iter_kernel's taps, h, w_n, w_z, w_cov and order, with
+//   w_c = exp(-min(|I(p) - I(q)|^2 / (sc2 V(p) + 1e-10), 80)),  sc2 = sigma_color^2 (no 2^-i: V shrinks
+// by itself), the quotient formed as a product with the pixel's one reciprocal as inv_c is there;
+//   I'(p) = sum hw I(q) / sum hw,   V'(p) = sum (hw hw) V(q) / ((sum hw) (sum hw)).
+// LAST: out = I' (times max(albedo, 1e-3) when demodulated), out_var (null: not wanted) = V'.
+template <bool LAST>
+__global__ __launch_bounds__(kDnX* kDnY) void denoise_var_iter_kernel(int W, int H, int s, float sc2, float inv_n,
+                                                                      float sigma_z, int demodulate,
+                                                                      const float4* __restrict__ guide,
+                                                                      const float4* __restrict__ src,
+                                                                      float4* __restrict__ dst, float* __restrict__ out,
+                                                                      float* __restrict__ out_var) {
+    const int x = blockIdx.x * kDnX + threadIdx.x, y = blockIdx.y * kDnY + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t p = static_cast<size_t>(y) * W + x;
+    const float4 ip = gld4(src + p), g0 = gld4(guide + 2 * p), g1 = gld4(guide + 2 * p + 1);
+    const float zs = sigma_z * fmaxf(g0.w, 1e-6f);
+    const float inv_z = 1.f / (zs * zs);
+    const float inv_c = 1.f / (sc2 * ip.w + 1e-10f);
+    float sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f, sw = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + dy * s;
+        if (qy < 0 || qy >= H) continue;
+        const float hy = (dy == 0 ? 6.f : (dy == -1 || dy == 1 ? 4.f : 1.f)) * 0.0625f;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + dx * s;
+            if (qx < 0 || qx >= W) continue;
+            const float hx = (dx == 0 ? 6.f : (dx == -1 || dx == 1 ? 4.f : 1.f)) * 0.0625f;
+            const size_t q = static_cast<size_t>(qy) * W + qx;
+            const float4 iq = gld4(src + q);
+            float w = 1.f;
+            if (dx != 0 || dy != 0) {
+                const float4 h0 = gld4(guide + 2 * q), h1 = gld4(guide + 2 * q + 1);
+                const float cr = ip.x - iq.x, cg = ip.y - iq.y, cb = ip.z - iq.z;
+                const float nx = g1.x - h1.x, ny = g1.y - h1.y, nz = g1.z - h1.z;
+                const float dz = g0.w - h0.w;
+                const float wc = expf(-fminf(((cr * cr + cg * cg) + cb * cb) * inv_c, 80.f));
+                const float wn = expf(-fminf(((nx * nx + ny * ny) + nz * nz) * inv_n, 80.f));
+                const float wz = expf(-fminf((dz * dz) * inv_z, 80.f));
+                w = g1.w == h1.w ? (wc * wn) * wz : 0.f;
+            }
+            const float hw = (hy * hx) * w;
+            sr += hw * iq.x, sg += hw * iq.y, sb += hw * iq.z, sv += (hw * hw) * iq.w, sw += hw;
+        }
+    }
+    float r = sr / sw, g = sg / sw, b = sb / sw;
+    const float vn = sv / (sw * sw);
+    if (LAST) {
+        if (demodulate) r *= fmaxf(g0.x, 1e-3f), g *= fmaxf(g0.y, 1e-3f), b *= fmaxf(g0.z, 1e-3f);
+        gst1(out + 3 * p, r), gst1(out + 3 * p + 1, g), gst1(out + 3 * p + 2, b);
+        if (out_var) gst1(out_var + p, vn);
+    } else {
+        gst4(dst + p, make_float4(r, g, b, vn));
+    }
+}
+
 // ------------------------------------------------------------ path-length layers
 // out[i] = the sum over the layers l in `mask` of layers[l * n + i] (n = W * H * 3 floats per
 // plane, bdpt_render_layers), float32 additions in ascending layer order starting from the
@@ -531,6 +711,44 @@ hipError_t launch_denoise_iter(int W, int H, int step, float inv_c, float inv_n,
         hipLaunchKernelGGL(dev::denoise_iter_kernel<false>, dn_grid(W, H), dim3(dev::kDnX, dev::kDnY), 0, st, W, H,
                            step, inv_c, inv_n, sigma_z, demodulate, static_cast<const float4*>(guide),
                            static_cast<const float4*>(src), static_cast<float4*>(dst), out);
+    return hipGetLastError();
+}
+
+// n floats per plane, K planes; c = K / (K - 1) in float; sum may be null.
+hipError_t launch_batch_moments(const float* planes, size_t n, int K, float c, float* sum, float* var, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(planes) | reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(var);
+    const bool vec = n % 4 == 0 && ptrs % 16 == 0;  // (n % 4 == 0 keeps every plane's start aligned too)
+    const size_t units = n / (vec ? 4 : 1);
+    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((units + 255) / 256, 4096));
+    const float Kf = static_cast<float>(K);
+    if (vec) hipLaunchKernelGGL(dev::batch_moments_kernel<4>, dim3(blocks), dim3(256), 0, st, planes, n, K, Kf, c, sum, var);
+    else hipLaunchKernelGGL(dev::batch_moments_kernel<1>, dim3(blocks), dim3(256), 0, st, planes, n, K, Kf, c, sum, var);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_var_prepare(int W, int H, const float* color, const float* var, const float* aov, float norm,
+                                      int demodulate, void* guide, void* img, hipStream_t st) {
+    hipLaunchKernelGGL(dev::denoise_var_prepare_kernel, dn_grid(W, H), dim3(dev::kDnX, dev::kDnY), 0, st, W, H, color, var,
+                       aov, norm, demodulate, static_cast<float4*>(guide), static_cast<float4*>(img));
+    return hipGetLastError();
+}
+// out_var: V_0 as W * H floats too (iterations == 0), or null.
+hipError_t launch_denoise_var_blur(int W, int H, const void* src, void* dst, float* out_var, hipStream_t st) {
+    hipLaunchKernelGGL(dev::denoise_var_blur_kernel, dn_grid(W, H), dim3(dev::kDnX, dev::kDnY), 0, st, W, H,
+                       static_cast<const float4*>(src), static_cast<float4*>(dst), out_var);
+    return hipGetLastError();
+}
+// sc2 = sigma_color^2. last: the result goes to out and (unless null) out_var, not to dst.
+hipError_t launch_denoise_var_iter(int W, int H, int step, float sc2, float inv_n, float sigma_z, int demodulate,
+                                   const void* guide, const void* src, void* dst, float* out, float* out_var, bool last,
+                                   hipStream_t st) {
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dn_grid(W, H), dim3(dev::kDnX, dev::kDnY), 0, st, W, H, step, sc2, inv_n, sigma_z,
+                           demodulate, static_cast<const float4*>(guide), static_cast<const float4*>(src),
+                           static_cast<float4*>(dst), out, out_var);
+    };
+    last ? go(dev::denoise_var_iter_kernel<true>) : go(dev::denoise_var_iter_kernel<false>);
     return hipGetLastError();
 }
 

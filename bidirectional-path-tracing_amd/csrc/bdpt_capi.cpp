@@ -80,6 +80,15 @@ hipError_t launch_denoise_planes_prepare(int W, int H, const float* planes, int 
 hipError_t launch_denoise_planes_iter(int W, int H, int step, float inv_c, float inv_n, float sigma_z, int demodulate,
                                       int cnt, const void* guide, const void* b, const void* src, void* dst, float* out,
                                       bool last, hipStream_t st);
+// aov_kernels.hip: per-pixel sum and variance across K batch planes of n floats (c = K / (K - 1); sum may be null)
+hipError_t launch_batch_moments(const float* planes, size_t n, int K, float c, float* sum, float* var, hipStream_t st);
+// aov_kernels.hip: the a-trous filter with a variance-normalised colour weight (the variance rides in the images' .w)
+hipError_t launch_denoise_var_prepare(int W, int H, const float* color, const float* var, const float* aov, float norm,
+                                      int demodulate, void* guide, void* img, hipStream_t st);
+hipError_t launch_denoise_var_blur(int W, int H, const void* src, void* dst, float* out_var, hipStream_t st);
+hipError_t launch_denoise_var_iter(int W, int H, int step, float sc2, float inv_n, float sigma_z, int demodulate,
+                                   const void* guide, const void* src, void* dst, float* out, float* out_var, bool last,
+                                   hipStream_t st);
 // aov_kernels.hip: a masked sum of path-length layers (planes of n floats)
 hipError_t launch_layers_compose(const float* layers, size_t n, uint64_t mask, float* out, hipStream_t st);
 // aov_kernels.hip: light-group planes (n floats each) recombined with per-group RGB gains (host, n_groups x 3)
@@ -2331,6 +2340,18 @@ static int check_denoise(int32_t width, int32_t height, const float* color, cons
     return BDPT_OK;
 }
 
+// The filter scratch of bdpt_denoise and bdpt_denoise_var (packed guides and the two images, 64 bytes per
+// pixel), grown when a larger frame comes.
+static int reserve_denoise_scratch(bdpt_ctx* c, size_t px) {
+    if (px <= c->dn_pixels) return BDPT_OK;
+    c->dn_pixels = 0;
+    HIP_TRY(c->dn_guide.reserve(px * 32));
+    HIP_TRY(c->dn_img[0].reserve(px * 16));
+    HIP_TRY(c->dn_img[1].reserve(px * 16));
+    c->dn_pixels = px;
+    return BDPT_OK;
+}
+
 int bdpt_denoise(bdpt_ctx* c, int32_t width, int32_t height, const float* color, const float* aov, float* out,
                  const bdpt_denoise_params* d, void* hip_stream) {
     if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
@@ -2340,13 +2361,7 @@ int bdpt_denoise(bdpt_ctx* c, int32_t width, int32_t height, const float* color,
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     const size_t px = static_cast<size_t>(width) * height;
     if ((rc = begin_use(c, st))) return rc;
-    if (d->iterations > 0 && px > c->dn_pixels) {
-        c->dn_pixels = 0;
-        HIP_TRY(c->dn_guide.reserve(px * 32));
-        HIP_TRY(c->dn_img[0].reserve(px * 16));
-        HIP_TRY(c->dn_img[1].reserve(px * 16));
-        c->dn_pixels = px;
-    }
+    if (d->iterations > 0 && (rc = reserve_denoise_scratch(c, px))) return rc;
     if ((rc = begin_timed(c, st))) return rc;
     if (d->iterations == 0) {
         HIP_TRY(launch_denoise_scale(px * 3, color, d->norm, out, st));
@@ -2376,6 +2391,128 @@ int bdpt_denoise_host(bdpt_ctx* c, int32_t width, int32_t height, const float* c
     HIP_TRY(hipMemcpyAsync(da, aov, px * 8 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if ((rc = bdpt_denoise(c, width, height, dc, da, dout, d, c->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(out, dout, px * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+// ---- per-pixel moments across sample batches, and the filter guided by them (aov_kernels.hip) ----
+struct FloatSpan {
+    const char* name;
+    const float* p;
+    size_t floats;
+};
+static bool spans_overlap(const FloatSpan& a, const FloatSpan& b) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
+    return a.p && b.p && a0 < b0 + b.floats * sizeof(float) && b0 < a0 + a.floats * sizeof(float);
+}
+
+static int check_batch_moments(int32_t width, int32_t height, int32_t n_batches, const float* planes, const float* out_sum,
+                               const float* out_var) {
+    const std::string entry = "bdpt_batch_moments";
+    if (width <= 0 || height <= 0) return fail(BDPT_ERR_INVALID, entry + ": width/height must be > 0");
+    if (n_batches < 2 || n_batches > 64) return fail(BDPT_ERR_INVALID, entry + ": n_batches must be in [2, 64]");
+    const uint64_t px = static_cast<uint64_t>(width) * static_cast<uint64_t>(height);
+    if (px >= (1ull << 30) || static_cast<uint64_t>(n_batches) * px >= (1ull << 30))
+        return fail(BDPT_ERR_INVALID, entry + ": n_batches * width * height must be below 2^30");
+    if (!planes) return fail(BDPT_ERR_INVALID, entry + ": planes must not be NULL");
+    if (!out_var) return fail(BDPT_ERR_INVALID, entry + ": out_var must not be NULL");
+    const FloatSpan in = {"planes", planes, n_batches * px * 3};
+    const FloatSpan sum = {"out_sum", out_sum, px * 3}, var = {"out_var", out_var, px * 3};
+    if (spans_overlap(sum, in)) return fail(BDPT_ERR_INVALID, entry + ": out_sum overlaps planes");
+    if (spans_overlap(var, in)) return fail(BDPT_ERR_INVALID, entry + ": out_var overlaps planes");
+    if (spans_overlap(var, sum)) return fail(BDPT_ERR_INVALID, entry + ": out_var overlaps out_sum");
+    return BDPT_OK;
+}
+
+int bdpt_batch_moments(bdpt_ctx* c, int32_t width, int32_t height, int32_t n_batches, const float* planes, float* out_sum,
+                       float* out_var, void* hip_stream) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_batch_moments(width, height, n_batches, planes, out_sum, out_var);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if ((rc = begin_use(c, st))) return rc;
+    if ((rc = begin_timed(c, st))) return rc;
+    const float scale = static_cast<float>(n_batches) / static_cast<float>(n_batches - 1);
+    HIP_TRY(launch_batch_moments(planes, static_cast<size_t>(width) * height * 3, n_batches, scale, out_sum, out_var, st));
+    return end_timed(c, st, 0, 1);
+}
+
+int bdpt_batch_moments_host(bdpt_ctx* c, int32_t width, int32_t height, int32_t n_batches, const float* planes,
+                            float* out_sum, float* out_var) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_batch_moments(width, height, n_batches, planes, out_sum, out_var);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = static_cast<size_t>(width) * height * 3, all = n * n_batches;
+    HIP_TRY(c->tmp_fb.reserve((all + 2 * n) * sizeof(float)));
+    float *dp = c->tmp_fb, *dsum = dp + all, *dvar = dsum + n;  // planes, out_sum, out_var
+    HIP_TRY(hipMemcpyAsync(dp, planes, all * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((rc = bdpt_batch_moments(c, width, height, n_batches, dp, out_sum ? dsum : nullptr, dvar, c->stream))) return rc;
+    if (out_sum) HIP_TRY(hipMemcpyAsync(out_sum, dsum, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_var, dvar, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+static int check_denoise_var(int32_t width, int32_t height, const float* color, const float* var, const float* aov,
+                             const float* out, const float* out_var, const bdpt_denoise_params* d) {
+    const std::string entry = "bdpt_denoise_var";
+    if (!color || !aov || !out || !d) return fail(BDPT_ERR_INVALID, "null argument");
+    if (!var) return fail(BDPT_ERR_INVALID, entry + ": var must not be NULL");
+    if (int rc = check_denoise_fields(entry, width, height, d)) return rc;
+    const size_t px = static_cast<size_t>(width) * height;
+    const FloatSpan in[] = {{"color", color, px * 3}, {"var", var, px * 3}, {"aov", aov, px * 8}};
+    const FloatSpan outs[] = {{"out", out, px * 3}, {"out_var", out_var, px}};
+    for (const FloatSpan& o : outs)
+        for (const FloatSpan& i : in)
+            if (spans_overlap(o, i)) return fail(BDPT_ERR_INVALID, entry + ": " + o.name + " overlaps " + i.name);
+    if (spans_overlap(outs[1], outs[0])) return fail(BDPT_ERR_INVALID, entry + ": out_var overlaps out");
+    return BDPT_OK;
+}
+
+int bdpt_denoise_var(bdpt_ctx* c, int32_t width, int32_t height, const float* color, const float* var, const float* aov,
+                     float* out, float* out_var, const bdpt_denoise_params* d, void* hip_stream) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_denoise_var(width, height, color, var, aov, out, out_var, d);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    const size_t px = static_cast<size_t>(width) * height;
+    const int it = d->iterations;
+    if ((rc = begin_use(c, st))) return rc;
+    if ((it > 0 || out_var) && (rc = reserve_denoise_scratch(c, px))) return rc;
+    if ((rc = begin_timed(c, st))) return rc;
+    if (it == 0) {
+        HIP_TRY(launch_denoise_scale(px * 3, color, d->norm, out, st));
+        if (!out_var) return end_timed(c, st, 0, 1);
+    }
+    // (I_0, U) in image 0, (I_0, V_0) in image 1; iteration i then reads image (i + 1) & 1 and writes image i & 1
+    HIP_TRY(launch_denoise_var_prepare(width, height, color, var, aov, d->norm, d->demodulate, c->dn_guide, c->dn_img[0], st));
+    HIP_TRY(launch_denoise_var_blur(width, height, c->dn_img[0], c->dn_img[1], it == 0 ? out_var : nullptr, st));
+    const float sc2 = d->sigma_color * d->sigma_color, inv_n = 1.f / (d->sigma_normal * d->sigma_normal);
+    for (int i = 0; i < it; i++)
+        HIP_TRY(launch_denoise_var_iter(width, height, 1 << i, sc2, inv_n, d->sigma_depth, d->demodulate, c->dn_guide,
+                                        c->dn_img[(i + 1) & 1], c->dn_img[i & 1], out, out_var, i + 1 == it, st));
+    return end_timed(c, st, 0, it == 0 ? 3 : it + 2);
+}
+
+int bdpt_denoise_var_host(bdpt_ctx* c, int32_t width, int32_t height, const float* color, const float* var,
+                          const float* aov, float* out, float* out_var, const bdpt_denoise_params* d) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_denoise_var(width, height, color, var, aov, out, out_var, d);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t px = static_cast<size_t>(width) * height;
+    HIP_TRY(c->tmp_fb.reserve(px * 18 * sizeof(float)));
+    // color, var, aov, out, out_var (16-byte aligned or not: scalar loads and stores)
+    float *dc = c->tmp_fb, *dv = dc + px * 3, *da = dv + px * 3, *dout = da + px * 8, *dov = dout + px * 3;
+    HIP_TRY(hipMemcpyAsync(dc, color, px * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dv, var, px * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(da, aov, px * 8 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((rc = bdpt_denoise_var(c, width, height, dc, dv, da, dout, out_var ? dov : nullptr, d, c->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout, px * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out_var) HIP_TRY(hipMemcpyAsync(out_var, dov, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BDPT_OK;
 }

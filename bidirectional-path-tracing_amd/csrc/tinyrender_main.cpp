@@ -51,6 +51,14 @@
 // <out>_denoised.exr, unless --denoise is given, whose file that is. The planes' own files are the same
 // bytes with or without it. Without a plane flag, with another value or with an empty --sample-window it
 // is refused before any device is used.
+// --batches K (2..64, any of the three integrators; one device, no plane flag) renders the frame as K
+// batches, the windows (first + b stride, stride K, count / K) of --sample-window's window or of the whole
+// spp, whose count must be a multiple of K. The main EXR is bdpt_batch_moments_host's sum of them (the plain
+// frame up to the order of the float additions), and <out>_variance.exr the per-pixel variance of that
+// sum, three channels. --denoise-var[=ITER] (with --batches; not with --denoise, whose file it writes) also
+// renders the feature buffers over the same samples and writes <out>_denoised.exr from
+// bdpt_denoise_var_host (the header's BDPT_DENOISE_VAR_* defaults, ITER iterations 0..8). Combines with
+// --aov. Each misuse is refused, the flag named, before any device is used.
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
@@ -106,7 +114,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Syntax: %s <scene.toml> [nogui] [--width W --height H --spp N --rr D --device K "
                              "--out FILE.exr --seed S --gpus N --devices a,b,... --shard samples|rows "
-                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted] --cross --denoise-planes[=own|shared]]\n", argv[0]);
+                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted] --cross --denoise-planes[=own|shared] --batches K --denoise-var[=ITER]]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string toml = argv[1];
@@ -124,6 +132,9 @@ int main(int argc, char** argv) {
     int strategies = -1;        // --strategies[=unweighted]: BDPT_STRATEGIES_* (-1: none)
     bool cross = false;         // --cross: the groups crossed with the layers or the strategies
     int denoise_planes = -1;    // --denoise-planes[=own|shared]: BDPT_DENOISE_PLANES_* (-1: none)
+    int batches = 0;            // --batches K (0: none)
+    bool want_denoise_var = false;  // --denoise-var[=ITER]
+    int denoise_var_iterations = BDPT_DENOISE_VAR_ITERATIONS;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -176,6 +187,30 @@ int main(int argc, char** argv) {
             }
             want_denoise = true;
             denoise_iterations = static_cast<int>(n);
+        } else if (a == "--denoise-var") {
+            want_denoise_var = true;
+        } else if (a.compare(0, 14, "--denoise-var=") == 0) {
+            const char* v = argv[i] + 14;
+            char* end = nullptr;
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 0 || n > 8) {
+                std::fprintf(stderr, "--denoise-var=%s: the iteration count must be an integer in [0, 8]\n", v);
+                return EXIT_FAILURE;
+            }
+            want_denoise_var = true;
+            denoise_var_iterations = static_cast<int>(n);
+        } else if (a.rfind("--denoise-var", 0) == 0) {
+            std::fprintf(stderr, "%s: --denoise-var takes no value or =ITER\n", a.c_str());
+            return EXIT_FAILURE;
+        } else if (a == "--batches") {
+            const char* v = next("--batches");
+            char* end = nullptr;
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 2 || n > 64) {
+                std::fprintf(stderr, "--batches %s: the batch count must be an integer in [2, 64]\n", v);
+                return EXIT_FAILURE;
+            }
+            batches = static_cast<int>(n);
         } else if (a == "--denoise-planes" || a == "--denoise-planes=shared") {
             denoise_planes = BDPT_DENOISE_PLANES_SHARED;
         } else if (a == "--denoise-planes=own") {
@@ -236,6 +271,23 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--denoise-planes of an empty --sample-window (count 0): there is no sample to normalise by\n");
         return EXIT_FAILURE;
     }
+    if (want_denoise_var && !batches) {
+        std::fprintf(stderr, "--denoise-var filters with the variance across batches: give --batches K\n");
+        return EXIT_FAILURE;
+    }
+    if (want_denoise_var && want_denoise) {
+        std::fprintf(stderr, "--denoise-var and --denoise both write <out>_denoised.exr: give one of them\n");
+        return EXIT_FAILURE;
+    }
+    if (batches && !devices.empty()) {
+        std::fprintf(stderr, "--batches renders on one device (not with --gpus / --devices)\n");
+        return EXIT_FAILURE;
+    }
+    if (batches && (layers || light_groups || strategies >= 0 || cross || denoise_planes >= 0)) {
+        std::fprintf(stderr, "--batches splits the frame by samples: not with --layers, --light-groups, --strategies, "
+                             "--cross or --denoise-planes\n");
+        return EXIT_FAILURE;
+    }
     if (shard_given && devices.empty()) {
         std::fprintf(stderr, "--shard applies to a multi-device render (--gpus N / --devices a,b,...)\n");
         return EXIT_FAILURE;
@@ -289,6 +341,15 @@ int main(int argc, char** argv) {
         return EXIT_FAILURE;
     }
 
+    if (batches) {  // equal batches: what the variance formula assumes
+        const int count = windowed ? window.count : cfg.spp;
+        if (count < 1 || count % batches != 0) {
+            std::fprintf(stderr, "--batches %d: the %s (%d) must be a positive multiple of the batch count\n", batches,
+                         windowed ? "--sample-window count" : "spp", count);
+            return EXIT_FAILURE;
+        }
+    }
+
     bdpt_scene* scene = nullptr;
     if (bdpt_scene_load_obj(cfg.obj_file, &scene) != BDPT_OK) return die("Scene::load");
     int32_t n_emitters = 0;
@@ -324,17 +385,30 @@ int main(int argc, char** argv) {
     std::vector<float> rgb(static_cast<size_t>(cfg.width) * cfg.height * 3, 0.f);  // Integrator::init: rgb->clear()
 
     const bdpt_sample_window* const win = windowed ? &window : nullptr;  // null: every sample
+    // --batches: the K planes (plane b: the window's samples b, b + K, ...), then their sum in rgb and its variance
+    std::vector<float> batch_planes, variance;
+    auto render_window = [&](const bdpt_path_params* pp, const bdpt_direct_params* dp) -> int {
+        if (!batches) return bdpt_render_window_host(ctx, &p, win, pp, dp, rgb.data());
+        const bdpt_sample_window base = windowed ? window : bdpt_sample_window{0, 1, cfg.spp};
+        batch_planes.assign(rgb.size() * batches, 0.f);
+        for (int b = 0; b < batches; b++) {
+            const bdpt_sample_window w = {base.first + b * base.stride, base.stride * batches, base.count / batches};
+            if (const int rc = bdpt_render_window_host(ctx, &p, &w, pp, dp, batch_planes.data() + rgb.size() * b)) return rc;
+        }
+        variance.resize(rgb.size());
+        return bdpt_batch_moments_host(ctx, cfg.width, cfg.height, batches, batch_planes.data(), rgb.data(), variance.data());
+    };
     const auto t0 = std::chrono::high_resolution_clock::now();
     if (path) {
         if (rr > 0) cfg.path.rr_depth = rr;
         p.rr_depth = 1;  // unused by the path tracer
         const int rc = multi ? bdpt_multi_render_host(multi, &p, &cfg.path, nullptr, rgb.data())
-                             : bdpt_render_window_host(ctx, &p, win, &cfg.path, nullptr, rgb.data());
+                             : render_window(&cfg.path, nullptr);
         if (rc != BDPT_OK) return die("render (path)");
     } else if (direct) {
         p.rr_depth = 1;  // unused by the direct integrator
         const int rc = multi ? bdpt_multi_render_host(multi, &p, nullptr, &cfg.direct, rgb.data())
-                             : bdpt_render_window_host(ctx, &p, win, nullptr, &cfg.direct, rgb.data());
+                             : render_window(nullptr, &cfg.direct);
         if (rc != BDPT_OK) {
             if (cfg.direct.sampling_strategy == 0) {  // direct.h:460-461
                 std::printf("Error: wrong strategy\n");
@@ -343,7 +417,7 @@ int main(int argc, char** argv) {
             return die("render (direct)");
         }
     } else if ((multi ? bdpt_multi_render_host(multi, &p, nullptr, nullptr, rgb.data())
-                      : bdpt_render_window_host(ctx, &p, win, nullptr, nullptr, rgb.data())) != BDPT_OK) {
+                      : render_window(nullptr, nullptr)) != BDPT_OK) {
         return die("render (bdpt)");
     }
     const auto t1 = std::chrono::high_resolution_clock::now();
@@ -358,7 +432,12 @@ int main(int argc, char** argv) {
     const std::string exr = out.empty() ? exr_path_of(toml) : out;
     if (bdpt_save_exr(rgb.data(), cfg.width, cfg.height, exr.c_str()) != BDPT_OK) return die("saveEXR");
     std::printf("\nSaved EXR image to %s\n", exr.c_str());  // utils.h:149
-    if (want_aov || want_denoise) {
+    if (batches) {
+        const std::string side = side_path(exr, "_variance");
+        if (bdpt_save_exr(variance.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
+        std::printf("Saved EXR image to %s\n", side.c_str());
+    }
+    if (want_aov || want_denoise || want_denoise_var) {
         bdpt_ctx* fctx = ctx;  // several devices: the first renders the feature buffers and filters
         if (!fctx && bdpt_ctx_create(scene, devices[0], &fctx) != BDPT_OK) return die("bdpt_ctx_create (feature buffers)");
         const size_t px = static_cast<size_t>(cfg.width) * cfg.height;
@@ -382,6 +461,18 @@ int main(int argc, char** argv) {
             std::vector<float> den(px * 3);
             if (bdpt_denoise_host(fctx, cfg.width, cfg.height, rgb.data(), aov.data(), den.data(), &d) != BDPT_OK)
                 return die("bdpt_denoise_host");
+            const std::string side = side_path(exr, "_denoised");
+            if (bdpt_save_exr(den.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
+            std::printf("Saved EXR image to %s\n", side.c_str());
+        }
+        if (want_denoise_var) {
+            bdpt_denoise_params d = {denoise_var_iterations, BDPT_DENOISE_VAR_SIGMA_COLOR, BDPT_DENOISE_SIGMA_NORMAL,
+                                     BDPT_DENOISE_SIGMA_DEPTH, BDPT_DENOISE_DEMODULATE, 1.f};
+            if (windowed) d.norm = static_cast<float>(cfg.spp) / static_cast<float>(window.count);
+            std::vector<float> den(px * 3);
+            if (bdpt_denoise_var_host(fctx, cfg.width, cfg.height, rgb.data(), variance.data(), aov.data(), den.data(),
+                                      nullptr, &d) != BDPT_OK)
+                return die("bdpt_denoise_var_host");
             const std::string side = side_path(exr, "_denoised");
             if (bdpt_save_exr(den.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
             std::printf("Saved EXR image to %s\n", side.c_str());

@@ -44,6 +44,8 @@
  *   bdpt_denoise             (no counterpart) an edge-avoiding filter of a low-spp frame on the device
  *   bdpt_denoise_planes      (no counterpart) that filter for the planes of a split frame, with weights
  *                            of their own or one set for all, under which the planes still add up
+ *   bdpt_batch_moments       (no counterpart) the per-pixel sum and variance across sample batches
+ *   bdpt_denoise_var         (no counterpart) the filter with its colour weight in standard deviations
  *
  * Conventions: plain C types only; status 0 = OK, < 0 = error (message from
  * bdpt_last_error(), thread-local). A context is bound to one HIP device and is
@@ -558,6 +560,62 @@ int bdpt_denoise_planes(bdpt_ctx* ctx, int32_t width, int32_t height, int32_t n_
 int bdpt_denoise_planes_host(bdpt_ctx* ctx, int32_t width, int32_t height, int32_t n_planes, const float* planes_host,
                              const float* aov_host, const float* guide_color_host, int32_t mode,
                              const bdpt_denoise_params* params, float* out_planes_host, float* out_guide_host);
+
+/* ---- per-pixel variance from sample batches, and the filter guided by it ---- */
+/* (new) K = n_batches planes of width * height * 3 floats, consecutive, each the frame rendered from its
+ * own equal share of the samples (bdpt_render_window with the windows (first + b stride, stride K,
+ * count / K), b = 0 .. K - 1, each into a zeroed plane: complete, independent estimates of the whole
+ * frame, light-path splats included, in the units the window entries accumulate). Per pixel and
+ * channel, float32, every operation rounded on its own (no fma), no atomics:
+ *   S = plane_0 + plane_1 + ...          ascending (the bits of bdpt_layers_compose with every bit set)
+ *   mu = S / (float)K
+ *   Q = d_0 d_0 + d_1 d_1 + ...          ascending, d_b = plane_b - mu
+ *   var = Q * c,  c = (float)K / (float)(K - 1) formed on the host in float
+ * out_sum (NULL: not wanted) receives S, the frame of the batches' samples; out_var receives var, the
+ * estimated variance of S (K^2 times the variance of the batch mean), both width * height * 3 floats.
+ * BDPT_ERR_INVALID, the field named in the message: n_batches outside 2..64, n_batches * width *
+ * height >= 2^30, NULL planes or out_var, an output overlapping the planes or the other output.
+ * bdpt_get_stats afterwards: kernel_ms and launches of this call. Asynchronous on `hip_stream`; the
+ * host form stages the buffers and is synchronous. */
+int bdpt_batch_moments(bdpt_ctx* ctx, int32_t width, int32_t height, int32_t n_batches, const float* planes_device,
+                       float* out_sum_device, float* out_var_device, void* hip_stream);
+int bdpt_batch_moments_host(bdpt_ctx* ctx, int32_t width, int32_t height, int32_t n_batches, const float* planes_host,
+                            float* out_sum_host, float* out_var_host);
+
+/* (new) bdpt_denoise's a-trous filter with a colour weight normalised by the pixel's variance (as SVGF,
+ * Schied et al. 2017, weights its luminance). params is bdpt_denoise's struct; sigma_color is now a
+ * number of standard deviations. With c = color * norm, a = aov * norm, v = var * (norm * norm): the
+ * guides alb, N, z, cov and m = max(alb, 1e-3) exactly as bdpt_denoise forms them,
+ *   I_0 = demodulate ? c / m : c,
+ *   U(p) = demodulate ? (v_r / (m_r m_r) + v_g / (m_g m_g)) + v_b / (m_b m_b) : (v_r + v_g) + v_b,
+ *   V_0(p) = sum_q k(q - p) U(q) / sum_q k(q - p),  q = p + (dx, dy), dx, dy in -1..1, taps outside the
+ *   image skipped, k the outer product of [1, 2, 1] / 4, dy outer and dx inner.
+ * Iteration i = 0 .. iterations - 1, step s = 2^i: taps, h, w_n, w_z, w_cov, the centre tap w = 1 and
+ * the summation order are bdpt_denoise's, and with hw = (h_y h_x) w(p, q)
+ *   w_c = exp(-min(|I_i(p) - I_i(q)|^2 / ((sigma_color sigma_color) V_i(p) + 1e-10), 80))
+ *         (no 2^-i narrowing: the variance shrinks by itself; the centre pixel's variance alone, so a
+ *         firefly accepts its neighbours and they do not accept it),
+ *   I_{i+1}(p) = sum hw I_i(q) / sum hw,
+ *   V_{i+1}(p) = sum (hw hw) V_i(q) / ((sum hw) (sum hw)).
+ * out = I_iterations * (demodulate ? m : 1); out_var (width * height floats, NULL: not wanted) =
+ * V_iterations, the residual variance in the filter's own (demodulated, channel-summed) domain.
+ * iterations == 0: out = color * norm and out_var = V_0. No atomics and a fixed order: two runs give the
+ * same bits. BDPT_ERR_INVALID, the field named in the message: bdpt_denoise's parameter checks, a NULL
+ * var, an output overlapping an input or the other output. The scratch is bdpt_denoise's (64 bytes per
+ * pixel: the variance rides in the fourth float of the images). bdpt_get_stats afterwards: kernel_ms
+ * and launches of this call. Asynchronous on `hip_stream`; the host form is synchronous. */
+/* Defaults for bdpt_denoise_var; sigma_normal, sigma_depth and demodulate are BDPT_DENOISE_*'s. Chosen on
+ * the 8-spp, 8-batch HardLight 64 x 64 frame of tests/test_gpu_batch_moments.py against its 256-spp
+ * frame and on nothing else (a grid over iterations 3..5 and sigma_color 0.5, 1, 2, 4, 8: mean squared
+ * error 0.00072 against the unfiltered sum's 0.00142 and 0.00104 for bdpt_denoise with its defaults on the
+ * same frame; the whole grid is in DESIGN.md §7i). */
+#define BDPT_DENOISE_VAR_ITERATIONS 3
+#define BDPT_DENOISE_VAR_SIGMA_COLOR 4.0f
+int bdpt_denoise_var(bdpt_ctx* ctx, int32_t width, int32_t height, const float* color_dev, const float* var_dev,
+                     const float* aov_dev, float* out_dev, float* out_var_dev, const bdpt_denoise_params* params,
+                     void* hip_stream);
+int bdpt_denoise_var_host(bdpt_ctx* ctx, int32_t width, int32_t height, const float* color_host, const float* var_host,
+                          const float* aov_host, float* out_host, float* out_var_host, const bdpt_denoise_params* params);
 
 /* ---- path-length layers: one BDPT frame split by bounce count ---- */
 /* (new) Not in the reference. Every contribution the BDPT frame kernel forms belongs to a full path
