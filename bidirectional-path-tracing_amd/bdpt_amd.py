@@ -230,9 +230,23 @@ class _Stats(ctypes.Structure):
                 ("rr_express_iters", ctypes.c_int64 * 3)]
 
 
+class _AdaptiveParams(ctypes.Structure):  # bdpt_adaptive_params
+    _fields_ = [("n_batches", ctypes.c_int32), ("step", ctypes.c_int32), ("max_passes", ctypes.c_int32),
+                ("threshold", ctypes.c_float), ("eps", ctypes.c_float), ("dilate", ctypes.c_int32),
+                ("record_passes", ctypes.c_int32)]
+
+
+ADAPTIVE_MAX_PASSES = 64  # BDPT_ADAPTIVE_MAX_PASSES
+
+
+class _AdaptiveStats(ctypes.Structure):  # bdpt_adaptive_stats
+    _fields_ = [("passes", ctypes.c_int32), ("reserved", ctypes.c_int32), ("samples", ctypes.c_int64),
+                ("active", ctypes.c_int32 * ADAPTIVE_MAX_PASSES)]
+
+
 # Sources that make up the frame kernels' code objects: their hash stamps the
 # profiles (PMC passes) so bench.py only reuses a measurement of the same kernel.
-KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_kernels_layers.hip", "csrc/bdpt_kernels_groups.hip", "csrc/bdpt_kernels_strat.hip", "csrc/bdpt_kernels_strat_unweighted.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
+KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_kernels_layers.hip", "csrc/bdpt_kernels_groups.hip", "csrc/bdpt_kernels_strat.hip", "csrc/bdpt_kernels_strat_unweighted.hip", "csrc/bdpt_kernels_pixels.hip", "csrc/adaptive_kernels.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
                   "csrc/dev_scene.hpp", "csrc/dev_rng.hpp", "csrc/dev_warp.hpp", "csrc/dev_traverse.hpp", "csrc/dev_shade.hpp", "csrc/dev_emitter.hpp",
                   "csrc/powf_restated.inc", "csrc/bdpt_types.h", "Makefile")
 
@@ -333,6 +347,18 @@ def lib():
         L.bdpt_denoise_planes_host.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(_DenoiseParams), vp, vp]
         L.bdpt_batch_moments.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
         L.bdpt_batch_moments_host.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+        L.bdpt_render_pixels.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), vp, i32, vp, vp]
+        L.bdpt_render_pixels_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), vp, i32, vp]
+        L.bdpt_adaptive_resolve.argtypes = [vp, i32, i32, i32, i32, vp, vp, ctypes.c_int64, vp, vp, vp]
+        L.bdpt_adaptive_resolve_host.argtypes = [vp, i32, i32, i32, i32, vp, vp, ctypes.c_int64, vp, vp]
+        f32 = ctypes.c_float
+        L.bdpt_adaptive_select.argtypes = [vp, i32, i32, vp, vp, f32, f32, i32, i32, i32, vp, vp, vp, vp]
+        L.bdpt_adaptive_select_host.argtypes = [vp, i32, i32, vp, vp, f32, f32, i32, i32, i32, vp, vp, vp]
+        L.bdpt_render_adaptive.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_AdaptiveParams), vp, vp, vp,
+                                           ctypes.POINTER(_AdaptiveStats), vp]
+        L.bdpt_render_adaptive_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_AdaptiveParams), vp, vp,
+                                                vp, ctypes.POINTER(_AdaptiveStats)]
+        L.bdpt_adaptive_pass_lists.argtypes = [vp, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
         L.bdpt_denoise_var.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(_DenoiseParams), vp]
         L.bdpt_denoise_var_host.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(_DenoiseParams)]
         L.bdpt_render_layers.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp, vp]
@@ -1074,6 +1100,85 @@ def batch_moments_numpy(planes, dt=np.float32):
     return S, var
 
 
+ADAPTIVE_EPS = 1e-3  # render_adaptive's default floor under the channel sum of S
+
+
+def adaptive_splat_scale(spp: int, n_pixels: int, n_batches: int, total: int, dt=np.float32):
+    """bdpt_adaptive_resolve's t = spp W H / (K M), formed in double and rounded once to dt (0 when M == 0)."""
+    if total <= 0:
+        return dt(0)
+    return dt(np.float64(spp) * np.float64(n_pixels) / (np.float64(n_batches) * np.float64(total)))
+
+
+def adaptive_resolve_numpy(planes, m, spp: int, dt=np.float32):
+    """What bdpt_adaptive_resolve computes, as the header states it, every operation in `dt`: planes
+    (K, 2, H, W, 3), pair b = (T_b splats, E_b eye) as render_pixels accumulates them, m (H, W) int samples per
+    batch -> (S, var), both (H, W, 3) in dt. In float32 the loop below is the kernel's, operation for operation."""
+    pl = np.asarray(planes)
+    if pl.ndim != 5 or pl.shape[1] != 2 or pl.shape[4] != 3:
+        raise ValueError(f"adaptive_resolve: planes must be (n_batches, 2, H, W, 3), got {pl.shape}")
+    K, _, H, W, _ = pl.shape
+    if not BATCHES_MIN <= K <= BATCHES_MAX:
+        raise ValueError(f"adaptive_resolve: n_batches must be in [{BATCHES_MIN}, {BATCHES_MAX}], got {K}")
+    mm = np.asarray(m, np.int64).reshape(H, W)
+    t = adaptive_splat_scale(spp, H * W, K, int(mm.sum()), dt)
+    den = np.where(mm > 0, K * mm, 1).astype(dt)
+    a = np.where(mm > 0, dt(spp) / den, dt(0)).astype(dt)[..., None]
+    pl = pl.astype(dt)
+
+    def plane(b):
+        x = pl[b, 1] * a
+        y = pl[b, 0] * t
+        return x + y
+
+    S = plane(0)
+    for b in range(1, K):
+        S = S + plane(b)
+    mu = S / dt(K)
+    Q = None
+    for b in range(K):
+        d = plane(b) - mu
+        Q = d * d if Q is None else Q + d * d
+    var = Q * dt(np.float32(K) / np.float32(K - 1))
+    assert S.dtype == dt and var.dtype == dt
+    return S, var
+
+
+def adaptive_noisy_numpy(S, var, threshold: float, eps: float) -> np.ndarray:
+    """bdpt_adaptive_select's noisy(p), float32 in the header's order: (H, W) bool from S and var (H, W, 3)."""
+    f = np.float32
+    S, var = np.asarray(S, f), np.asarray(var, f)
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = (var[..., 0] + var[..., 1]) + var[..., 2]
+        s = ((S[..., 0] + S[..., 1]) + S[..., 2]) + f(eps)
+        return v > (f(threshold) * f(threshold)) * (s * s)
+
+
+def adaptive_select_numpy(S, var, m, threshold: float, eps: float, step: int, m_max: int, dilate: bool = True):
+    """What bdpt_adaptive_select computes: S, var (H, W, 3), m (H, W) int32 -> (list int32 ascending, m_new (H, W)
+    int32): the active pixels (noisy, or with dilate any pixel of the clipped 3 x 3 neighbourhood noisy, and
+    m + step <= m_max) and m with step added at exactly those."""
+    noisy = adaptive_noisy_numpy(S, var, threshold, eps)
+    H, W = noisy.shape
+    wanted = noisy
+    if dilate:
+        pad = np.zeros((H + 2, W + 2), bool)
+        pad[1:-1, 1:-1] = noisy
+        wanted = np.zeros((H, W), bool)
+        for dy in range(3):
+            for dx in range(3):
+                wanted |= pad[dy:dy + H, dx:dx + W]
+    mm = np.asarray(m, np.int32).reshape(H, W)
+    active = wanted & (mm.astype(np.int64) + int(step) <= int(m_max))
+    lst = np.flatnonzero(active.reshape(-1)).astype(np.int32)
+    return lst, (mm + np.where(active, np.int32(step), np.int32(0))).astype(np.int32)
+
+
+def adaptive_windows(n_batches: int, step: int, n_pass: int) -> list:
+    """The sample windows of adaptive pass n_pass, one per batch: (n_pass * step * K + b, K, step)."""
+    return [SampleWindow(n_pass * step * n_batches + b, n_batches, step) for b in range(n_batches)]
+
+
 def denoise_var_settings() -> "DenoiseSettings":
     """bdpt_denoise_var's defaults: the header's BDPT_DENOISE_VAR_ITERATIONS / _SIGMA_COLOR, the other fields
     DenoiseSettings' own."""
@@ -1161,6 +1266,7 @@ class BDPTIntegrator:
         self.aov = None
         self.batches = None  # render_batches' last planes
         self.var = None      # batch_moments' last variance
+        self.adaptive = None  # render_adaptive's last stats
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -1442,6 +1548,112 @@ class BDPTIntegrator:
         _check(lib().bdpt_batch_moments(self._h, int(width), int(height), int(n_batches), ctypes.c_void_p(planes_ptr),
                                         ctypes.c_void_p(sum_ptr or None), ctypes.c_void_p(var_ptr),
                                         ctypes.c_void_p(stream_ptr)))
+
+    # ---- adaptive sampling
+    def render_pixels(self, pixels, window: SampleWindow | None = None, out=None, row_offset: int = 0,
+                      row_stride: int = 1, flags: int = 0) -> np.ndarray:
+        """bdpt_render_pixels_host: the window's samples (None: all spp) of the listed pixels only, ADDED to
+        `out` (None: a new zeroed array), a (2, H, W, 3) float32 array that is returned: out[0] the camera
+        splats of those samples' light paths, out[1] everything formed at the samples' own pixels (untouched
+        at unlisted pixels). pixels: int32 indices y * W + x, strictly ascending; the library checks them."""
+        H, W = self.config.height, self.config.width
+        px = np.ascontiguousarray(pixels, np.int32).reshape(-1)
+        if out is None:
+            out = np.zeros((2, H, W, 3), np.float32)
+        if out.dtype != np.float32 or out.shape != (2, H, W, 3) or not out.flags.c_contiguous:
+            raise BdptError(f"render_pixels: out must be a contiguous float32 (2, {H}, {W}, 3) array")
+        p = self.params(row_offset, row_stride, flags)
+        w = window.c() if window is not None else None
+        _check(lib().bdpt_render_pixels_host(self._h, ctypes.byref(p), w and ctypes.byref(w),
+                                             px.ctypes.data if px.size else None, int(px.size), out.ctypes.data))
+        return out
+
+    def render_pixels_device(self, pixels_ptr: int, n_pixels: int, fb_ptr: int, window: SampleWindow | None = None,
+                             stream_ptr: int = 0) -> None:
+        """bdpt_render_pixels: asynchronous, ADDED to a device buffer of 2 * H * W * 3 floats. The list is a
+        device array the library TRUSTS (inside the image, strictly ascending): pass only what adaptive_select
+        wrote or what was checked as render_pixels checks."""
+        p = self.params()
+        w = window.c() if window is not None else None
+        _check(lib().bdpt_render_pixels(self._h, ctypes.byref(p), w and ctypes.byref(w), ctypes.c_void_p(pixels_ptr or None),
+                                        int(n_pixels), ctypes.c_void_p(fb_ptr), ctypes.c_void_p(stream_ptr)))
+
+    def adaptive_resolve(self, planes, m, spp: int | None = None):
+        """bdpt_adaptive_resolve_host of (K, 2, H, W, 3) plane pairs and the (H, W) int32 samples per batch:
+        (S, var), both (H, W, 3); the bits of adaptive_resolve_numpy."""
+        a = np.ascontiguousarray(planes, np.float32)
+        if a.ndim != 5 or a.shape[1] != 2 or a.shape[4] != 3:
+            raise BdptError(f"adaptive_resolve: planes must be (n_batches, 2, H, W, 3), got {a.shape}")
+        K, _, H, W, _ = a.shape
+        mm = np.ascontiguousarray(m, np.int32).reshape(H, W)
+        S, v = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.float32)
+        _check(lib().bdpt_adaptive_resolve_host(self._h, W, H, K, int(self.config.spp if spp is None else spp),
+                                                a.ctypes.data, mm.ctypes.data, -1, S.ctypes.data, v.ctypes.data))
+        return S, v
+
+    def adaptive_resolve_device(self, planes_ptr: int, m_ptr: int, n_batches: int, splat_total: int, sum_ptr: int,
+                                var_ptr: int, spp: int | None = None, stream_ptr: int = 0) -> None:
+        """bdpt_adaptive_resolve: asynchronous, on device buffers; splat_total = the sum of m, counted by the caller."""
+        _check(lib().bdpt_adaptive_resolve(self._h, self.config.width, self.config.height, int(n_batches),
+                                           int(self.config.spp if spp is None else spp), ctypes.c_void_p(planes_ptr),
+                                           ctypes.c_void_p(m_ptr), int(splat_total), ctypes.c_void_p(sum_ptr),
+                                           ctypes.c_void_p(var_ptr), ctypes.c_void_p(stream_ptr)))
+
+    def adaptive_select_device(self, sum_ptr: int, var_ptr: int, m_ptr: int, list_ptr: int, count_ptr: int,
+                               threshold: float, eps: float, step: int, m_max: int, dilate: bool = True,
+                               stream_ptr: int = 0) -> None:
+        """bdpt_adaptive_select: asynchronous, on device buffers (list: W * H int32, count: one int32)."""
+        _check(lib().bdpt_adaptive_select(self._h, self.config.width, self.config.height, ctypes.c_void_p(sum_ptr),
+                                          ctypes.c_void_p(var_ptr), float(threshold), float(eps), int(step), int(m_max),
+                                          int(bool(dilate)), ctypes.c_void_p(m_ptr), ctypes.c_void_p(list_ptr),
+                                          ctypes.c_void_p(count_ptr), ctypes.c_void_p(stream_ptr)))
+
+    def adaptive_select(self, S, var, m, threshold: float, eps: float, step: int, m_max: int, dilate: bool = True):
+        """bdpt_adaptive_select_host: (list int32 ascending, m_new (H, W) int32); adaptive_select_numpy's."""
+        s = np.ascontiguousarray(S, np.float32)
+        v = np.ascontiguousarray(var, np.float32)
+        if s.ndim != 3 or s.shape[2] != 3 or v.shape != s.shape:
+            raise BdptError(f"adaptive_select: S and var must both be (H, W, 3), got {s.shape} and {v.shape}")
+        H, W = s.shape[:2]
+        mm = np.array(m, np.int32).reshape(H, W)  # a copy: the library updates it
+        lst = np.zeros(H * W, np.int32)
+        n = ctypes.c_int32(0)
+        _check(lib().bdpt_adaptive_select_host(self._h, W, H, s.ctypes.data, v.ctypes.data, float(threshold), float(eps),
+                                               int(step), int(m_max), int(bool(dilate)), mm.ctypes.data, lst.ctypes.data,
+                                               ctypes.byref(n)))
+        return lst[:n.value].copy(), mm
+
+    def render_adaptive(self, threshold: float, n_batches: int = 8, step: int = 1, max_passes: int | None = None,
+                        eps: float = ADAPTIVE_EPS, dilate: bool = True, return_passes: bool = False):
+        """bdpt_render_adaptive_host: the frame with further samples only where the batch variance asks. The
+        budget is config.spp = max_passes * step * n_batches samples per pixel (max_passes None: spp /
+        (step * n_batches)). Pass 0 gives every pixel step * n_batches samples; a pixel then stays active while
+        its relative standard deviation, estimated from the n_batches batches, exceeds `threshold` (or, with
+        dilate, a neighbour's does) and its budget lasts. Returns (frame (H, W, 3), variance (H, W, 3), samples
+        (H, W) int32) and, with return_passes, the list of active pixel indices of every pass. Also sets self.rgb,
+        self.var and self.adaptive (passes, samples traced, active pixels per pass). threshold = 0 is the
+        unbiased frame: choosing samples from the estimate they feed biases it, as in every such sampler."""
+        H, W = self.config.height, self.config.width
+        a = _AdaptiveParams()
+        a.n_batches, a.step = int(n_batches), int(step)
+        a.max_passes = int(max_passes) if max_passes is not None else self.config.spp // max(1, int(step) * int(n_batches))
+        a.threshold, a.eps, a.dilate, a.record_passes = float(threshold), float(eps), int(bool(dilate)), int(bool(return_passes))
+        frame, var = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.float32)
+        samples = np.zeros((H, W), np.int32)
+        st = _AdaptiveStats()
+        p = self.params()
+        _check(lib().bdpt_render_adaptive_host(self._h, ctypes.byref(p), ctypes.byref(a), frame.ctypes.data,
+                                               var.ctypes.data, samples.ctypes.data, ctypes.byref(st)))
+        self.rgb, self.var = frame, var
+        self.adaptive = dict(passes=st.passes, samples=st.samples, active=list(st.active[:st.passes]))
+        if not return_passes:
+            return frame, var, samples
+        total = ctypes.c_int64(0)
+        _check(lib().bdpt_adaptive_pass_lists(self._h, None, 0, ctypes.byref(total)))
+        flat = np.zeros(max(total.value, 1), np.int32)
+        _check(lib().bdpt_adaptive_pass_lists(self._h, flat.ctypes.data, flat.size, ctypes.byref(total)))
+        cuts = np.cumsum([0] + self.adaptive["active"])
+        return frame, var, samples, [flat[cuts[j]:cuts[j + 1]].copy() for j in range(st.passes)]
 
     def render_aov(self, row_offset: int = 0, row_stride: int = 1, window: SampleWindow | None = None) -> np.ndarray:
         """bdpt_render_aov_host: the first-hit feature buffers of the (sharded, windowed) frame

@@ -23,7 +23,7 @@ namespace bdpt {
 // The builds of the BDPT frame kernel (bdpt_kernels_<x>.hip; FrameBuild: bdpt_device.hpp)
 extern FrameBuild frame_build, frame_build_tex, frame_build_rr, frame_build_rrc, frame_build_deep,
     frame_build_hbm, frame_build_split, frame_build_ng, frame_build_layers, frame_build_groups, frame_build_strat, frame_build_strat_unweighted,
-    frame_build_groups_layers, frame_build_groups_strat, frame_build_groups_strat_unweighted;
+    frame_build_groups_layers, frame_build_groups_strat, frame_build_groups_strat_unweighted, frame_build_pixels;
 // sample_state.hip: the single-sample kernels (the caller's std::mt19937 state at sc.mt_ring)
 hipError_t launch_sample(const dev::DevScene& sc, const dev::DevFrame& fr, float* splats, float* lvbuf, uint2* gstack,
                          const dev::Ray& ray, float* out, hipStream_t stream);
@@ -83,6 +83,14 @@ hipError_t launch_denoise_planes_iter(int W, int H, int step, float inv_c, float
 // aov_kernels.hip: per-pixel sum and variance across K batch planes of n floats (c = K / (K - 1); sum may be null)
 hipError_t launch_batch_moments(const float* planes, size_t n, int K, float c, float* sum, float* var, hipStream_t st);
 // aov_kernels.hip: the a-trous filter with a variance-normalised colour weight (the variance rides in the images' .w)
+// adaptive_kernels.hip: adaptive sampling's state (bdpt_adaptive_resolve, bdpt_adaptive_select)
+hipError_t launch_adaptive_resolve(const float* planes, const int32_t* m, size_t n, int K, int spp, float t, float c,
+                                   float* sum, float* var, hipStream_t st);
+size_t adaptive_select_scratch_bytes(size_t pixels);
+hipError_t launch_adaptive_select(const float* S, const float* var, int W, int H, float thr, float eps, int step, int m_max,
+                                  int dilate, int32_t* m, int32_t* list, int32_t* count, void* scratch, hipStream_t st);
+hipError_t launch_adaptive_start(size_t pixels, int step, int32_t* m, int32_t* list, hipStream_t st);
+hipError_t launch_adaptive_samples(size_t pixels, int K, const int32_t* m, int32_t* samples, hipStream_t st);
 hipError_t launch_denoise_var_prepare(int W, int H, const float* color, const float* var, const float* aov, float norm,
                                       int demodulate, void* guide, void* img, hipStream_t st);
 hipError_t launch_denoise_var_blur(int W, int H, const void* src, void* dst, float* out_var, hipStream_t st);
@@ -325,6 +333,13 @@ struct bdpt_ctx : CtxStream {
     std::vector<float> sheet_gains_host;
     DevBuf<int32_t> row_order;  // bdpt_set_row_order (device copy; DevFrame::row_order)
     int32_t row_order_n = 0;    // its row count (0: top to bottom)
+    DevBuf<int32_t> pixel_list;  // bdpt_render_pixels_host: the device copy of the caller's list (DevFrame::pixel_list)
+    // adaptive sampling (bdpt_render_adaptive): the K plane pairs, samples per batch and pixel, the pass's
+    // list, its count, the select kernels' scratch; the host forms' staging; the recorded lists
+    DevBuf<float> ad_planes;
+    DevBuf<int32_t> ad_m, ad_list, ad_count;
+    DevBuf<void> ad_scratch, ad_stage;
+    std::vector<int32_t> ad_pass_lists;
     DevBuf<unsigned long long> row_cost;  // counting renders: queries per local row (DevFrame::row_cost)
     int32_t row_cost_n = 0;               // the rows of the last counting render
     unsigned long long work_init = 0;  // BDPT_SAMPLE_RANGE's first sample (host copy for the async upload)
@@ -1176,6 +1191,9 @@ static const PlaneKind kGroupStrategyPlanes = {"bdpt_render_group_strategies", "
                                                "light groups x strategies",
                                                {&frame_build_groups_strat, &frame_build_groups_strat_unweighted}, true, true,
                                                &kStrategyPlanes};
+// bdpt_render_pixels: the strategy build's planes at the fixed shape (1, 2) for a list of pixels
+static const PlaneKind kPixelPlanes = {"bdpt_render_pixels", "2 (the splat and eye planes)", 2, "pixel lists",
+                                       {&frame_build_pixels, &frame_build_pixels}, true, false, nullptr};
 // what bdpt_group_planes_combine takes: the planes of either crossed kind (n_inner up to the larger limit)
 static const PlaneKind kAnyInnerPlanes = {nullptr, "n_inner", std::max(kMaxLayers, kMaxStratS * kMaxStratT), "", {}, false, false, nullptr};
 static const PlaneKind kCrossedPlanes = {"bdpt_group_planes_combine", "n_groups", kMaxGroups, "", {}, false, true, &kAnyInnerPlanes};
@@ -1200,6 +1218,9 @@ struct Planes {
     const int32_t* group_of_emitter = nullptr;  // mapped kinds: the caller's host map (null: identity)
     int n_s = 0, n_t = 0, weighting = 0;        // shaped kinds: n_s * n_t planes, BDPT_STRATEGIES_*
     int n_inner = 1;                            // crossed kinds: planes per group (n_layers, n_s * n_t)
+    const int32_t* pixels = nullptr;            // the pixel-list kind: the DEVICE list and its length (-1: no list)
+    int64_t n_pixels = -1;
+    bool listed() const { return n_pixels >= 0; }
 
     // planes in the framebuffer (sized by it only after check_planes has accepted the counts)
     size_t planes() const { return static_cast<size_t>(n) * n_inner; }
@@ -1218,6 +1239,12 @@ static int strategy_plane_count(int32_t n_s, int32_t n_t) { return strategy_shap
 static Planes strategy_planes(int32_t n_s, int32_t n_t, int32_t weighting) {
     Planes pl{&kStrategyPlanes, strategy_plane_count(n_s, n_t)};
     pl.n_s = n_s, pl.n_t = n_t, pl.weighting = weighting;
+    return pl;
+}
+static Planes pixel_planes(const int32_t* pixels_dev, int64_t n_pixels) {
+    Planes pl{&kPixelPlanes, 2};
+    pl.n_s = 1, pl.n_t = 2, pl.weighting = BDPT_STRATEGIES_WEIGHTED;
+    pl.pixels = pixels_dev, pl.n_pixels = n_pixels;
     return pl;
 }
 static Planes group_layer_planes(const int32_t* group_of_emitter, int32_t n_groups, int32_t n_layers) {
@@ -1273,6 +1300,21 @@ static int check_planes(const bdpt_ctx* c, const bdpt_frame_params* p, const Pla
     return BDPT_OK;
 }
 
+// What a pixel-list render refuses beyond check_planes: a list that cannot lie in the image, a row
+// shard, a row order (the list's word in DevFrame is the row order's).
+static int check_pixel_list(const bdpt_ctx* c, const bdpt_frame_params* p, const Planes& pl) {
+    if (!pl.listed()) return BDPT_OK;
+    const std::string entry = std::string(pl.kind->entry) + ": ";
+    if (pl.n_pixels > static_cast<int64_t>(p->width) * p->height)
+        return fail(BDPT_ERR_INVALID, entry + "n_pixels must be in [0, width * height]");
+    if (pl.n_pixels > 0 && !pl.pixels) return fail(BDPT_ERR_INVALID, entry + "pixels must not be NULL");
+    if (p->row_offset != 0 || p->row_stride != 1)
+        return fail(BDPT_ERR_INVALID, entry + "a pixel list takes no row shard (row_offset must be 0, row_stride 1)");
+    if (c->row_order_n)
+        return fail(BDPT_ERR_INVALID, entry + "a row order is set on the context (bdpt_set_row_order); clear it first");
+    return BDPT_OK;
+}
+
 // bdpt_render and the BDPT form of bdpt_render_window (w null: every sample); with planes:
 // the plane kinds' render entries (fb is pl.planes() planes, the kind's build; check_planes refuses
 // what it does not serve).
@@ -1283,10 +1325,15 @@ static int render_bdpt(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sampl
     if (rc) return rc;
     if ((rc = check_window(p, w))) return rc;
     if (pl.kind && (rc = check_planes(c, p, pl))) return rc;
+    if ((rc = check_pixel_list(c, p, pl))) return rc;
     if ((rc = textured_frame_check(c, p))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     dev::DevFrame fr = make_frame(p, w);
+    if (pl.listed()) {  // the window's samples of the listed pixels (no row order: refused above)
+        fr.pixel_list = pl.pixels;
+        fr.total_samples = static_cast<uint64_t>(pl.n_pixels) * static_cast<uint64_t>(fr.win_count);
+    }
     fr.capped = c->capped;
     if (!fr.rr_mode && fr.total_samples > 0 && (rc = ensure_tasks(c))) return rc;
     fr.tasks = c->tasks;
@@ -1913,6 +1960,7 @@ static int render_bdpt_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_
     if (rc) return rc;
     if ((rc = check_window(p, w))) return rc;
     if (pl.kind && (rc = check_planes(c, p, pl))) return rc;  // before the planes are staged
+    if ((rc = check_pixel_list(c, p, pl))) return rc;
     if ((rc = stage_host(c, fb_host, static_cast<size_t>(p->width) * p->height * 3 * pl.planes(),
                          [&](float* fb) { return render_bdpt(c, p, w, fb, c->stream, pl); })))
         return rc;
@@ -2452,6 +2500,298 @@ int bdpt_batch_moments_host(bdpt_ctx* c, int32_t width, int32_t height, int32_t 
     if (out_sum) HIP_TRY(hipMemcpyAsync(out_sum, dsum, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(out_var, dvar, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+// ---------------------------------------------------------------- adaptive sampling
+int bdpt_render_pixels(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, const int32_t* pixels,
+                       int32_t n_pixels, float* fb, void* hip_stream) {
+    if (n_pixels < 0) return fail(BDPT_ERR_INVALID, "bdpt_render_pixels: n_pixels must be in [0, width * height]");
+    return render_bdpt(c, p, w, fb, hip_stream, pixel_planes(pixels, n_pixels));
+}
+
+int bdpt_render_pixels_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_sample_window* w, const int32_t* pixels,
+                            int32_t n_pixels, float* fb_host) {
+    const std::string entry = "bdpt_render_pixels: ";
+    if (!c || !fb_host) return fail(BDPT_ERR_INVALID, "null argument");
+    if (int rc = check_frame_size(p)) return rc;
+    const int64_t npx = static_cast<int64_t>(p->width) * p->height;
+    if (n_pixels < 0 || n_pixels > npx) return fail(BDPT_ERR_INVALID, entry + "n_pixels must be in [0, width * height]");
+    if (n_pixels > 0 && !pixels) return fail(BDPT_ERR_INVALID, entry + "pixels must not be NULL");
+    // the list's contract, which the device form trusts: inside the image, strictly ascending
+    for (int32_t i = 0; i < n_pixels; i++) {
+        if (pixels[i] < 0 || pixels[i] >= npx)
+            return fail(BDPT_ERR_INVALID, entry + "pixels[" + std::to_string(i) + "] = " + std::to_string(pixels[i]) +
+                                              " is outside [0, width * height)");
+        if (i > 0 && pixels[i] <= pixels[i - 1])
+            return fail(BDPT_ERR_INVALID, entry + "pixels[" + std::to_string(i) + "] = " + std::to_string(pixels[i]) +
+                                              " does not ascend (the list must be strictly ascending)");
+    }
+    // every refusal before the list is uploaded (render_bdpt_host repeats them before it stages the planes)
+    Planes pl = pixel_planes(n_pixels > 0 ? pixels : nullptr, n_pixels);
+    int rc = check_params(p);
+    if (rc || (rc = check_window(p, w)) || (rc = check_planes(c, p, pl)) || (rc = check_pixel_list(c, p, pl))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->pixel_list.reserve(std::max<size_t>(sizeof(int32_t) * static_cast<size_t>(n_pixels), 16)));
+    if (n_pixels > 0)
+        HIP_TRY(hipMemcpy(c->pixel_list, pixels, sizeof(int32_t) * static_cast<size_t>(n_pixels), hipMemcpyHostToDevice));
+    pl.pixels = c->pixel_list;
+    return render_bdpt_host(c, p, w, fb_host, pl);
+}
+
+static bool finite_nonneg(float x) { return std::isfinite(x) && x >= 0.f; }
+
+static int check_adaptive_resolve(int32_t width, int32_t height, int32_t n_batches, int32_t spp, const void* planes,
+                                  const void* m, const void* out_sum, const void* out_var) {
+    const std::string entry = "bdpt_adaptive_resolve: ";
+    if (width <= 0 || height <= 0) return fail(BDPT_ERR_INVALID, entry + "width/height must be > 0");
+    if (n_batches < 2 || n_batches > 64) return fail(BDPT_ERR_INVALID, entry + "n_batches must be in [2, 64]");
+    if (spp < 1) return fail(BDPT_ERR_INVALID, entry + "spp must be >= 1");
+    if (2ull * static_cast<uint64_t>(n_batches) * static_cast<uint64_t>(width) * static_cast<uint64_t>(height) >= (1ull << 30))
+        return fail(BDPT_ERR_INVALID, entry + "2 * n_batches * width * height must be below 2^30");
+    if (!planes) return fail(BDPT_ERR_INVALID, entry + "planes must not be NULL");
+    if (!m) return fail(BDPT_ERR_INVALID, entry + "samples_per_batch must not be NULL");
+    if (!out_sum) return fail(BDPT_ERR_INVALID, entry + "out_sum must not be NULL");
+    if (!out_var) return fail(BDPT_ERR_INVALID, entry + "out_var must not be NULL");
+    return BDPT_OK;
+}
+
+// t = spp W H / (K M) in double, rounded once (0 when no sample was traced)
+static float adaptive_splat_scale(int32_t spp, int32_t width, int32_t height, int32_t K, int64_t M) {
+    if (M <= 0) return 0.f;
+    return static_cast<float>(static_cast<double>(spp) * width * height / (static_cast<double>(K) * static_cast<double>(M)));
+}
+
+// the launch alone, for callers that order and time their own work (the driver)
+static int adaptive_resolve_launch(int32_t width, int32_t height, int32_t K, int32_t spp, const float* planes,
+                                   const int32_t* m, int64_t M, float* out_sum, float* out_var, hipStream_t st) {
+    const float scale = static_cast<float>(K) / static_cast<float>(K - 1);
+    HIP_TRY(launch_adaptive_resolve(planes, m, static_cast<size_t>(width) * height * 3, K, spp,
+                                    adaptive_splat_scale(spp, width, height, K, M), scale, out_sum, out_var, st));
+    return BDPT_OK;
+}
+
+int bdpt_adaptive_resolve(bdpt_ctx* c, int32_t width, int32_t height, int32_t n_batches, int32_t spp, const float* planes,
+                          const int32_t* m, int64_t splat_total, float* out_sum, float* out_var, void* hip_stream) {
+    int rc = check_adaptive_resolve(width, height, n_batches, spp, planes, m, out_sum, out_var);
+    if (rc) return rc;
+    if (splat_total < 0)
+        return fail(BDPT_ERR_INVALID, "bdpt_adaptive_resolve: splat_total must be >= 0 (only the host form counts it)");
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if ((rc = begin_use(c, st))) return rc;
+    if ((rc = begin_timed(c, st))) return rc;
+    if ((rc = adaptive_resolve_launch(width, height, n_batches, spp, planes, m, splat_total, out_sum, out_var, st))) return rc;
+    return end_timed(c, st, 0, 1);
+}
+
+int bdpt_adaptive_resolve_host(bdpt_ctx* c, int32_t width, int32_t height, int32_t n_batches, int32_t spp,
+                               const float* planes, const int32_t* m, int64_t splat_total, float* out_sum, float* out_var) {
+    int rc = check_adaptive_resolve(width, height, n_batches, spp, planes, m, out_sum, out_var);
+    if (rc) return rc;
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    const size_t N = static_cast<size_t>(width) * height, n = N * 3, all = n * 2 * n_batches;
+    if (splat_total < 0) {
+        splat_total = 0;
+        for (size_t i = 0; i < N; i++) splat_total += m[i];
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // planes, out_sum, out_var (floats, each a multiple of 16 bytes when n is), then m
+    const size_t n16 = (n + 3) & ~static_cast<size_t>(3);
+    HIP_TRY(c->ad_stage.reserve((all + 2 * n16) * sizeof(float) + N * sizeof(int32_t)));
+    float* const dp = static_cast<float*>(c->ad_stage.get());
+    float *dsum = dp + all, *dvar = dsum + n16;
+    int32_t* const dm = reinterpret_cast<int32_t*>(dvar + n16);
+    HIP_TRY(hipMemcpyAsync(dp, planes, all * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dm, m, N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = bdpt_adaptive_resolve(c, width, height, n_batches, spp, dp, dm, splat_total, dsum, dvar, c->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(out_sum, dsum, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_var, dvar, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+static int check_adaptive_select(int32_t width, int32_t height, const void* sum, const void* var, float threshold, float eps,
+                                 int32_t step, int32_t m_max, int32_t dilate, const void* m, const void* list,
+                                 const void* count) {
+    const std::string entry = "bdpt_adaptive_select: ";
+    if (width <= 0 || height <= 0) return fail(BDPT_ERR_INVALID, entry + "width/height must be > 0");
+    if (static_cast<uint64_t>(width) * static_cast<uint64_t>(height) >= (1ull << 30))
+        return fail(BDPT_ERR_INVALID, entry + "width * height must be below 2^30");
+    if (!finite_nonneg(threshold)) return fail(BDPT_ERR_INVALID, entry + "threshold must be finite and >= 0");
+    if (!finite_nonneg(eps)) return fail(BDPT_ERR_INVALID, entry + "eps must be finite and >= 0");
+    if (step < 1) return fail(BDPT_ERR_INVALID, entry + "step must be >= 1");
+    if (m_max < 0) return fail(BDPT_ERR_INVALID, entry + "m_max must be >= 0");
+    if (static_cast<int64_t>(m_max) + step >= (int64_t{1} << 31)) return fail(BDPT_ERR_INVALID, entry + "m_max + step must fit int32");
+    if (dilate != 0 && dilate != 1) return fail(BDPT_ERR_INVALID, entry + "dilate must be 0 or 1");
+    if (!sum || !var) return fail(BDPT_ERR_INVALID, entry + "sum and var must not be NULL");
+    if (!m) return fail(BDPT_ERR_INVALID, entry + "samples_per_batch must not be NULL");
+    if (!list || !count) return fail(BDPT_ERR_INVALID, entry + "out_list and out_count must not be NULL");
+    return BDPT_OK;
+}
+
+static int adaptive_select_launch(bdpt_ctx* c, int32_t width, int32_t height, const float* sum, const float* var,
+                                  float threshold, float eps, int32_t step, int32_t m_max, int32_t dilate, int32_t* m,
+                                  int32_t* list, int32_t* count, hipStream_t st) {
+    HIP_TRY(c->ad_scratch.reserve(adaptive_select_scratch_bytes(static_cast<size_t>(width) * height)));
+    HIP_TRY(launch_adaptive_select(sum, var, width, height, threshold, eps, step, m_max, dilate, m, list, count, c->ad_scratch, st));
+    return BDPT_OK;
+}
+
+int bdpt_adaptive_select(bdpt_ctx* c, int32_t width, int32_t height, const float* sum, const float* var, float threshold,
+                         float eps, int32_t step, int32_t m_max, int32_t dilate, int32_t* m, int32_t* list, int32_t* count,
+                         void* hip_stream) {
+    int rc = check_adaptive_select(width, height, sum, var, threshold, eps, step, m_max, dilate, m, list, count);
+    if (rc) return rc;
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if ((rc = begin_use(c, st))) return rc;
+    if ((rc = begin_timed(c, st))) return rc;
+    if ((rc = adaptive_select_launch(c, width, height, sum, var, threshold, eps, step, m_max, dilate, m, list, count, st)))
+        return rc;
+    return end_timed(c, st, 0, 3);
+}
+
+int bdpt_adaptive_select_host(bdpt_ctx* c, int32_t width, int32_t height, const float* sum, const float* var,
+                              float threshold, float eps, int32_t step, int32_t m_max, int32_t dilate, int32_t* m,
+                              int32_t* list, int32_t* count) {
+    int rc = check_adaptive_select(width, height, sum, var, threshold, eps, step, m_max, dilate, m, list, count);
+    if (rc) return rc;
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    const size_t N = static_cast<size_t>(width) * height, n = N * 3;
+    HIP_TRY(hipSetDevice(c->device));
+    // sum, var (floats), m, list (N int32 each), count
+    HIP_TRY(c->ad_stage.reserve(2 * n * sizeof(float) + (2 * N + 4) * sizeof(int32_t)));
+    float* const dsum = static_cast<float*>(c->ad_stage.get());
+    float* const dvar = dsum + n;
+    int32_t* const dm = reinterpret_cast<int32_t*>(dvar + n);
+    int32_t *dlist = dm + N, *dcount = dlist + N;
+    HIP_TRY(hipMemcpyAsync(dsum, sum, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dvar, var, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dm, m, N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = bdpt_adaptive_select(c, width, height, dsum, dvar, threshold, eps, step, m_max, dilate, dm, dlist, dcount, c->stream)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(count, dcount, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (*count < 0 || static_cast<size_t>(*count) > N) return fail(BDPT_ERR_HIP, "bdpt_adaptive_select: a count outside [0, width * height]");
+    HIP_TRY(hipMemcpy(m, dm, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (*count > 0) HIP_TRY(hipMemcpy(list, dlist, static_cast<size_t>(*count) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return BDPT_OK;
+}
+
+// The driver's own parameters (no context needed), then what its pixel-list renders refuse.
+static int check_adaptive(const bdpt_frame_params* p, const bdpt_adaptive_params* a) {
+    const std::string entry = "bdpt_render_adaptive: ";
+    if (int rc = check_frame_size(p)) return rc;
+    if (!a) return fail(BDPT_ERR_INVALID, entry + "null adaptive params");
+    if (a->n_batches < 2 || a->n_batches > 64) return fail(BDPT_ERR_INVALID, entry + "n_batches must be in [2, 64]");
+    if (a->step < 1) return fail(BDPT_ERR_INVALID, entry + "step must be >= 1");
+    if (a->max_passes < 1 || a->max_passes > BDPT_ADAPTIVE_MAX_PASSES)
+        return fail(BDPT_ERR_INVALID, entry + "max_passes" + in_range(BDPT_ADAPTIVE_MAX_PASSES));
+    if (static_cast<int64_t>(a->max_passes) * a->step * a->n_batches != p->spp)
+        return fail(BDPT_ERR_INVALID, entry + "spp must equal max_passes * step * n_batches (" + std::to_string(a->max_passes) +
+                                          " * " + std::to_string(a->step) + " * " + std::to_string(a->n_batches) + "), got " +
+                                          std::to_string(p->spp));
+    if (!finite_nonneg(a->threshold)) return fail(BDPT_ERR_INVALID, entry + "threshold must be finite and >= 0");
+    if (!finite_nonneg(a->eps)) return fail(BDPT_ERR_INVALID, entry + "eps must be finite and >= 0");
+    if (a->dilate != 0 && a->dilate != 1) return fail(BDPT_ERR_INVALID, entry + "dilate must be 0 or 1");
+    return BDPT_OK;
+}
+
+int bdpt_render_adaptive(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_adaptive_params* a, float* frame,
+                         float* variance, int32_t* samples, bdpt_adaptive_stats* stats, void* hip_stream) {
+    int rc = check_adaptive(p, a);
+    if (rc) return rc;
+    if (!c || !frame || !variance || !samples) return fail(BDPT_ERR_INVALID, "null argument");
+    {  // what every pass's render would refuse, before anything is allocated or launched
+        const Planes pl = pixel_planes(nullptr, 0);
+        if ((rc = check_params(p)) || (rc = check_planes(c, p, pl)) || (rc = check_pixel_list(c, p, pl)) ||
+            (rc = textured_frame_check(c, p)))
+            return rc;
+    }
+    const int32_t W = p->width, H = p->height, K = a->n_batches, step = a->step;
+    if (2ull * static_cast<uint64_t>(K) * static_cast<uint64_t>(W) * static_cast<uint64_t>(H) >= (1ull << 30))
+        return fail(BDPT_ERR_INVALID, "bdpt_render_adaptive: 2 * n_batches * width * height must be below 2^30");
+    const size_t N = static_cast<size_t>(W) * H, n = N * 3;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    HIP_TRY(c->ad_planes.reserve(sizeof(float) * 2 * n * K));
+    HIP_TRY(c->ad_m.reserve(sizeof(int32_t) * N));
+    HIP_TRY(c->ad_list.reserve(sizeof(int32_t) * N));
+    HIP_TRY(c->ad_count.reserve(16));
+    if ((rc = begin_use(c, st))) return rc;
+    HIP_TRY(hipMemsetAsync(c->ad_planes, 0, sizeof(float) * 2 * n * K, st));
+    HIP_TRY(launch_adaptive_start(N, step, c->ad_m, c->ad_list, st));
+    if ((rc = end_use(c, st))) return rc;  // (the renders below order themselves after it)
+    bdpt_adaptive_stats out{};
+    c->ad_pass_lists.clear();
+    int32_t count = static_cast<int32_t>(N);
+    int64_t M = 0;  // the sum of m over the pixels: samples per batch traced so far
+    for (int32_t j = 0; j < a->max_passes; j++) {
+        for (int32_t b = 0; b < K; b++) {  // pass j, batch b: one window, into that batch's plane pair
+            const bdpt_sample_window w = {j * step * K + b, K, step};
+            if ((rc = render_bdpt(c, p, &w, c->ad_planes + static_cast<size_t>(b) * 2 * n, st, pixel_planes(c->ad_list, count))))
+                return rc;
+        }
+        M += static_cast<int64_t>(count) * step;
+        out.active[j] = count;
+        out.passes = j + 1;
+        if (a->record_passes) {
+            const size_t at = c->ad_pass_lists.size();
+            c->ad_pass_lists.resize(at + static_cast<size_t>(count));
+            HIP_TRY(hipMemcpyAsync(c->ad_pass_lists.data() + at, c->ad_list, sizeof(int32_t) * static_cast<size_t>(count),
+                                   hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        if (j + 1 == a->max_passes) break;  // the budget
+        if ((rc = adaptive_resolve_launch(W, H, K, p->spp, c->ad_planes, c->ad_m, M, frame, variance, st))) return rc;
+        if ((rc = adaptive_select_launch(c, W, H, frame, variance, a->threshold, a->eps, step, a->max_passes * step, a->dilate,
+                                         c->ad_m, c->ad_list, c->ad_count, st)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(&count, c->ad_count, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (count < 0 || static_cast<size_t>(count) > N) return fail(BDPT_ERR_HIP, "bdpt_render_adaptive: a count outside [0, width * height]");
+        if (count == 0) break;  // every pixel settled, or at its budget
+    }
+    out.samples = M * K;
+    if ((rc = adaptive_resolve_launch(W, H, K, p->spp, c->ad_planes, c->ad_m, M, frame, variance, st))) return rc;
+    HIP_TRY(launch_adaptive_samples(N, K, c->ad_m, samples, st));
+    if ((rc = end_use(c, st))) return rc;
+    if (stats) *stats = out;
+    return BDPT_OK;
+}
+
+int bdpt_render_adaptive_host(bdpt_ctx* c, const bdpt_frame_params* p, const bdpt_adaptive_params* a, float* frame,
+                              float* variance, int32_t* samples, bdpt_adaptive_stats* stats) {
+    int rc = check_adaptive(p, a);
+    if (rc) return rc;
+    if (!c || !frame || !variance || !samples) return fail(BDPT_ERR_INVALID, "null argument");
+    const size_t N = static_cast<size_t>(p->width) * p->height, n = N * 3;
+    const size_t n16 = (n + 3) & ~static_cast<size_t>(3);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->ad_stage.reserve(2 * n16 * sizeof(float) + N * sizeof(int32_t)));
+    float* const dframe = static_cast<float*>(c->ad_stage.get());
+    float* const dvar = dframe + n16;
+    int32_t* const dsamples = reinterpret_cast<int32_t*>(dvar + n16);
+    if ((rc = bdpt_render_adaptive(c, p, a, dframe, dvar, dsamples, stats, c->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(frame, dframe, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(variance, dvar, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(samples, dsamples, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    bdpt_stats bs;
+    if ((rc = bdpt_get_stats(c, &bs))) return rc;
+    if (bs.schedule_errors) return fail(BDPT_ERR_HIP, std::to_string(bs.schedule_errors) + " schedule errors");
+    return BDPT_OK;
+}
+
+int bdpt_adaptive_pass_lists(bdpt_ctx* c, int32_t* out, int64_t capacity, int64_t* total) {
+    if (!c || !total) return fail(BDPT_ERR_INVALID, "null argument");
+    *total = static_cast<int64_t>(c->ad_pass_lists.size());
+    if (!out) return BDPT_OK;
+    if (capacity < *total) return fail(BDPT_ERR_INVALID, "bdpt_adaptive_pass_lists: capacity is below the lists' length");
+    std::copy(c->ad_pass_lists.begin(), c->ad_pass_lists.end(), out);
     return BDPT_OK;
 }
 

@@ -1107,7 +1107,25 @@ __device__ __forceinline__ void conn_batch(Lane& L, bool owner, const DevScene& 
 // (the per-(pixel, sample) convention of SURVEY §8c on renderer.cpp:155). The shard's
 // work index runs over W * win_count samples per row; the i-th of a pixel is the frame's
 // sample k = win_first + i * win_stride (the whole frame: k = i), seeded with the full spp.
+//
+// The pixel-list build (BDPT_PIXEL_LIST 1: bdpt_kernels_pixels.hip) renders the
+// window's samples of a list of pixels instead of whole rows: work index s is sample
+// k = win_first + (s % win_count) * win_stride of pixel pixel_list[s / win_count], and
+// total_samples = n_pixels * win_count. A wave seeds all 64 samples of the chunk it claimed, also
+// the ones past the frame's end that no lane starts; those read the list's first entry, so the
+// list is never read past its end. The seed and the 1 / spp weight are the frame's.
+#ifndef BDPT_PIXEL_LIST
+#define BDPT_PIXEL_LIST 0
+#endif
+#if BDPT_PIXEL_LIST && !BDPT_STRATS
+#error "BDPT_PIXEL_LIST is a form of the strategy build (BDPT_STRATS)"
+#endif
 __device__ __forceinline__ uint32_t sample_seed(uint64_t s, const DevFrame& fr, int& pixel) {
+#if BDPT_PIXEL_LIST
+    const uint64_t e = s < fr.total_samples ? s / static_cast<uint32_t>(fr.win_count) : 0;
+    const int k = fr.win_first + static_cast<int>(s % static_cast<uint32_t>(fr.win_count)) * fr.win_stride;
+    pixel = static_cast<int>(((const gbl_i32*)fr.pixel_list)[e]);
+#else
     const uint64_t per_row = static_cast<uint64_t>(fr.W) * fr.win_count;
     uint64_t lr = s / per_row;
     const uint64_t q = s % per_row;
@@ -1116,6 +1134,7 @@ __device__ __forceinline__ uint32_t sample_seed(uint64_t s, const DevFrame& fr, 
     const int k = fr.win_first + static_cast<int>(q % fr.win_count) * fr.win_stride;
     const int row = fr.row_offset + static_cast<int>(lr) * fr.row_stride;
     pixel = row * fr.W + j;
+#endif
     return fr.seed_base + static_cast<uint32_t>(pixel) * static_cast<uint32_t>(fr.spp) + static_cast<uint32_t>(k);
 }
 

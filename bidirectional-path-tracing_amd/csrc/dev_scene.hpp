@@ -202,8 +202,15 @@ struct DevFrame {
     float4* tasks;
     uint32_t task_cap;
     // the shard's row claim order (bdpt_set_row_order; null: top to bottom) and, in a
-    // counting pass, the queries issued per local row (null otherwise)
-    const int32_t* row_order;
+    // counting pass, the queries issued per local row (null otherwise).
+    // The pixel-list build (bdpt_render_pixels, bdpt_kernels_pixels.hip) keeps its list in the same
+    // word: total_samples / win_count ascending pixel indices in [0, W * H). A pixel-list render
+    // refuses row shards and a row order, and no other build reads the word as a list, so the
+    // record and every other build's code stay as they were.
+    union {
+        const int32_t* row_order;
+        const int32_t* pixel_list;
+    };
     // light groups (bdpt_render_light_groups, the bdpt_kernels_groups.hip build): the framebuffer
     // is n_groups consecutive W x H x 3 planes and a contribution goes to plane emitter_group[e]
     // of the emitter e its path ends on (one int32 per emitter, each in [0, n_groups)). It shares

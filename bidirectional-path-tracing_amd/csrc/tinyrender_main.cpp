@@ -59,6 +59,12 @@
 // renders the feature buffers over the same samples and writes <out>_denoised.exr from
 // bdpt_denoise_var_host (the header's BDPT_DENOISE_VAR_* defaults, ITER iterations 0..8). Combines with
 // --aov. Each misuse is refused, the flag named, before any device is used.
+// --adaptive THR[:K[:STEP[:PASSES]]] (a bdpt scene, one device) renders with bdpt_render_adaptive_host: spp is
+// the budget per pixel and must equal PASSES * STEP * K (K batches, default 8; STEP samples per batch and
+// pass, default 1; PASSES default spp / (STEP * K)); a pixel gets further passes while its relative standard
+// deviation across the batches exceeds THR. Writes the frame, <out>_variance.exr (its per-pixel variance)
+// and <out>_samples.exr (the samples each pixel had, as a grey value). Refused, the flag named, with --gpus /
+// --devices, --layers, --light-groups, --strategies, --batches, --cross, --denoise-planes and --sample-window.
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
@@ -114,7 +120,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Syntax: %s <scene.toml> [nogui] [--width W --height H --spp N --rr D --device K "
                              "--out FILE.exr --seed S --gpus N --devices a,b,... --shard samples|rows "
-                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted] --cross --denoise-planes[=own|shared] --batches K --denoise-var[=ITER]]\n", argv[0]);
+                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted] --cross --denoise-planes[=own|shared] --batches K --denoise-var[=ITER] --adaptive THR[:K[:STEP[:PASSES]]]]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string toml = argv[1];
@@ -133,6 +139,8 @@ int main(int argc, char** argv) {
     bool cross = false;         // --cross: the groups crossed with the layers or the strategies
     int denoise_planes = -1;    // --denoise-planes[=own|shared]: BDPT_DENOISE_PLANES_* (-1: none)
     int batches = 0;            // --batches K (0: none)
+    bool adaptive = false;      // --adaptive THR[:K[:STEP[:PASSES]]]
+    bdpt_adaptive_params ad = {8, 1, 0, 0.f, 1e-3f, 1, 0};  // (max_passes 0: spp / (step * n_batches))
     bool want_denoise_var = false;  // --denoise-var[=ITER]
     int denoise_var_iterations = BDPT_DENOISE_VAR_ITERATIONS;
     for (int i = 2; i < argc; i++) {
@@ -211,6 +219,24 @@ int main(int argc, char** argv) {
                 return EXIT_FAILURE;
             }
             batches = static_cast<int>(n);
+        } else if (a == "--adaptive") {
+            const char* v = next("--adaptive");
+            char* end = nullptr;
+            ad.threshold = std::strtof(v, &end);
+            long f[3] = {ad.n_batches, ad.step, 0};
+            bool ok = end != v && ad.threshold >= 0.f && ad.threshold < 1e30f;
+            for (int k = 0; ok && k < 3 && *end == ':'; k++) {
+                const char* q = end + 1;
+                f[k] = std::strtol(q, &end, 10);
+                ok = end != q && f[k] >= 1 && f[k] <= 1 << 20;
+            }
+            if (!ok || *end != '\0' || f[0] < 2 || f[0] > 64 || f[2] > BDPT_ADAPTIVE_MAX_PASSES) {
+                std::fprintf(stderr, "--adaptive %s: THR[:K[:STEP[:PASSES]]] with THR >= 0, K in [2, 64], STEP >= 1, PASSES in [1, %d]\n",
+                             v, BDPT_ADAPTIVE_MAX_PASSES);
+                return EXIT_FAILURE;
+            }
+            adaptive = true;
+            ad.n_batches = static_cast<int32_t>(f[0]), ad.step = static_cast<int32_t>(f[1]), ad.max_passes = static_cast<int32_t>(f[2]);
         } else if (a == "--denoise-planes" || a == "--denoise-planes=shared") {
             denoise_planes = BDPT_DENOISE_PLANES_SHARED;
         } else if (a == "--denoise-planes=own") {
@@ -288,6 +314,15 @@ int main(int argc, char** argv) {
                              "--cross or --denoise-planes\n");
         return EXIT_FAILURE;
     }
+    if (adaptive) {
+        const char* with = !devices.empty() ? "--gpus / --devices" : layers ? "--layers" : light_groups ? "--light-groups"
+                           : strategies >= 0 ? "--strategies" : batches ? "--batches" : cross ? "--cross"
+                           : denoise_planes >= 0 ? "--denoise-planes" : windowed ? "--sample-window" : nullptr;
+        if (with) {
+            std::fprintf(stderr, "--adaptive chooses each pixel's samples itself, on one device and one frame: not with %s\n", with);
+            return EXIT_FAILURE;
+        }
+    }
     if (shard_given && devices.empty()) {
         std::fprintf(stderr, "--shard applies to a multi-device render (--gpus N / --devices a,b,...)\n");
         return EXIT_FAILURE;
@@ -327,10 +362,24 @@ int main(int argc, char** argv) {
                      cfg.integrator);
         return EXIT_FAILURE;
     }
+    if (adaptive && (path || direct)) {
+        std::fprintf(stderr, "--adaptive samples a bdpt frame (integrator type \"%s\" has no pixel-list kernel)\n", cfg.integrator);
+        return EXIT_FAILURE;
+    }
     if (W > 0) cfg.width = W;
     if (H > 0) cfg.height = H;
     if (spp > 0) cfg.spp = spp;
     if (rr > 0) cfg.rr_depth = rr;
+    if (adaptive) {  // spp is the budget: PASSES * STEP * K
+        const int per_pass = ad.step * ad.n_batches;
+        if (ad.max_passes == 0) ad.max_passes = cfg.spp / per_pass;
+        if (ad.max_passes < 1 || ad.max_passes > BDPT_ADAPTIVE_MAX_PASSES ||
+            static_cast<long long>(ad.max_passes) * per_pass != cfg.spp) {
+            std::fprintf(stderr, "--adaptive: spp (%d) must be PASSES * STEP * K with PASSES in [1, %d] (STEP * K = %d)\n",
+                         cfg.spp, BDPT_ADAPTIVE_MAX_PASSES, per_pass);
+            return EXIT_FAILURE;
+        }
+    }
     int32_t n_s = 0, n_t = 0;  // --strategies: the shape that clamps nothing
     if (strategies >= 0 && bdpt_strategies_shape(cfg.rr_depth, BDPT_STRATEGY_BDPT, &n_s, &n_t) != BDPT_OK)
         return die("--strategies");
@@ -387,7 +436,14 @@ int main(int argc, char** argv) {
     const bdpt_sample_window* const win = windowed ? &window : nullptr;  // null: every sample
     // --batches: the K planes (plane b: the window's samples b, b + K, ...), then their sum in rgb and its variance
     std::vector<float> batch_planes, variance;
+    std::vector<int32_t> sample_map;  // --adaptive: samples per pixel
+    bdpt_adaptive_stats ad_stats{};
     auto render_window = [&](const bdpt_path_params* pp, const bdpt_direct_params* dp) -> int {
+        if (adaptive) {
+            variance.resize(rgb.size());
+            sample_map.resize(rgb.size() / 3);
+            return bdpt_render_adaptive_host(ctx, &p, &ad, rgb.data(), variance.data(), sample_map.data(), &ad_stats);
+        }
         if (!batches) return bdpt_render_window_host(ctx, &p, win, pp, dp, rgb.data());
         const bdpt_sample_window base = windowed ? window : bdpt_sample_window{0, 1, cfg.spp};
         batch_planes.assign(rgb.size() * batches, 0.f);
@@ -432,7 +488,16 @@ int main(int argc, char** argv) {
     const std::string exr = out.empty() ? exr_path_of(toml) : out;
     if (bdpt_save_exr(rgb.data(), cfg.width, cfg.height, exr.c_str()) != BDPT_OK) return die("saveEXR");
     std::printf("\nSaved EXR image to %s\n", exr.c_str());  // utils.h:149
-    if (batches) {
+    if (adaptive) {
+        std::printf("adaptive: %d passes, %lld samples (uniform: %lld)\n", ad_stats.passes,
+                    static_cast<long long>(ad_stats.samples), static_cast<long long>(sample_map.size()) * cfg.spp);
+        std::vector<float> grey(rgb.size());
+        for (size_t i = 0; i < sample_map.size(); i++) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = static_cast<float>(sample_map[i]);
+        const std::string side = side_path(exr, "_samples");
+        if (bdpt_save_exr(grey.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
+        std::printf("Saved EXR image to %s\n", side.c_str());
+    }
+    if (batches || adaptive) {
         const std::string side = side_path(exr, "_variance");
         if (bdpt_save_exr(variance.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
         std::printf("Saved EXR image to %s\n", side.c_str());

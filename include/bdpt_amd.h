@@ -46,6 +46,8 @@
  *                            of their own or one set for all, under which the planes still add up
  *   bdpt_batch_moments       (no counterpart) the per-pixel sum and variance across sample batches
  *   bdpt_denoise_var         (no counterpart) the filter with its colour weight in standard deviations
+ *   bdpt_render_pixels       (no counterpart) a sample window of the BDPT frame for a list of pixels
+ *   bdpt_render_adaptive     (no counterpart) further samples only where the batch variance asks
  *
  * Conventions: plain C types only; status 0 = OK, < 0 = error (message from
  * bdpt_last_error(), thread-local). A context is bound to one HIP device and is
@@ -772,6 +774,116 @@ int bdpt_group_planes_combine(bdpt_ctx* ctx, const float* planes_device, int32_t
 int bdpt_group_planes_combine_host(bdpt_ctx* ctx, const float* planes_host, int32_t n_groups, int32_t n_inner,
                                    int32_t width, int32_t height, const float* gains, const float* weights,
                                    float* out_host);
+
+/* ---- adaptive sampling: a pixel-list frame kernel, its state kernels and the driver ---- */
+/* (new) Not in the reference. bdpt_render_pixels renders, for each of the n_pixels pixels of a list, the
+ * window's samples k = first + i * stride of that pixel, with the seed seed_base + pixel * spp + k and
+ * the 1 / spp weight of the frame's full spp: the very samples bdpt_render_window renders for those
+ * pixels. fb is TWO consecutive width * height * 3 planes, ADDED to and never zeroed (so passes
+ * accumulate): plane 0 takes the camera splats of the samples' light paths (t = 1: they land on any
+ * pixel of the image), plane 1 everything formed at the sample's own pixel (t >= 2) - the planes of
+ * bdpt_render_strategies at shape (1, 2). Plane 1 stays untouched at every unlisted pixel. With the
+ * list 0 .. width * height - 1 the two planes are bdpt_render_strategies(1, 2)'s.
+ * The list: entries in [0, width * height), strictly ascending (so n_pixels <= width * height). The host
+ * form checks that (BDPT_ERR_INVALID, the entry named). The DEVICE form trusts it: an index outside the
+ * image would send the kernel's atomic adds outside the framebuffer, so pass it only a list that
+ * bdpt_adaptive_select wrote or that was checked as the host form checks. n_pixels == 0 or an empty
+ * window launches nothing.
+ * BDPT_ERR_INVALID: a bad window, n_pixels outside [0, width * height], a NULL list with n_pixels > 0,
+ * row_offset != 0 or row_stride != 1, a row order set on the context (bdpt_set_row_order), 2 * width *
+ * height >= 2^30. BDPT_ERR_UNSUPPORTED (the message says "pixel lists"), before any launch: what
+ * bdpt_render_strategies refuses. bdpt_last_kernel afterwards: "bdpt_frame_kernel_pixels";
+ * bdpt_get_stats().samples = n_pixels * count. Asynchronous on `hip_stream`; the host form stages the
+ * list and the two planes and is synchronous. */
+int bdpt_render_pixels(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                       const int32_t* pixels_device, int32_t n_pixels, float* fb_device, void* hip_stream);
+int bdpt_render_pixels_host(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_sample_window* window,
+                            const int32_t* pixels_host, int32_t n_pixels, float* fb_host);
+
+/* (new) The frame and its variance from K = n_batches accumulated plane pairs. planes: K consecutive
+ * pairs as bdpt_render_pixels accumulates them, pair b = (T_b splats, E_b eye), each width * height * 3
+ * floats. samples_per_batch: int32 m[p] per pixel, the samples of each batch pixel p has had. With
+ * M = sum m and the splat scale t = (float)((double)spp * width * height / ((double)K * M)) formed on the
+ * host (0 when M == 0), per pixel and channel in float32, every operation rounded on its own:
+ *   a = m[p] > 0 ? (float)spp / (float)(K * m[p]) : 0           one IEEE division
+ *   plane_b = E_b * a + T_b * t
+ * and on those K planes exactly bdpt_batch_moments: out_sum = S, out_var = the variance of S. The eye
+ * part of a pixel is a mean over its own samples and the splat part a mean over all M * K light paths
+ * of the frame, which is why the two are kept apart. With m = spp / K everywhere both scales are 1 and
+ * the outputs have the bits of bdpt_batch_moments on E_b + T_b. No atomics: the same bits every run.
+ * splat_total: M as the caller counted it (the driver knows it from its passes); < 0: counted here on
+ * the host from samples_per_batch (host form only; the device form needs it >= 0).
+ * BDPT_ERR_INVALID, the field named: n_batches outside 2..64, spp < 1, 2 * n_batches * width * height
+ * >= 2^30, a NULL pointer. Asynchronous on `hip_stream`; the host form is synchronous. */
+int bdpt_adaptive_resolve(bdpt_ctx* ctx, int32_t width, int32_t height, int32_t n_batches, int32_t spp,
+                          const float* planes_device, const int32_t* samples_per_batch_device, int64_t splat_total,
+                          float* out_sum_device, float* out_var_device, void* hip_stream);
+int bdpt_adaptive_resolve_host(bdpt_ctx* ctx, int32_t width, int32_t height, int32_t n_batches, int32_t spp,
+                               const float* planes_host, const int32_t* samples_per_batch_host, int64_t splat_total,
+                               float* out_sum_host, float* out_var_host);
+
+/* (new) The pixels that get `step` more samples per batch. Per pixel p, float32 in this order:
+ *   noisy(p)  = (var_r + var_g + var_b) > (threshold * threshold) * ((S_r + S_g + S_b + eps) * (S_r + S_g + S_b + eps))
+ *               (a relative standard deviation against the threshold, without the square root)
+ *   wanted(p) = dilate ? noisy(q) for any q of p's 3 x 3 neighbourhood clipped to the image : noisy(p)
+ *   active(p) = wanted(p) && m[p] + step <= m_max
+ * out_list (room for width * height int32) receives the active pixel indices in ASCENDING order,
+ * *out_count their number, and m[p] += step for exactly those pixels. An ordered compaction without
+ * atomics: the same list every run. The device form writes out_count on the device (one int32).
+ * BDPT_ERR_INVALID, the field named: a threshold or eps that is negative or not finite, step < 1,
+ * m_max < 0, dilate outside {0, 1}, width * height >= 2^30, a NULL pointer. */
+int bdpt_adaptive_select(bdpt_ctx* ctx, int32_t width, int32_t height, const float* sum_device, const float* var_device,
+                         float threshold, float eps, int32_t step, int32_t m_max, int32_t dilate,
+                         int32_t* samples_per_batch_device, int32_t* out_list_device, int32_t* out_count_device,
+                         void* hip_stream);
+int bdpt_adaptive_select_host(bdpt_ctx* ctx, int32_t width, int32_t height, const float* sum_host, const float* var_host,
+                              float threshold, float eps, int32_t step, int32_t m_max, int32_t dilate,
+                              int32_t* samples_per_batch_host, int32_t* out_list_host, int32_t* out_count_host);
+
+/* (new) The driver. The frame's budget is params->spp = max_passes * step * n_batches samples per
+ * pixel (anything else is BDPT_ERR_INVALID). Pass j renders, for every pixel of its list and every
+ * batch b, the window (first = j * step * K + b, stride K, count step) with bdpt_render_pixels into
+ * batch b's plane pair: K launches. Pass 0 lists every pixel. After a pass: bdpt_adaptive_resolve, then
+ * bdpt_adaptive_select with m_max = max_passes * step; the count comes to the host (one 4-byte read per
+ * pass), which stops on an empty list or at the budget and runs a last resolve. A pixel that skips a
+ * pass skips those sample indices; samples are independent by seed, and a run in which every pixel
+ * stays active renders exactly the samples of bdpt_render. Choosing a pixel's samples from the estimate
+ * they feed biases it, as in every adaptive sampler of this kind; threshold = 0 (every pixel with any
+ * variance stays active) is the unbiased frame.
+ * frame, variance: width * height * 3 floats each, overwritten; samples: width * height int32, the
+ * samples each pixel has had (K * m). stats (NULL: not wanted): filled when the call returns.
+ * record_passes != 0 keeps every pass's list on the host for bdpt_adaptive_pass_lists.
+ * BDPT_ERR_INVALID, the field named: n_batches outside 2..64, step < 1, max_passes outside
+ * 1..BDPT_ADAPTIVE_MAX_PASSES, spp != max_passes * step * n_batches, a threshold or eps that is negative
+ * or not finite, dilate outside {0, 1}; then what bdpt_render_pixels refuses. The device form takes
+ * device pointers and returns once the last resolve is enqueued on `hip_stream` (it has waited for each
+ * pass's count before); the host form is synchronous. */
+#define BDPT_ADAPTIVE_MAX_PASSES 64
+typedef struct {
+    int32_t n_batches;     /* K */
+    int32_t step;          /* c: samples per batch a pass adds to an active pixel */
+    int32_t max_passes;
+    float threshold;       /* relative standard deviation below which a pixel is settled */
+    float eps;             /* floor added to the channel sum of S */
+    int32_t dilate;        /* 1: a noisy pixel keeps its 3 x 3 neighbourhood active */
+    int32_t record_passes; /* 1: keep the passes' lists for bdpt_adaptive_pass_lists */
+} bdpt_adaptive_params;
+typedef struct {
+    int32_t passes;        /* passes rendered */
+    int32_t reserved;
+    int64_t samples;       /* camera samples traced: K * step * the sum of active[] */
+    int32_t active[BDPT_ADAPTIVE_MAX_PASSES]; /* pixels listed in pass j (0 beyond `passes`) */
+} bdpt_adaptive_stats;
+int bdpt_render_adaptive(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_adaptive_params* adaptive,
+                         float* frame_device, float* variance_device, int32_t* samples_device,
+                         bdpt_adaptive_stats* stats, void* hip_stream);
+int bdpt_render_adaptive_host(bdpt_ctx* ctx, const bdpt_frame_params* params, const bdpt_adaptive_params* adaptive,
+                              float* frame_host, float* variance_host, int32_t* samples_host,
+                              bdpt_adaptive_stats* stats);
+/* The lists of the last bdpt_render_adaptive with record_passes, one after the other (pass j has
+ * stats.active[j] entries). *total receives their length; out (NULL: only the length is wanted) must
+ * hold `capacity` >= *total entries (BDPT_ERR_INVALID otherwise). */
+int bdpt_adaptive_pass_lists(bdpt_ctx* ctx, int32_t* out, int64_t capacity, int64_t* total);
 
 /* ---- several HIP devices in one process ---- */
 /* The reference fans the offline loop out over host threads (parallel_for,
