@@ -294,6 +294,7 @@ def lib():
         L.bdpt_intersect_from.argtypes = [vp, ctypes.c_int64, vp, vp, vp, i32, vp]
         L.bdpt_intersect_deferred.argtypes = [vp, ctypes.c_int64, vp, vp, vp, vp, vp]
         L.bdpt_get_leaf_rewalks.argtypes = [vp, ctypes.c_int64 * 2]
+        L.bdpt_get_grid.argtypes = [vp, ctypes.c_int64 * 2]
         L.bdpt_scene_create.argtypes = [ctypes.POINTER(_SceneDesc), ctypes.POINTER(vp)]
         L.bdpt_scene_export_layout.argtypes = [vp, i32, vp, ctypes.POINTER(ctypes.c_int64)]
         L.bdpt_scene_export_shade_records.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64)]
@@ -2049,7 +2050,9 @@ class BDPTIntegrator:
         _check(lib().bdpt_get_stats(self._h, ctypes.byref(s)))
         leaf = (ctypes.c_int64 * 2)()  # (bdpt_get_leaf_rewalks: an entry of its own, bdpt_stats keeps its layout)
         _check(lib().bdpt_get_leaf_rewalks(self._h, leaf))
-        return dict(leaf_rewalks=leaf[0], leaf_hits=leaf[1], kernel_ms=s.kernel_ms, samples=s.samples, launches=s.launches,
+        grid = (ctypes.c_int64 * 2)()  # (bdpt_get_grid: frame-kernel blocks, lane slots)
+        _check(lib().bdpt_get_grid(self._h, grid))
+        return dict(leaf_rewalks=leaf[0], leaf_hits=leaf[1], grid=grid[0], slots=grid[1], kernel_ms=s.kernel_ms, samples=s.samples, launches=s.launches,
                     counters=dict(zip(COUNTER_NAMES, list(s.counters))), capped_samples=s.capped_samples,
                     span_ms=s.span_ms, tail_ms=s.tail_ms, max_light_depth=s.max_light_depth,
                     max_eye_depth=s.max_eye_depth, max_queries=s.max_queries, schedule_errors=s.schedule_errors, parked_samples=s.parked_samples,

@@ -1930,6 +1930,14 @@ int bdpt_get_stats(bdpt_ctx* c, bdpt_stats* out) {
     return BDPT_OK;
 }
 
+// out[0]: the frame kernels' grid in blocks, out[1]: the lane slots (read-only; nothing is launched)
+int bdpt_get_grid(const bdpt_ctx* c, int64_t out[2]) {
+    if (!c || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    out[0] = c->grid;
+    out[1] = c->nslots;
+    return BDPT_OK;
+}
+
 // out[0]: checked re-walks, out[1]: closest hits applied, of the last BDPT frame render, a counting
 // pass of a build with the deferred reference-leaf check (dev::kDiagLeafRewalks, kDiagLeafHits); 0
 // for every other render.

@@ -1009,6 +1009,10 @@ int bdpt_intersect_deferred(bdpt_ctx* ctx, int64_t n, const float* rays, const f
  * accel.h:133's range) in the context's last BDPT frame render, counted by a counting pass
  * (BDPT_FLAG_COUNT) of a frame-kernel build with the deferred check; 0 otherwise. */
 int bdpt_get_leaf_rewalks(bdpt_ctx* ctx, int64_t out[2]);
+/* (new) out[0]: the blocks of a frame-kernel launch (the context's persistent grid), out[1]: the lane
+ * slots the context serves at a time (grid x block, before any debugging knob narrows the grid): the
+ * feature-buffer kernel runs at most out[1] / 64 blocks and strides over its 8 x 8 tiles beyond that. */
+int bdpt_get_grid(const bdpt_ctx* ctx, int64_t out[2]);
 /* BDPTIntegrator::splatToImagePlane (bdpt.h:485-496) of points p (n x 3) for the
  * camera and image of params: xy = n x 2 (the reference's int truncation). */
 int bdpt_splat_to_image_plane(bdpt_ctx* ctx, const bdpt_frame_params* params, int64_t n, const float* p,
