@@ -512,6 +512,19 @@ static uint32_t graze_code(const float* v0, const float* v1, const float* v2, co
     double g[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
     const double gl = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
     if (!(gl > 0.0) || !std::isfinite(gl)) return 255u;
+    {  // A sliver: the near cull's argument (dev_traverse.hpp kGrazeCos) needs every corner above ~0.35
+       // degrees; below it the triangle test's t on a coplanar origin is noise the reference may accept
+       // at any |cos|, so queries leaving such a triangle always walk without the near cull.
+        constexpr double kMinCornerSin = 6.2e-3;  // sin(0.355 degrees)
+        double e3[3];
+        for (int a = 0; a < 3; a++) e3[a] = double(v2[a]) - v1[a];
+        const double l1 = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+        const double l2 = std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+        const double l3 = std::sqrt(e3[0] * e3[0] + e3[1] * e3[1] + e3[2] * e3[2]);
+        // sin of the corner between two sides = |cross| / (their lengths); |cross| is gl for every pair
+        const double smallest = gl / std::max(l1 * l2, std::max(l1 * l3, l2 * l3));
+        if (!(smallest >= kMinCornerSin)) return 255u;
+    }
     double worst = 0.0;  // max over corners of 2 sin(th / 2) = |n_k - sgn n_g|
     int sgn = 0;
     for (int k = 0; k < 3; k++) {

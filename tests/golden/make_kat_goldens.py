@@ -18,6 +18,10 @@ of the BDPT path (ref_bdpt kat / sample_state, oracle/ref/ref_driver.cpp):
   kat_adversarial_<scene>.npz  AcceleratorBVH::intersect + the any-hit query on rays where the
                             product traversal's exactness argument is thinnest (grazing, ties,
                             surface origins, origins beyond 100 scene diagonals)
+  kat_geom_<scene>.npz      the same two queries on the generated scenes of scenes/variants.py GEOM_SCENES
+                            (`python make_kat_goldens.py generated`): one-leaf and first-split trees, a
+                            zero-thick grid, exact duplicates, detail below the box padding, slivers, a
+                            52-level chain; ray kinds of tests/geom_rays.py
   kat_sampler_<integ>.npz   Integrator::render(ray, sampler) from arbitrary std::mt19937 states
                             (integrator.h:31; bdpt.h:219, path.h:235, direct.h:449)
 The sampling side (`python make_kat_goldens.py sampling`; draws enter as std::mt19937 output words):
@@ -555,6 +559,38 @@ def adversarial_fixture(scene, n, seed):
           int(out[:, 20].sum()), "per kind", np.bincount(kind))
 
 
+# Seeds at which the reference's own results meet tests/test_geom_walk_cpu.py's conditions (hits and misses in
+# every ray kind that can have them; flat's rays leaving the grid can only hit the small emitter: seed 84 has none).
+GEOM_SEEDS = dict(tiny1=80, tiny2=81, tiny4=82, tiny5=83, flat=85, dupes=85, scales=86, slivers=87, chain=88)
+
+
+def generated_fixture(name, n=2048, seed=0):
+    """kat_geom_<name>.npz: a generated scene of variants.GEOM_SCENES (geometry classes the shipped
+    scenes lack), rays of tests/geom_rays.py's kinds with the surfaces they leave, the reference's
+    21-word intersect output on them, and the SHA-256 of the OBJ text the reference read."""
+    sys.path.insert(0, os.path.join(REPO, "bidirectional-path-tracing_amd"))
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import bdpt_amd
+    import geom_rays
+
+    cam = variants.GEOM_SCENES[name][2]
+    obj = variants.geom_obj(name, os.path.join(TMP, "geom"))
+    tf, _, nf, _ = bdpt_amd.Scene(obj).export()  # host-only ingest: the triangles and the scene box to aim at
+    rays, kind, onrm, otri, osn = geom_rays.geometry_rays(name, tf, nf, cam["eye"], n, seed)
+    f3 = lambda v: "[ " + ", ".join(repr(float(x)) for x in v) + " ]"
+    path = os.path.join(TMP, f"geom_{name}.toml")
+    with open(path, "w") as f:
+        f.write(f'[input]\nobjfile = "{obj}"\n\n[camera]\neye = {f3(cam["eye"])}\nat = {f3(cam["at"])}\n'
+                f'up = {f3(cam["up"])}\nfov = {float(cam["fov"])!r}\n\n[film]\nwidth = 64\nheight = 64\n\n'
+                f'[renderer]\nrealtime = false\ntype = "bdpt"\nrrDepth = 5\nrrProb = 0.95\nspp = 1\n')
+    out = kat(path, 64, 64, "intersect", rays, 21)
+    dst = os.path.join(HERE, f"kat_geom_{name}.npz")
+    np.savez_compressed(dst, rays=rays, kind=kind, onrm=onrm, otri=otri, osn=osn, out=out,
+                        obj_sha256=np.array(variants.file_sha256(obj)))
+    print("generated", name, rays.shape[0], "rays; hits", int(out[:, 0].sum()), "occluded", int(out[:, 20].sum()),
+          "per kind", np.bincount(kind), os.path.getsize(dst), "bytes")
+
+
 def splat_fixture(seed=5):
     rng = np.random.default_rng(seed)
     res = {}
@@ -910,6 +946,10 @@ def main():
         for i, (sc, n) in enumerate([("caustic", 48000), ("hardlight", 48000), ("synth1m", 30000)]):
             adversarial_fixture(sc, n, seed=40 + i)
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "generated":  # only the generated-geometry fixtures
+        for name in variants.GEOM_SCENES:
+            generated_fixture(name, seed=GEOM_SEEDS[name])
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "bsdf_edges":  # only this fixture
         bsdf_edges_fixture()
         return
@@ -925,6 +965,8 @@ def main():
     for i, (sc, n) in enumerate([("caustic", 48000), ("hardlight", 48000), ("synth1m", 30000)]):
         adversarial_fixture(sc, n, seed=40 + i)
     bsdf_edges_fixture()
+    for name in variants.GEOM_SCENES:
+        generated_fixture(name, seed=GEOM_SEEDS[name])
     sampler_fixture("bdpt_caustic", "caustic", toml("caustic", 64, 64, 16, 8), 64, 64, 16, 8, 160, 30)
     sampler_fixture("bdpt_hardlight_rr12", "hardlight", toml("hardlight", 64, 64, 16, 12), 64, 64, 16, 12, 100, 31)
     sampler_fixture("path_caustic", "caustic", toml("caustic", 64, 64, 16, kind="path"), 64, 64, 16, 5, 80, 32)
