@@ -244,9 +244,15 @@ class _AdaptiveStats(ctypes.Structure):  # bdpt_adaptive_stats
                 ("active", ctypes.c_int32 * ADAPTIVE_MAX_PASSES)]
 
 
+class _ReprojectParams(ctypes.Structure):  # bdpt_reproject_params
+    _fields_ = [("prev_camera", _Camera), ("norm", ctypes.c_float), ("cur_samples", ctypes.c_float),
+                ("max_history", ctypes.c_float), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float),
+                ("min_weight", ctypes.c_float), ("clamp_sigma", ctypes.c_float), ("demodulate", ctypes.c_int32)]
+
+
 # Sources that make up the frame kernels' code objects: their hash stamps the
 # profiles (PMC passes) so bench.py only reuses a measurement of the same kernel.
-KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_kernels_layers.hip", "csrc/bdpt_kernels_groups.hip", "csrc/bdpt_kernels_strat.hip", "csrc/bdpt_kernels_strat_unweighted.hip", "csrc/bdpt_kernels_pixels.hip", "csrc/adaptive_kernels.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
+KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_kernels_layers.hip", "csrc/bdpt_kernels_groups.hip", "csrc/bdpt_kernels_strat.hip", "csrc/bdpt_kernels_strat_unweighted.hip", "csrc/bdpt_kernels_pixels.hip", "csrc/adaptive_kernels.hip", "csrc/temporal_kernels.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
                   "csrc/dev_scene.hpp", "csrc/dev_rng.hpp", "csrc/dev_warp.hpp", "csrc/dev_traverse.hpp", "csrc/dev_shade.hpp", "csrc/dev_emitter.hpp",
                   "csrc/powf_restated.inc", "csrc/bdpt_types.h", "Makefile")
 
@@ -360,6 +366,10 @@ def lib():
         L.bdpt_render_adaptive_host.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_AdaptiveParams), vp, vp,
                                                 vp, ctypes.POINTER(_AdaptiveStats)]
         L.bdpt_adaptive_pass_lists.argtypes = [vp, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+        L.bdpt_reproject.argtypes = [vp, ctypes.POINTER(_FrameParams), vp, vp, vp, vp, vp,
+                                     ctypes.POINTER(_ReprojectParams), vp]
+        L.bdpt_reproject_host.argtypes = [vp, ctypes.POINTER(_FrameParams), vp, vp, vp, vp, vp,
+                                          ctypes.POINTER(_ReprojectParams)]
         L.bdpt_denoise_var.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(_DenoiseParams), vp]
         L.bdpt_denoise_var_host.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(_DenoiseParams)]
         L.bdpt_render_layers.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp, vp]
@@ -1180,6 +1190,141 @@ def adaptive_windows(n_batches: int, step: int, n_pass: int) -> list:
     return [SampleWindow(n_pass * step * n_batches + b, n_batches, step) for b in range(n_batches)]
 
 
+@dataclass
+class ReprojectSettings:
+    """bdpt_reproject_params with the header's defaults (BDPT_REPROJECT_*); prev_camera, norm and cur_samples
+    are set per call."""
+    max_history: float = 16.0
+    sigma_normal: float = 0.3
+    sigma_depth: float = 0.02
+    min_weight: float = 0.1
+    clamp_sigma: float = 2.0
+    demodulate: bool = True
+
+    def c(self, prev_camera: "Camera", cur_samples: float, norm: float = 1.0) -> _ReprojectParams:
+        return _ReprojectParams(prev_camera.c(), float(norm), float(cur_samples), float(self.max_history),
+                                float(self.sigma_normal), float(self.sigma_depth), float(self.min_weight),
+                                float(self.clamp_sigma), int(self.demodulate))
+
+
+HISTORY_CHANNELS = 8  # bdpt_reproject's state per pixel: I_r I_g I_b n N_x N_y N_z z
+
+
+def reproject_numpy(color, aov, hist, dirs, cam_consts_cur, cam_consts_prev, settings=None, norm=1.0, dt=np.float32,
+                    cur_samples=1.0):
+    """What bdpt_reproject computes, as the header states it, every operation in `dt`: color (H, W, 3), aov
+    (H, W, 8), hist (H, W, 8) or None, dirs (H, W, 3) the pixels' primary ray directions at spp 1, the two
+    cameras' 72 constants (camera_constants) -> (out_color (H, W, 3), hist_out (H, W, 8)) in dt. In float32
+    the steps below are the kernel's, operation for operation."""
+    f = dt
+    s = settings or ReprojectSettings()
+    av = np.asarray(aov, np.float32)
+    H, W = av.shape[:2]
+    av = av.reshape(H, W, 8).astype(dt) * f(norm)
+    c = np.asarray(color, np.float32).reshape(H, W, 3).astype(dt) * f(norm)
+    d = np.asarray(dirs, np.float32).reshape(H, W, 3).astype(dt)
+    cc = np.asarray(cam_consts_cur, np.float32).reshape(72).astype(dt)
+    cp = np.asarray(cam_consts_prev, np.float32).reshape(72).astype(dt)
+    n_c, demod, k = f(cur_samples), bool(s.demodulate), f(s.clamp_sigma)
+    one, half, zero = f(1), f(0.5), f(0)
+    with np.errstate(all="ignore"):
+        cov = av[..., 7]
+        hit = cov > 0
+        sc = np.where(hit, cov, one)
+        g = av / sc[..., None]
+        m = np.maximum(g[..., 0:3], f(1e-3))
+        Np, z = g[..., 3:6], g[..., 6]
+        Ic = c / m if demod else c
+
+        has = np.zeros((H, W), bool)
+        Hh = np.zeros((H, W, 3), dt)
+        n_h = np.zeros((H, W), dt)
+        if hist is not None:
+            hs = np.asarray(hist, np.float32).reshape(H, W, 8).astype(dt)
+            eye_c, eye_p = cc[28:31], cp[28:31]  # cameraToWorld's translation
+            X = [eye_c[i] + z * d[..., i] for i in range(3)]
+            w = cp[0:16]  # worldToCamera, column-major: row r is w[r], w[4 + r], w[8 + r], w[12 + r]
+            xc, yc, zc = (((w[r] * X[0] + w[4 + r] * X[1]) + w[8 + r] * X[2]) + w[12 + r] for r in range(3))
+            zc = -zc
+            front = hit & (zc >= one)
+            zs = np.where(front, zc, one)
+            tan = cp[66]
+            u = xc / (zs * (tan * cp[67]))
+            v = yc / (zs * tan)
+
+            def snap(x):
+                r = np.floor(x + half)
+                return np.where(np.abs(x - r) <= f(2.0 ** -10), r, x)
+
+            fx = snap(((u + one) * half) * f(W) - half)
+            fy = snap(((one - v) * half) * f(H) - half)
+            x0f, y0f = np.floor(fx), np.floor(fy)
+            near = front & (x0f >= -one) & (x0f < f(2.0 ** 30)) & (y0f >= -one) & (y0f < f(2.0 ** 30))
+            x0 = np.where(near, x0f, zero).astype(np.int64)
+            y0 = np.where(near, y0f, zero).astype(np.int64)
+            ax, ay = fx - x0f, fy - y0f
+            bx, by = (one - ax, ax), (one - ay, ay)
+            e = [X[i] - eye_p[i] for i in range(3)]
+            zp = np.sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2])
+            ztol = f(s.sigma_depth) * zp
+            sn2 = f(s.sigma_normal) * f(s.sigma_normal)
+            sw = np.zeros((H, W), dt)
+            sn = np.zeros((H, W), dt)
+            sI = np.zeros((H, W, 3), dt)
+            for t in range(4):
+                qx, qy = x0 + (t & 1), y0 + (t >> 1)
+                b = bx[t & 1] * by[t >> 1]
+                ok = near & (b != zero) & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+                hq = hs[np.clip(qy, 0, H - 1), np.clip(qx, 0, W - 1)]
+                ok &= (hq[..., 7] > zero) & (np.abs(hq[..., 7] - zp) <= ztol)
+                dn = Np - hq[..., 4:7]
+                ok &= (dn[..., 0] * dn[..., 0] + dn[..., 1] * dn[..., 1]) + dn[..., 2] * dn[..., 2] <= sn2
+                has |= ok
+                sw = np.where(ok, sw + b, sw)
+                sI = np.where(ok[..., None], sI + b[..., None] * hq[..., 0:3], sI)
+                sn = np.where(ok, sn + b * hq[..., 3], sn)
+            has &= sw >= f(s.min_weight)
+            sws = np.where(has, sw, one)
+            Hh = sI / sws[..., None]
+            n_h = np.minimum(sn / sws, f(s.max_history))
+
+        if k > zero and has.any():
+            pad = np.zeros((H + 2, W + 2), bool)
+            pad[1:-1, 1:-1] = hit
+            Ip = np.zeros((H + 2, W + 2, 3), dt)
+            Ip[1:-1, 1:-1] = Ic
+            S, Q, cnt = np.zeros((H, W, 3), dt), np.zeros((H, W, 3), dt), np.zeros((H, W), dt)
+            for dy in range(3):
+                for dx in range(3):
+                    ok = pad[dy:dy + H, dx:dx + W]
+                    S = np.where(ok[..., None], S + Ip[dy:dy + H, dx:dx + W], S)
+                    cnt = np.where(ok, cnt + one, cnt)
+            cs = np.where(cnt > zero, cnt, one)[..., None]
+            mu = S / cs
+            for dy in range(3):
+                for dx in range(3):
+                    ok = pad[dy:dy + H, dx:dx + W]
+                    dI = Ip[dy:dy + H, dx:dx + W] - mu
+                    Q = np.where(ok[..., None], Q + dI * dI, Q)
+            sd = np.sqrt(Q / cs)
+            lo, hi = mu - sd * k, mu + sd * k
+            Hh = np.where(Hh < lo, lo, np.where(Hh > hi, hi, Hh))
+
+        n_out = n_h + n_c
+        alpha = (n_c / n_out)[..., None]
+        Io = Hh + (Ic - Hh) * alpha
+        blended = Io * m if demod else Io
+        hb = has[..., None]
+        out = np.where(hb, blended, c)
+        state = np.zeros((H, W, 8), dt)
+        state[..., 0:3] = np.where(hit[..., None], np.where(hb, Io, Ic), c)
+        state[..., 3] = np.where(has, n_out, n_c)
+        state[..., 4:7] = np.where(hit[..., None], Np, zero)
+        state[..., 7] = np.where(hit, z, zero)
+    assert out.dtype == dt and state.dtype == dt
+    return out, state
+
+
 def denoise_var_settings() -> "DenoiseSettings":
     """bdpt_denoise_var's defaults: the header's BDPT_DENOISE_VAR_ITERATIONS / _SIGMA_COLOR, the other fields
     DenoiseSettings' own."""
@@ -1962,6 +2107,90 @@ class BDPTIntegrator:
         _check(lib().bdpt_denoise(self._h, self.config.width, self.config.height, ctypes.c_void_p(rgb_ptr),
                                   ctypes.c_void_p(aov_ptr), ctypes.c_void_p(out_ptr), ctypes.byref(d),
                                   ctypes.c_void_p(stream_ptr)))
+
+    def primary_directions(self) -> np.ndarray:
+        """The primary ray direction of every pixel at spp 1 (the pixel centre, no jitter draws), through the
+        frame kernels' own camera function (bdpt_debug_sampling's camera entry): float32 (H, W, 3). What
+        bdpt_reproject forms its world points from, and reproject_numpy's `dirs`."""
+        H, W = self.config.height, self.config.width
+        rec = np.zeros((H * W, 3), np.uint32)
+        rec[:, 0] = np.arange(H * W, dtype=np.uint32)
+        out = np.zeros((H * W, 3), np.uint32)
+        p = self.params()
+        p.spp = 1
+        code = SAMPLING_FNS["camera"][0]
+        _check(lib().bdpt_debug_sampling(self._h, ctypes.byref(p), KAT_BUILDS["exact"], code, EMITTER_PLACEMENTS["ctx"],
+                                         H * W, rec.ctypes.data, out.ctypes.data, None))
+        return out.view(np.float32).reshape(H, W, 3)
+
+    def _reproject_params(self, prev_camera, samples_done, params):
+        settings = params.pop("settings", None) or ReprojectSettings()
+        if params:
+            from dataclasses import replace
+            settings = replace(settings, **params)
+        if samples_done is not None and samples_done < 1:
+            raise ValueError("reproject: samples_done must be >= 1")
+        n_c = self.config.spp if samples_done is None else samples_done
+        return settings.c(prev_camera, n_c, self.config.spp / n_c)
+
+    def reproject(self, prev_camera: Camera, hist=None, rgb=None, aov=None, samples_done: int | None = None, **params):
+        """bdpt_reproject_host: the history `hist` ((H, W, 8), made with prev_camera; None: no history) carried into
+        this integrator's camera and blended with rgb (default self.rgb) under the guides aov (default self.aov) ->
+        (accumulated colour (H, W, 3), new history (H, W, 8)), both new arrays. samples_done: the samples per pixel
+        rgb and aov hold (None = the full spp; norm = spp / samples_done). params: ReprojectSettings fields, or
+        settings=ReprojectSettings(...)."""
+        H, W = self.config.height, self.config.width
+        r = self._reproject_params(prev_camera, samples_done, params)
+        c = np.ascontiguousarray(self.rgb if rgb is None else rgb, np.float32)
+        a = np.ascontiguousarray(self.aov if aov is None else aov, np.float32)
+        h = None if hist is None else np.ascontiguousarray(hist, np.float32)
+        if c.size != W * H * 3 or a.size != W * H * 8 or (h is not None and h.size != W * H * 8):
+            raise BdptError(f"reproject: rgb / aov / hist have {c.size} / {a.size} / {None if h is None else h.size} "
+                            f"floats, expected {W * H * 3} / {W * H * 8} / {W * H * 8}")
+        out, state = np.zeros((H, W, 3), np.float32), np.zeros((H, W, HISTORY_CHANNELS), np.float32)
+        p = self.params()
+        _check(lib().bdpt_reproject_host(self._h, ctypes.byref(p), c.ctypes.data, a.ctypes.data,
+                                         None if h is None else h.ctypes.data, out.ctypes.data, state.ctypes.data,
+                                         ctypes.byref(r)))
+        return out, state
+
+    def reproject_device(self, prev_camera: Camera, rgb_ptr: int, aov_ptr: int, hist_in_ptr: int, out_ptr: int,
+                         hist_out_ptr: int, stream_ptr: int = 0, cur_samples: float | None = None, norm: float = 1.0,
+                         settings: "ReprojectSettings | None" = None) -> None:
+        """bdpt_reproject: asynchronous, on device buffers; hist_in_ptr 0 = no history."""
+        r = (settings or ReprojectSettings()).c(prev_camera, self.config.spp if cur_samples is None else cur_samples, norm)
+        p = self.params()
+        _check(lib().bdpt_reproject(self._h, ctypes.byref(p), ctypes.c_void_p(rgb_ptr), ctypes.c_void_p(aov_ptr),
+                                    ctypes.c_void_p(hist_in_ptr or None), ctypes.c_void_p(out_ptr),
+                                    ctypes.c_void_p(hist_out_ptr), ctypes.byref(r), ctypes.c_void_p(stream_ptr)))
+
+    def render_sequence(self, cameras, spp_per_frame: int | None = None, denoise: bool = False, **params):
+        """Generator: one accumulated frame per camera of `cameras`. Frame f renders spp_per_frame samples
+        (default the configured spp) and the feature buffers at cameras[f], with the seed base moved on by
+        f * width * height * spp so that no two frames repeat a sample, and carries the history of frame f - 1
+        into it with reproject (params: ReprojectSettings fields or settings=). Yields the accumulated (H, W, 3)
+        frame; with denoise, (accumulated, bdpt_denoise of it at norm 1 under the frame's own guides). The
+        configured camera, spp and seed base are put back when the generator ends."""
+        cfg = self.config
+        saved = (cfg.camera, cfg.spp, cfg.seed_base)
+        spp = cfg.spp if spp_per_frame is None else int(spp_per_frame)
+        settings = params.pop("settings", None) or ReprojectSettings()
+        if params:
+            from dataclasses import replace
+            settings = replace(settings, **params)
+        try:
+            hist, prev = None, None
+            for f, cam in enumerate(cameras):
+                cfg.camera, cfg.spp = cam, spp
+                cfg.seed_base = (saved[2] + f * cfg.width * cfg.height * spp) & 0xFFFFFFFF
+                self.init()
+                self.render_frame()
+                self.render_aov()
+                out, hist = self.reproject(cam if prev is None else prev, hist, settings=settings)
+                prev = cam
+                yield (out, self.denoise(out)) if denoise else out
+        finally:
+            cfg.camera, cfg.spp, cfg.seed_base = saved
 
     def denoise_var(self, rgb=None, var=None, aov=None, samples_done: int | None = None, return_variance: bool = False,
                     **params):

@@ -91,6 +91,11 @@ hipError_t launch_adaptive_select(const float* S, const float* var, int W, int H
                                   int dilate, int32_t* m, int32_t* list, int32_t* count, void* scratch, hipStream_t st);
 hipError_t launch_adaptive_start(size_t pixels, int step, int32_t* m, int32_t* list, hipStream_t st);
 hipError_t launch_adaptive_samples(size_t pixels, int K, const int32_t* m, int32_t* samples, hipStream_t st);
+// temporal_kernels.hip: temporal accumulation (bdpt_reproject)
+hipError_t launch_reproject(const dev::DevFrame& fr, const CameraConstants& prev, float norm, float n_c, float max_history,
+                            float sigma_normal, float sigma_depth, float min_weight, float clamp_sigma, int demodulate,
+                            const float* color, const float* aov, const float* hist_in, float* out, float* hist_out,
+                            hipStream_t st);
 hipError_t launch_denoise_var_prepare(int W, int H, const float* color, const float* var, const float* aov, float norm,
                                       int demodulate, void* guide, void* img, hipStream_t st);
 hipError_t launch_denoise_var_blur(int W, int H, const void* src, void* dst, float* out_var, hipStream_t st);
@@ -2813,6 +2818,78 @@ int bdpt_adaptive_pass_lists(bdpt_ctx* c, int32_t* out, int64_t capacity, int64_
     if (!out) return BDPT_OK;
     if (capacity < *total) return fail(BDPT_ERR_INVALID, "bdpt_adaptive_pass_lists: capacity is below the lists' length");
     std::copy(c->ad_pass_lists.begin(), c->ad_pass_lists.end(), out);
+    return BDPT_OK;
+}
+
+// ---------------------------------------------------------------- temporal accumulation
+static int check_reproject(const bdpt_frame_params* p, const float* color, const float* aov, const float* hist_in,
+                           const float* out, const float* hist_out, const bdpt_reproject_params* r) {
+    const std::string entry = "bdpt_reproject: ";
+    if (!p) return fail(BDPT_ERR_INVALID, entry + "null frame params");
+    if (!r) return fail(BDPT_ERR_INVALID, entry + "null reproject params");
+    if (p->width <= 0 || p->height <= 0) return fail(BDPT_ERR_INVALID, entry + "width/height must be > 0");
+    const uint64_t px = static_cast<uint64_t>(p->width) * static_cast<uint64_t>(p->height);
+    if (px >= (1ull << 28)) return fail(BDPT_ERR_INVALID, entry + "width * height must be below 2^28");
+    auto positive = [](float v) { return v > 0.f && std::isfinite(v); };
+    if (!positive(r->norm)) return fail(BDPT_ERR_INVALID, entry + "norm must be > 0");
+    if (!positive(r->cur_samples)) return fail(BDPT_ERR_INVALID, entry + "cur_samples must be > 0");
+    if (!positive(r->max_history)) return fail(BDPT_ERR_INVALID, entry + "max_history must be > 0");
+    if (!positive(r->sigma_normal)) return fail(BDPT_ERR_INVALID, entry + "sigma_normal must be > 0");
+    if (!positive(r->sigma_depth)) return fail(BDPT_ERR_INVALID, entry + "sigma_depth must be > 0");
+    if (!(r->min_weight > 0.f && r->min_weight <= 1.f)) return fail(BDPT_ERR_INVALID, entry + "min_weight must be in (0, 1]");
+    if (!(r->clamp_sigma >= 0.f) || !std::isfinite(r->clamp_sigma)) return fail(BDPT_ERR_INVALID, entry + "clamp_sigma must be >= 0");
+    if (r->demodulate != 0 && r->demodulate != 1) return fail(BDPT_ERR_INVALID, entry + "demodulate must be 0 or 1");
+    if (!color) return fail(BDPT_ERR_INVALID, entry + "color must not be NULL");
+    if (!aov) return fail(BDPT_ERR_INVALID, entry + "aov must not be NULL");
+    if (!out) return fail(BDPT_ERR_INVALID, entry + "out_color must not be NULL");
+    if (!hist_out) return fail(BDPT_ERR_INVALID, entry + "hist_out must not be NULL");
+    const FloatSpan in[] = {{"color", color, px * 3}, {"aov", aov, px * 8}, {"hist_in", hist_in, px * 8}};
+    const FloatSpan outs[] = {{"out_color", out, px * 3}, {"hist_out", hist_out, px * 8}};
+    for (const FloatSpan& o : outs)
+        for (const FloatSpan& i : in)
+            if (spans_overlap(o, i)) return fail(BDPT_ERR_INVALID, entry + o.name + " overlaps " + i.name);
+    if (spans_overlap(outs[1], outs[0])) return fail(BDPT_ERR_INVALID, entry + "hist_out overlaps out_color");
+    return BDPT_OK;
+}
+
+int bdpt_reproject(bdpt_ctx* c, const bdpt_frame_params* p, const float* color, const float* aov, const float* hist_in,
+                   float* out, float* hist_out, const bdpt_reproject_params* r, void* hip_stream) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_reproject(p, color, aov, hist_in, out, hist_out, r);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    // the current camera's frame as camera_dir reads it: camera, size, and spp 1 (the pixel centre, no draws)
+    dev::DevFrame fr{};
+    camera_constants(p->camera.eye, p->camera.at, p->camera.up, p->camera.fov, p->width, p->height, fr.cam);
+    fr.W = p->width, fr.H = p->height, fr.spp = 1;
+    CameraConstants prev;
+    const bdpt_camera& pc = r->prev_camera;
+    camera_constants(pc.eye, pc.at, pc.up, pc.fov, p->width, p->height, prev);
+    if ((rc = begin_use(c, st))) return rc;
+    if ((rc = begin_timed(c, st))) return rc;
+    HIP_TRY(launch_reproject(fr, prev, r->norm, r->cur_samples, r->max_history, r->sigma_normal, r->sigma_depth,
+                             r->min_weight, r->clamp_sigma, r->demodulate, color, aov, hist_in, out, hist_out, st));
+    return end_timed(c, st, 0, 1);
+}
+
+int bdpt_reproject_host(bdpt_ctx* c, const bdpt_frame_params* p, const float* color, const float* aov,
+                        const float* hist_in, float* out, float* hist_out, const bdpt_reproject_params* r) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_reproject(p, color, aov, hist_in, out, hist_out, r);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t px = static_cast<size_t>(p->width) * p->height;
+    HIP_TRY(c->tmp_fb.reserve(px * 30 * sizeof(float)));
+    // aov, hist_in, hist_out (each a multiple of 32 bytes from the 16-byte aligned start), color, out_color
+    float *da = c->tmp_fb, *dhi = da + px * 8, *dho = da + px * 16, *dc = da + px * 24, *dout = da + px * 27;
+    HIP_TRY(hipMemcpyAsync(da, aov, px * 8 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dc, color, px * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (hist_in) HIP_TRY(hipMemcpyAsync(dhi, hist_in, px * 8 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((rc = bdpt_reproject(c, p, dc, da, hist_in ? dhi : nullptr, dout, dho, r, c->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout, px * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hist_out, dho, px * 8 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return BDPT_OK;
 }
 

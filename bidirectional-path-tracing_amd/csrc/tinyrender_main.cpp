@@ -65,12 +65,25 @@
 // deviation across the batches exceeds THR. Writes the frame, <out>_variance.exr (its per-pixel variance)
 // and <out>_samples.exr (the samples each pixel had, as a grey value). Refused, the flag named, with --gpus /
 // --devices, --layers, --light-groups, --strategies, --batches, --cross, --denoise-planes and --sample-window.
+// --cameras FILE --temporal[=MAXHIST] (a bdpt scene, one device) renders a camera sequence with temporal accumulation
+// (bdpt_reproject_host, the header's BDPT_REPROJECT_* defaults, MAXHIST > 0 in place of its history cap). FILE has one
+// line per frame, ex ey ez ax ay az ux uy uz fov (eye, at, up, fov in degrees); blank lines and lines starting
+// with # are skipped. Frame f is rendered at the TOML's spp from camera f, its seed base moved on by f * width *
+// height * spp so that no two frames repeat a sample, and blended with the history of frame f - 1: <out
+// stem>.f<nn>.exr is the accumulated frame (frame 0: the plain render of camera 0), and with --denoise <out
+// stem>.f<nn>_denoised.exr the filter of the accumulated frame under that frame's feature buffers, norm 1. The TOML's
+// own camera is not rendered and <out> itself is not written. Refused, the flag named, before any device is
+// used: one flag without the other, an unreadable or malformed FILE, a path / direct scene, and --gpus /
+// --devices, --layers, --light-groups, --strategies, --cross, --denoise-planes, --batches, --denoise-var,
+// --adaptive, --sample-window and --aov.
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -114,13 +127,49 @@ std::string side_path(const std::string& exr, const char* suffix) {
     return (ext ? exr.substr(0, exr.size() - 4) : exr) + suffix + ".exr";
 }
 
+// --cameras FILE: ten numbers per line (eye, at, up, fov); blank lines and # lines skipped. false with a message.
+bool parse_cameras(const std::string& file, std::vector<bdpt_camera>* out, std::string* error) {
+    std::ifstream in(file);
+    if (!in) {
+        *error = "cannot read the file";
+        return false;
+    }
+    std::string line;
+    for (int n = 1; std::getline(in, line); n++) {
+        const size_t first = line.find_first_not_of(" \t\r");
+        if (first == std::string::npos || line[first] == '#') continue;
+        std::istringstream fields(line);
+        float v[10];
+        int got = 0;
+        while (got < 10 && fields >> v[got]) got++;
+        std::string rest;
+        if (got < 10 || (fields >> rest)) {  // too few, not a number, or something after the tenth
+            *error = "line " + std::to_string(n) + ": expected ten numbers (ex ey ez ax ay az ux uy uz fov)";
+            return false;
+        }
+        bdpt_camera c;
+        for (int k = 0; k < 3; k++) c.eye[k] = v[k], c.at[k] = v[3 + k], c.up[k] = v[6 + k];
+        c.fov = v[9];
+        if (!(c.fov > 0.f && c.fov < 180.f)) {
+            *error = "line " + std::to_string(n) + ": fov must be in (0, 180) degrees";
+            return false;
+        }
+        out->push_back(c);
+    }
+    if (out->empty()) {
+        *error = "no camera line";
+        return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Syntax: %s <scene.toml> [nogui] [--width W --height H --spp N --rr D --device K "
                              "--out FILE.exr --seed S --gpus N --devices a,b,... --shard samples|rows "
-                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted] --cross --denoise-planes[=own|shared] --batches K --denoise-var[=ITER] --adaptive THR[:K[:STEP[:PASSES]]]]\n", argv[0]);
+                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted] --cross --denoise-planes[=own|shared] --batches K --denoise-var[=ITER] --adaptive THR[:K[:STEP[:PASSES]]] --cameras FILE --temporal[=MAXHIST]]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string toml = argv[1];
@@ -143,6 +192,10 @@ int main(int argc, char** argv) {
     bdpt_adaptive_params ad = {8, 1, 0, 0.f, 1e-3f, 1, 0};  // (max_passes 0: spp / (step * n_batches))
     bool want_denoise_var = false;  // --denoise-var[=ITER]
     int denoise_var_iterations = BDPT_DENOISE_VAR_ITERATIONS;
+    bool temporal = false;          // --temporal[=MAXHIST]
+    float temporal_max_history = BDPT_REPROJECT_MAX_HISTORY;
+    std::string cameras_file;       // --cameras FILE
+    std::vector<bdpt_camera> cameras;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -237,6 +290,22 @@ int main(int argc, char** argv) {
             }
             adaptive = true;
             ad.n_batches = static_cast<int32_t>(f[0]), ad.step = static_cast<int32_t>(f[1]), ad.max_passes = static_cast<int32_t>(f[2]);
+        } else if (a == "--cameras") {
+            cameras_file = next("--cameras");
+        } else if (a == "--temporal") {
+            temporal = true;
+        } else if (a.compare(0, 11, "--temporal=") == 0) {
+            const char* v = argv[i] + 11;
+            char* end = nullptr;
+            temporal_max_history = std::strtof(v, &end);
+            if (end == v || *end != '\0' || !(temporal_max_history > 0.f) || !(temporal_max_history < 1e30f)) {
+                std::fprintf(stderr, "--temporal=%s: the history cap must be a number > 0\n", v);
+                return EXIT_FAILURE;
+            }
+            temporal = true;
+        } else if (a.rfind("--temporal", 0) == 0) {
+            std::fprintf(stderr, "%s: --temporal takes no value or =MAXHIST\n", a.c_str());
+            return EXIT_FAILURE;
         } else if (a == "--denoise-planes" || a == "--denoise-planes=shared") {
             denoise_planes = BDPT_DENOISE_PLANES_SHARED;
         } else if (a == "--denoise-planes=own") {
@@ -323,6 +392,26 @@ int main(int argc, char** argv) {
             return EXIT_FAILURE;
         }
     }
+    if (temporal != !cameras_file.empty()) {
+        std::fprintf(stderr, temporal ? "--temporal accumulates over a camera sequence: give --cameras FILE\n"
+                                      : "--cameras is the sequence --temporal[=MAXHIST] renders: give that flag\n");
+        return EXIT_FAILURE;
+    }
+    if (temporal) {
+        const char* with = !devices.empty() ? "--gpus / --devices" : layers ? "--layers" : light_groups ? "--light-groups"
+                           : strategies >= 0 ? "--strategies" : cross ? "--cross" : denoise_planes >= 0 ? "--denoise-planes"
+                           : batches ? "--batches" : want_denoise_var ? "--denoise-var" : adaptive ? "--adaptive"
+                           : windowed ? "--sample-window" : want_aov ? "--aov" : nullptr;
+        if (with) {
+            std::fprintf(stderr, "--temporal renders whole frames of a camera sequence on one device: not with %s\n", with);
+            return EXIT_FAILURE;
+        }
+        std::string error;
+        if (!parse_cameras(cameras_file, &cameras, &error)) {
+            std::fprintf(stderr, "--cameras %s: %s\n", cameras_file.c_str(), error.c_str());
+            return EXIT_FAILURE;
+        }
+    }
     if (shard_given && devices.empty()) {
         std::fprintf(stderr, "--shard applies to a multi-device render (--gpus N / --devices a,b,...)\n");
         return EXIT_FAILURE;
@@ -359,6 +448,11 @@ int main(int argc, char** argv) {
     }
     if (strategies >= 0 && (path || direct)) {
         std::fprintf(stderr, "--strategies splits a bdpt frame (integrator type \"%s\" has no (s, t) strategies)\n",
+                     cfg.integrator);
+        return EXIT_FAILURE;
+    }
+    if (temporal && (path || direct)) {
+        std::fprintf(stderr, "--temporal accumulates a bdpt frame sequence (integrator type \"%s\" has no sequence loop)\n",
                      cfg.integrator);
         return EXIT_FAILURE;
     }
@@ -432,6 +526,47 @@ int main(int argc, char** argv) {
     p.row_offset = 0;
     p.row_stride = 1;
     std::vector<float> rgb(static_cast<size_t>(cfg.width) * cfg.height * 3, 0.f);  // Integrator::init: rgb->clear()
+
+    if (temporal) {  // the camera sequence: render, feature buffers, reproject, per frame
+        const std::string exr = out.empty() ? exr_path_of(toml) : out;
+        const size_t px = static_cast<size_t>(cfg.width) * cfg.height;
+        std::vector<float> aov(px * 8), acc(px * 3), den(px * 3), hist[2] = {std::vector<float>(px * 8), std::vector<float>(px * 8)};
+        const uint32_t seed0 = p.seed_base;
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        for (size_t f = 0; f < cameras.size(); f++) {
+            p.camera = cameras[f];
+            p.seed_base = seed0 + static_cast<uint32_t>(f * px * static_cast<size_t>(cfg.spp));
+            std::fill(rgb.begin(), rgb.end(), 0.f);
+            std::fill(aov.begin(), aov.end(), 0.f);
+            if (bdpt_render_window_host(ctx, &p, nullptr, nullptr, nullptr, rgb.data()) != BDPT_OK) return die("render (bdpt)");
+            if (bdpt_render_aov_host(ctx, &p, nullptr, aov.data()) != BDPT_OK) return die("bdpt_render_aov_host");
+            const bdpt_reproject_params r = {cameras[f ? f - 1 : 0], 1.f, static_cast<float>(cfg.spp), temporal_max_history,
+                                             BDPT_REPROJECT_SIGMA_NORMAL, BDPT_REPROJECT_SIGMA_DEPTH, BDPT_REPROJECT_MIN_WEIGHT,
+                                             BDPT_REPROJECT_CLAMP_SIGMA, BDPT_REPROJECT_DEMODULATE};
+            if (bdpt_reproject_host(ctx, &p, rgb.data(), aov.data(), f ? hist[(f - 1) & 1].data() : nullptr, acc.data(),
+                                    hist[f & 1].data(), &r) != BDPT_OK)
+                return die("bdpt_reproject_host");
+            char suffix[32];
+            std::snprintf(suffix, sizeof suffix, ".f%02d", static_cast<int>(f));
+            const std::string frame = side_path(exr, suffix);
+            if (bdpt_save_exr(acc.data(), cfg.width, cfg.height, frame.c_str()) != BDPT_OK) return die("saveEXR");
+            std::printf("Saved EXR image to %s\n", frame.c_str());
+            if (want_denoise) {
+                const bdpt_denoise_params d = {denoise_iterations, BDPT_DENOISE_SIGMA_COLOR, BDPT_DENOISE_SIGMA_NORMAL,
+                                               BDPT_DENOISE_SIGMA_DEPTH, BDPT_DENOISE_DEMODULATE, 1.f};
+                if (bdpt_denoise_host(ctx, cfg.width, cfg.height, acc.data(), aov.data(), den.data(), &d) != BDPT_OK)
+                    return die("bdpt_denoise_host");
+                const std::string side = side_path(exr, (std::string(suffix) + "_denoised").c_str());
+                if (bdpt_save_exr(den.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
+                std::printf("Saved EXR image to %s\n", side.c_str());
+            }
+        }
+        const auto t1 = std::chrono::high_resolution_clock::now();
+        std::printf("Render took: %g seconds.\n", std::chrono::duration<double>(t1 - t0).count());
+        bdpt_ctx_destroy(ctx);
+        bdpt_scene_free(scene);
+        return EXIT_SUCCESS;
+    }
 
     const bdpt_sample_window* const win = windowed ? &window : nullptr;  // null: every sample
     // --batches: the K planes (plane b: the window's samples b, b + K, ...), then their sum in rgb and its variance

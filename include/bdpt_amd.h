@@ -48,6 +48,7 @@
  *   bdpt_denoise_var         (no counterpart) the filter with its colour weight in standard deviations
  *   bdpt_render_pixels       (no counterpart) a sample window of the BDPT frame for a list of pixels
  *   bdpt_render_adaptive     (no counterpart) further samples only where the batch variance asks
+ *   bdpt_reproject           (no counterpart) a preview's history reprojected into the next camera's frame
  *
  * Conventions: plain C types only; status 0 = OK, < 0 = error (message from
  * bdpt_last_error(), thread-local). A context is bound to one HIP device and is
@@ -884,6 +885,89 @@ int bdpt_render_adaptive_host(bdpt_ctx* ctx, const bdpt_frame_params* params, co
  * stats.active[j] entries). *total receives their length; out (NULL: only the length is wanted) must
  * hold `capacity` >= *total entries (BDPT_ERR_INVALID otherwise). */
 int bdpt_adaptive_pass_lists(bdpt_ctx* ctx, int32_t* out, int64_t capacity, int64_t* total);
+
+/* ---- temporal accumulation: the preview's history reprojected across camera moves ---- */
+/* (new) Not in the reference. Takes the history carried from the previous camera, the current frame's
+ * colour and feature buffers (bdpt_render_aov of the same camera and samples) and the two cameras; gives
+ * the accumulated frame and the new history. Scenes are static: a pixel's first hit is looked up where the
+ * previous camera saw it. Integrator-agnostic: any colour + aov pair of `cur`'s camera and size.
+ *
+ * History state: hist is width * height * 8 floats, interleaved per pixel, [I_r, I_g, I_b, n, N_x, N_y, N_z,
+ * z]: I the accumulated colour in the filter's domain (demodulated when `demodulate` is set), n the sample
+ * count behind it, N and z the pixel's first-hit normal and depth, z = 0 marking a miss. Two 16-byte vectors
+ * per pixel; documented, not opaque: a caller may save and reload it. A history is only meaningful with the
+ * `demodulate` it was made with.
+ *
+ * With c = color * norm and a = aov * norm, the guides cov, alb, N, z and m = max(alb, 1e-3) exactly as
+ * bdpt_denoise forms them, and I_cur = demodulate ? c / m : c. Float32, every operation rounded on its own
+ * (no fma), only + - * /, sqrt, floor, min / max and comparisons; no atomics: two runs give the same bits.
+ * Per pixel p = (row i, column j) of the current frame:
+ *  1. Miss (cov <= 0): out_color = c, hist_out = [c, n_c, 0, 0, 0, 0].
+ *  2. World point X = eye_cur + z * d_p, each component one product then one sum. d_p is the primary ray
+ *     direction the frame kernels build for pixel p at spp = 1 (the pixel centre, no jitter draws: the device
+ *     function BDPT_SAMPLING_CAMERA pins). eye_cur, eye_prev: the translation of the camera's cameraToWorld
+ *     (floats 28..30 of bdpt_camera_constants), so the constants alone state the operation.
+ *  3. Into the previous camera, with bdpt_camera_constants(prev_camera, width, height): Xc = worldToCamera_prev
+ *     (X, 1), each component ((m0 x + m1 y) + m2 z) + m3 along a matrix row. No history unless -Xc.z >= 1 (the
+ *     near plane of the primary rays). u = Xc.x / (-Xc.z * (tan_prev * aspect_prev)), v = Xc.y / (-Xc.z *
+ *     tan_prev), fx = ((u + 1) * 0.5) * width - 0.5, fy = ((1 - v) * 0.5) * height - 0.5 (the inverse of the
+ *     camera-ray formula). Snap: r = floor(fx + 0.5); if |fx - r| <= 2^-10 then fx = r; the same for fy - a
+ *     static camera lands on its own pixel, and history degenerates to plain progressive accumulation.
+ *  4. Taps: x0 = floor(fx), ax = fx - x0, likewise y; the bilinear taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1),
+ *     (x0 + 1, y0 + 1) with weights b = (1 - ax)(1 - ay), ax (1 - ay), (1 - ax) ay, ax ay; a tap with b == 0 is
+ *     skipped. zp = sqrt(|X - eye_prev|^2), the square as (dx dx + dy dy) + dz dz. Tap q is accepted iff it is
+ *     inside the image, hist_in[q].z > 0, |hist_in[q].z - zp| <= sigma_depth * zp and |N_p - N_q|^2 <=
+ *     sigma_normal * sigma_normal. sw = sum of b over the accepted taps in tap order, starting from 0. No
+ *     history if hist_in is NULL, no tap is accepted or sw < min_weight.
+ *  5. H = (sum b I_q) / sw per channel, n_h = min((sum b n_q) / sw, max_history), sums in tap order from 0.
+ *  6. Clamp (clamp_sigma = k > 0 only): over the in-image 3 x 3 neighbours q of p in the current frame with
+ *     cov_q > 0 (p itself counts), dy outer and dx inner: mu = (sum I_cur(q)) / cnt, s2 = (sum (I_cur(q) -
+ *     mu)^2) / cnt per channel, sums from 0, sd = sqrt(s2); lo = mu - sd k, hi = mu + sd k;
+ *     H = H < lo ? lo : (H > hi ? hi : H). n_h is unchanged.
+ *  7. Blend: n_out = n_h + n_c, alpha = n_c / n_out, I_out = H + (I_cur - H) * alpha.
+ *  8. out_color = demodulate ? I_out * m : I_out, hist_out = [I_out, n_out, N, z].
+ *  A covered pixel without history: out_color = c (the frame's own bits, not (c / m) * m) and hist_out =
+ *  [I_cur, n_c, N, z]. So with hist_in NULL, or with a static camera and clamp_sigma 0, the result is the
+ *  plain estimator; choosing history by the current estimate (acceptance, clamp) otherwise biases the frame.
+ *
+ * First-hit reprojection is wrong for what is seen through a mirror or through glass and for caustics that
+ * move with the view; only the clamp limits that.
+ * BDPT_ERR_INVALID, the field named in the message: a bad field (below); a NULL color, aov, out_color or
+ * hist_out; width * height >= 2^28; an output overlapping an input or the other output - so hist_in ==
+ * hist_out is refused: callers ping-pong two buffers. Of `cur`, camera, width and height are read. No
+ * scratch allocation. bdpt_get_stats afterwards: kernel_ms and launches (1) of this call. Asynchronous on
+ * `hip_stream`; the host form stages the buffers and is synchronous. The buffers' 16-byte accesses need
+ * aov, hist_in and hist_out 16-byte aligned (any allocation is); otherwise dwords are used, same bits. */
+typedef struct {
+    bdpt_camera prev_camera;   /* the camera the history was made with */
+    float norm;                /* multiplies color and aov on load, as bdpt_denoise_params.norm; > 0 */
+    float cur_samples;         /* n_c: samples per pixel behind color * norm; > 0 */
+    float max_history;         /* cap on the carried sample count n_h; > 0 */
+    float sigma_normal, sigma_depth;  /* tap acceptance, each > 0 */
+    float min_weight;          /* least sum of accepted bilinear weights, in (0, 1] */
+    float clamp_sigma;         /* k >= 0; 0 = no neighbourhood clamp */
+    int32_t demodulate;        /* 0 / 1, as bdpt_denoise */
+} bdpt_reproject_params;
+/* Defaults. The sigmas are the denoiser's. MAX_HISTORY, MIN_WEIGHT and CLAMP_SIGMA were chosen on the
+ * rendered pair of tests/test_gpu_temporal.py (HardLight 40 x 28 at 4 spp, the camera moved sideways by 2 % of
+ * the eye-at distance) against camera B's 256-spp frame and on nothing else: a grid over min_weight 0.1 .. 0.75,
+ * clamp_sigma 0 .. 3 and both demodulate (mean squared error over the frame 0.000670 against the 4-spp frame's
+ * 0.001791; clamp_sigma 0 and 3 score within 0.3 % of 2). One move cannot tell history caps of 4 and more
+ * apart, so the cap comes from the same end frame reached in seven moves of 2/7 % (caps 4 .. 64: 16 scores
+ * best, 0.000235 against 0.000254 for 32). The whole grid is in DESIGN.md §7k. A recorded choice, not an
+ * acceptance number. */
+#define BDPT_REPROJECT_SIGMA_NORMAL 0.3f
+#define BDPT_REPROJECT_SIGMA_DEPTH 0.02f
+#define BDPT_REPROJECT_MAX_HISTORY 16.0f
+#define BDPT_REPROJECT_MIN_WEIGHT 0.1f
+#define BDPT_REPROJECT_CLAMP_SIGMA 2.0f
+#define BDPT_REPROJECT_DEMODULATE 1
+int bdpt_reproject(bdpt_ctx* ctx, const bdpt_frame_params* cur, const float* color_device, const float* aov_device,
+                   const float* hist_in_device /* NULL: no history */, float* out_color_device, float* hist_out_device,
+                   const bdpt_reproject_params* params, void* hip_stream);
+int bdpt_reproject_host(bdpt_ctx* ctx, const bdpt_frame_params* cur, const float* color_host, const float* aov_host,
+                        const float* hist_in_host, float* out_color_host, float* hist_out_host,
+                        const bdpt_reproject_params* params);
 
 /* ---- several HIP devices in one process ---- */
 /* The reference fans the offline loop out over host threads (parallel_for,
