@@ -250,9 +250,20 @@ class _ReprojectParams(ctypes.Structure):  # bdpt_reproject_params
                 ("min_weight", ctypes.c_float), ("clamp_sigma", ctypes.c_float), ("demodulate", ctypes.c_int32)]
 
 
+class _MeterParams(ctypes.Structure):  # bdpt_meter_params
+    _fields_ = [("norm", ctypes.c_float), ("key", ctypes.c_float), ("key_permille", ctypes.c_int32),
+                ("white_permille", ctypes.c_int32), ("rate", ctypes.c_float), ("fallback_exposure", ctypes.c_float),
+                ("fallback_white", ctypes.c_float)]
+
+
+class _DisplayParams(ctypes.Structure):  # bdpt_display_params
+    _fields_ = [("norm", ctypes.c_float), ("exposure", ctypes.c_float), ("white", ctypes.c_float),
+                ("tone", ctypes.c_int32), ("encode", ctypes.c_int32), ("channels", ctypes.c_int32)]
+
+
 # Sources that make up the frame kernels' code objects: their hash stamps the
 # profiles (PMC passes) so bench.py only reuses a measurement of the same kernel.
-KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_kernels_layers.hip", "csrc/bdpt_kernels_groups.hip", "csrc/bdpt_kernels_strat.hip", "csrc/bdpt_kernels_strat_unweighted.hip", "csrc/bdpt_kernels_pixels.hip", "csrc/adaptive_kernels.hip", "csrc/temporal_kernels.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
+KERNEL_SOURCES = ("csrc/bdpt_kernels.hip", "csrc/aov_kernels.hip", "csrc/bdpt_kernels_split.hip", "csrc/bdpt_kernels_ng.hip", "csrc/bdpt_kernels_layers.hip", "csrc/bdpt_kernels_groups.hip", "csrc/bdpt_kernels_strat.hip", "csrc/bdpt_kernels_strat_unweighted.hip", "csrc/bdpt_kernels_pixels.hip", "csrc/adaptive_kernels.hip", "csrc/temporal_kernels.hip", "csrc/display_kernels.hip", "csrc/bdpt_path.hpp", "csrc/bdpt_device.hpp", "csrc/device_math.hpp",
                   "csrc/dev_scene.hpp", "csrc/dev_rng.hpp", "csrc/dev_warp.hpp", "csrc/dev_traverse.hpp", "csrc/dev_shade.hpp", "csrc/dev_emitter.hpp",
                   "csrc/powf_restated.inc", "csrc/bdpt_types.h", "Makefile")
 
@@ -370,6 +381,15 @@ def lib():
                                      ctypes.POINTER(_ReprojectParams), vp]
         L.bdpt_reproject_host.argtypes = [vp, ctypes.POINTER(_FrameParams), vp, vp, vp, vp, vp,
                                           ctypes.POINTER(_ReprojectParams)]
+        L.bdpt_display_thresholds.argtypes = [i32, vp]
+        L.bdpt_meter.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.POINTER(_MeterParams), vp, vp]
+        L.bdpt_meter_host.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.POINTER(_MeterParams), vp]
+        L.bdpt_debug_meter_histogram.argtypes = [vp, vp]
+        L.bdpt_display.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(_DisplayParams), vp, vp]
+        L.bdpt_display_host.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(_DisplayParams), vp]
+        L.bdpt_encode_png.argtypes = [vp, i32, i32, i32, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+        L.bdpt_save_png.argtypes = [vp, i32, i32, i32, ctypes.c_char_p]
+        L.bdpt_save_ppm.argtypes = [vp, i32, i32, ctypes.c_char_p]
         L.bdpt_denoise_var.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(_DenoiseParams), vp]
         L.bdpt_denoise_var_host.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(_DenoiseParams)]
         L.bdpt_render_layers.argtypes = [vp, ctypes.POINTER(_FrameParams), ctypes.POINTER(_SampleWindow), i32, vp, vp]
@@ -1325,6 +1345,159 @@ def reproject_numpy(color, aov, hist, dirs, cam_consts_cur, cam_consts_prev, set
     return out, state
 
 
+TONES = {"clamp": 0, "reinhard": 1, "filmic": 2}      # BDPT_TONE_*
+ENCODES = {"srgb": 0, "gamma22": 1, "linear": 2}     # BDPT_ENCODE_*
+METER_BINS = 4096  # BDPT_METER_BINS
+
+
+def _code_of(table, value, what):
+    if isinstance(value, str):
+        if value not in table:
+            raise ValueError(f"{what} must be one of {sorted(table)}, not {value!r}")
+        return table[value]
+    return int(value)  # (the library refuses an unknown code)
+
+
+@dataclass
+class MeterSettings:
+    """bdpt_meter_params with the header's defaults (BDPT_METER_*); norm is set per call."""
+    key: float = 0.18
+    key_permille: int = 500
+    white_permille: int = 990
+    rate: float = 0.25
+    fallback_exposure: float = 1.0
+    fallback_white: float = 1.0
+
+    def c(self, norm: float = 1.0) -> _MeterParams:
+        return _MeterParams(float(norm), float(self.key), int(self.key_permille), int(self.white_permille),
+                            float(self.rate), float(self.fallback_exposure), float(self.fallback_white))
+
+
+@dataclass
+class DisplaySettings:
+    """bdpt_display_params; tone and encode by name (TONES, ENCODES) or code; norm is set per call. exposure and
+    white are what a call without meter words uses."""
+    exposure: float = 1.0
+    white: float = 1.0
+    tone: "str | int" = "reinhard"
+    encode: "str | int" = "srgb"
+    channels: int = 3
+
+    def c(self, norm: float = 1.0) -> _DisplayParams:
+        return _DisplayParams(float(norm), float(self.exposure), float(self.white), _code_of(TONES, self.tone, "tone"),
+                              _code_of(ENCODES, self.encode, "encode"), int(self.channels))
+
+
+def display_thresholds(encode="srgb") -> np.ndarray:
+    """bdpt_display_thresholds: the 255 float32 places where the 8-bit code of `encode` steps (no device)."""
+    out = np.zeros(255, np.float32)
+    _check(lib().bdpt_display_thresholds(_code_of(ENCODES, encode, "encode"), out.ctypes.data))
+    return out
+
+
+def meter_histogram_numpy(color, aov=None, norm=1.0) -> np.ndarray:
+    """The 4096 bin counts bdpt_meter forms (uint32), float32 as the kernel: bin = bits(Y) >> 19 of the
+    covered pixels whose Y is a positive normal finite float."""
+    f = np.float32
+    c = np.asarray(color, f).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        c = c * f(norm)
+        Y = (f(0.212671) * c[:, 0] + f(0.715160) * c[:, 1]) + f(0.072169) * c[:, 2]
+        b = np.ascontiguousarray(Y, f).view(np.uint32) >> np.uint32(19)
+        ok = (b >= 16) & (b < 4080)
+        if aov is not None:
+            ok &= np.asarray(aov, f).reshape(-1, 8)[:, 7] * f(norm) > 0
+    return np.bincount(b[ok].astype(np.int64), minlength=METER_BINS).astype(np.uint32)
+
+
+def meter_numpy(color, aov=None, settings=None, prev=None, norm=1.0) -> np.ndarray:
+    """What bdpt_meter computes, as the header states it: color (H, W, 3), aov (H, W, 8) or None, prev an earlier
+    call's 4 words or None -> the 4 words [e, w, T, b_key | b_white << 16] as uint32. Float32, operation for
+    operation the kernels' own."""
+    f = np.float32
+    s = settings or MeterSettings()
+    hist = meter_histogram_numpy(color, aov, norm)
+    T = int(hist.sum())
+    out = np.zeros(4, np.uint32)
+    if T == 0:
+        out[:2] = np.array([s.fallback_exposure, s.fallback_white], f).view(np.uint32)
+        return out
+    run = np.cumsum(hist.astype(np.int64))
+    bins = [int(np.searchsorted(run, (T * int(pm) + 999) // 1000, side="left")) for pm in (s.key_permille, s.white_permille)]
+    Yk, Yw = (np.array([b << 19 | 1 << 18], np.uint32).view(f)[0] for b in bins)
+    with np.errstate(all="ignore"):
+        e = f(s.key) / Yk
+        if prev is not None and f(s.rate) < 1:
+            e_p = np.asarray(prev, np.uint32).reshape(4)[:1].view(f)[0]
+            if e_p > 0:
+                e = e_p + (e - e_p) * f(s.rate)
+        ew = e * Yw
+    w = ew if ew > 1 else f(1)
+    out[:2] = np.array([e, w], f).view(np.uint32)
+    out[2], out[3] = T, bins[0] | bins[1] << 16
+    return out
+
+
+def display_numpy(color, thresholds, settings=None, meter=None, norm=1.0) -> np.ndarray:
+    """What bdpt_display computes, as the header states it: color (H, W, 3), thresholds the library's table of
+    settings.encode (display_thresholds), meter bdpt_meter's 4 words or None -> uint8 (H, W, channels). Float32,
+    operation for operation the kernel's own; the code is searchsorted(T, y, side="right")."""
+    f = np.float32
+    s = settings or DisplaySettings()
+    c = np.asarray(color, f)
+    H, W = c.shape[:2]
+    T = np.asarray(thresholds, f).reshape(255)
+    e, w = f(s.exposure), f(s.white)
+    if meter is not None:
+        e, w = np.asarray(meter, np.uint32).reshape(4)[:2].view(f)
+    tone = _code_of(TONES, s.tone, "tone")
+    with np.errstate(all="ignore"):
+        x = (c.reshape(H, W, 3) * f(norm)) * e
+        x = np.where(x > 0, x, f(0))
+        x = np.where(x < f(65536), x, f(65536))
+        if tone == TONES["reinhard"]:
+            iw2 = f(1) / (w * w)
+            y = (x * (f(1) + x * iw2)) / (f(1) + x)
+        elif tone == TONES["filmic"]:
+            n = x * (f(2.51) * x + f(0.03))
+            d = x * (f(2.43) * x + f(0.59)) + f(0.14)
+            y = n / d
+        else:
+            y = x
+    code = np.searchsorted(T, y, side="right").astype(np.uint8)
+    if int(s.channels) == 4:
+        code = np.concatenate([code, np.full((H, W, 1), 255, np.uint8)], axis=-1)
+    return code
+
+
+def _image_bytes(pixels, width, height, channels):
+    a = np.ascontiguousarray(pixels, dtype=np.uint8).reshape(-1)
+    if a.size != width * height * channels:
+        raise BdptError(f"image has {a.size} bytes, expected {width * height * channels}")
+    return a
+
+
+def encode_png(pixels, width: int, height: int, channels: int = 3) -> bytes:
+    """bdpt_encode_png: 8-bit RGB / RGBA as an uncompressed PNG (filter 0, zlib stored blocks)."""
+    a = _image_bytes(pixels, width, height, channels)
+    n = ctypes.c_int64(0)
+    _check(lib().bdpt_encode_png(a.ctypes.data, width, height, channels, None, 0, ctypes.byref(n)))
+    out = np.zeros(n.value, np.uint8)
+    _check(lib().bdpt_encode_png(a.ctypes.data, width, height, channels, out.ctypes.data, n.value, ctypes.byref(n)))
+    return out.tobytes()
+
+
+def save_png(pixels, width: int, height: int, path: str, channels: int = 3) -> None:
+    a = _image_bytes(pixels, width, height, channels)
+    _check(lib().bdpt_save_png(a.ctypes.data, width, height, channels, path.encode()))
+
+
+def save_ppm(rgb, width: int, height: int, path: str) -> None:
+    """bdpt_save_ppm: binary P6, maxval 255, the header form the texture reader accepts."""
+    a = _image_bytes(rgb, width, height, 3)
+    _check(lib().bdpt_save_ppm(a.ctypes.data, width, height, path.encode()))
+
+
 def denoise_var_settings() -> "DenoiseSettings":
     """bdpt_denoise_var's defaults: the header's BDPT_DENOISE_VAR_ITERATIONS / _SIGMA_COLOR, the other fields
     DenoiseSettings' own."""
@@ -2164,13 +2337,17 @@ class BDPTIntegrator:
                                     ctypes.c_void_p(hist_in_ptr or None), ctypes.c_void_p(out_ptr),
                                     ctypes.c_void_p(hist_out_ptr), ctypes.byref(r), ctypes.c_void_p(stream_ptr)))
 
-    def render_sequence(self, cameras, spp_per_frame: int | None = None, denoise: bool = False, **params):
+    def render_sequence(self, cameras, spp_per_frame: int | None = None, denoise: bool = False,
+                        display: "DisplaySettings | None" = None, meter: "MeterSettings | None" = None, **params):
         """Generator: one accumulated frame per camera of `cameras`. Frame f renders spp_per_frame samples
         (default the configured spp) and the feature buffers at cameras[f], with the seed base moved on by
         f * width * height * spp so that no two frames repeat a sample, and carries the history of frame f - 1
         into it with reproject (params: ReprojectSettings fields or settings=). Yields the accumulated (H, W, 3)
-        frame; with denoise, (accumulated, bdpt_denoise of it at norm 1 under the frame's own guides). The
-        configured camera, spp and seed base are put back when the generator ends."""
+        frame; with denoise, (accumulated, bdpt_denoise of it at norm 1 under the frame's own guides). With
+        display=DisplaySettings(...) the tuple additionally ends in the frame's 8-bit image, a uint8 (H, W,
+        channels) array: the last float frame of the tuple metered under the frame's guides (meter=, default
+        MeterSettings()) and displayed on the device, each frame's exposure adapted from the previous frame's
+        meter words at meter.rate. The configured camera, spp and seed base are put back when the generator ends."""
         cfg = self.config
         saved = (cfg.camera, cfg.spp, cfg.seed_base)
         spp = cfg.spp if spp_per_frame is None else int(spp_per_frame)
@@ -2179,7 +2356,7 @@ class BDPTIntegrator:
             from dataclasses import replace
             settings = replace(settings, **params)
         try:
-            hist, prev = None, None
+            hist, prev, words = None, None, None
             for f, cam in enumerate(cameras):
                 cfg.camera, cfg.spp = cam, spp
                 cfg.seed_base = (saved[2] + f * cfg.width * cfg.height * spp) & 0xFFFFFFFF
@@ -2188,9 +2365,121 @@ class BDPTIntegrator:
                 self.render_aov()
                 out, hist = self.reproject(cam if prev is None else prev, hist, settings=settings)
                 prev = cam
-                yield (out, self.denoise(out)) if denoise else out
+                frames = (out, self.denoise(out)) if denoise else (out,)
+                if display is not None:
+                    import torch
+                    dev = torch.device("cuda", self.device)
+                    words = self.meter(torch.from_numpy(frames[-1]).to(dev), torch.from_numpy(self.aov).to(dev), prev=words,
+                                       settings=meter)
+                    frames += (self.display(torch.from_numpy(frames[-1]).to(dev), meter=words, settings=display).cpu().numpy(),)
+                yield frames if len(frames) > 1 else frames[0]
         finally:
             cfg.camera, cfg.spp, cfg.seed_base = saved
+
+    @staticmethod
+    def _frame_tensor(entry, t, channels, what):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3
+                and t.shape[2] == channels and t.is_contiguous()):
+            raise BdptError(f"{entry}: {what} must be a contiguous float32 cuda tensor of shape (H, W, {channels})")
+        return t
+
+    @staticmethod
+    def _words_tensor(entry, t, what):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.numel() == 4 and t.is_contiguous()):
+            raise BdptError(f"{entry}: {what} must be a contiguous int32 cuda tensor of 4 words (meter()'s result)")
+        return t
+
+    def _torch_stream(self, device):
+        """The handle of torch's current stream for a call on torch tensors. A stream of torch's own orders the
+        call with the tensors' other work and nothing waits. Torch's default stream has the handle 0, which the
+        library reads as "the context's own stream", and the two are not ordered against each other: then the
+        tensors' pending work is waited for here, and the caller waits for the call (_torch_done)."""
+        import torch
+        s = torch.cuda.current_stream(device)
+        if s.cuda_stream == 0:
+            s.synchronize()
+        return s.cuda_stream
+
+    def _torch_done(self, handle):
+        if handle == 0:
+            self.synchronize()
+
+    def meter(self, color, aov=None, prev=None, settings: "MeterSettings | None" = None, norm: float = 1.0):
+        """bdpt_meter on torch's current stream (_torch_stream): color a float32 cuda tensor (H, W, 3), aov (H, W,
+        8) or None, prev an earlier call's words or None -> the 4 words [e, w, T, b_key | b_white << 16] as an
+        int32 cuda tensor (the bits; .view(torch.float32)[:2] are e and w)."""
+        import torch
+        c = self._frame_tensor("meter", color, 3, "color")
+        H, W = c.shape[:2]
+        a = None if aov is None else self._frame_tensor("meter", aov, 8, "aov")
+        if a is not None and tuple(a.shape[:2]) != (H, W):
+            raise BdptError(f"meter: aov is {tuple(a.shape[:2])}, color {(H, W)}")
+        pw = None if prev is None else self._words_tensor("meter", prev, "prev")
+        out = torch.empty(4, dtype=torch.int32, device=c.device)
+        st = self._torch_stream(c.device)
+        self.meter_device(c.data_ptr(), 0 if a is None else a.data_ptr(), 0 if pw is None else pw.data_ptr(), out.data_ptr(),
+                          W, H, st, norm, settings)
+        self._torch_done(st)
+        return out
+
+    def meter_device(self, rgb_ptr: int, aov_ptr: int, prev_ptr: int, out_ptr: int, width: int | None = None,
+                     height: int | None = None, stream_ptr: int = 0, norm: float = 1.0,
+                     settings: "MeterSettings | None" = None) -> None:
+        """bdpt_meter: asynchronous, on device buffers; aov_ptr / prev_ptr 0 = none."""
+        m = (settings or MeterSettings()).c(norm)
+        W, H = self.config.width if width is None else width, self.config.height if height is None else height
+        _check(lib().bdpt_meter(self._h, W, H, ctypes.c_void_p(rgb_ptr), ctypes.c_void_p(aov_ptr or None),
+                                ctypes.c_void_p(prev_ptr or None), ctypes.byref(m), ctypes.c_void_p(out_ptr),
+                                ctypes.c_void_p(stream_ptr)))
+
+    def meter_histogram(self) -> np.ndarray:
+        """The 4096 bin counts of this context's last meter call (bdpt_debug_meter_histogram; waits for it)."""
+        out = np.zeros(METER_BINS, np.uint32)
+        _check(lib().bdpt_debug_meter_histogram(self._h, out.ctypes.data))
+        return out
+
+    def display(self, color, exposure=None, aov=None, meter=None, prev=None, settings: "DisplaySettings | None" = None,
+                meter_settings: "MeterSettings | None" = None, norm: float = 1.0, out=None):
+        """bdpt_display on torch's current stream (_torch_stream): color a float32 cuda tensor (H, W, 3) -> a uint8 cuda tensor
+        (H, W, channels). exposure: None = settings.exposure, a number = that exposure, "auto" = bdpt_meter of
+        color (under aov, from prev, with meter_settings) chained into the display on the device, with no host
+        round trip. meter: words of an earlier meter() call to use as they are. out: a uint8 cuda tensor (or a
+        view of one) of H * W * channels bytes to write into."""
+        import torch
+        from dataclasses import replace
+        c = self._frame_tensor("display", color, 3, "color")
+        H, W = c.shape[:2]
+        s = settings or DisplaySettings()
+        if isinstance(exposure, str):
+            if exposure != "auto":
+                raise ValueError(f'display: exposure must be a number, None or "auto", not {exposure!r}')
+            if meter is not None:
+                raise ValueError('display: exposure="auto" meters the frame itself: give that or meter=, not both')
+            meter = self.meter(c, aov, prev, meter_settings, norm)
+        elif exposure is not None:
+            s = replace(s, exposure=float(exposure))
+        mw = None if meter is None else self._words_tensor("display", meter, "meter")
+        ch = int(s.channels)
+        if out is None:
+            out = torch.empty((H, W, ch) if ch in (3, 4) else (H, W, 4), dtype=torch.uint8, device=c.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+                  and out.numel() == H * W * ch):
+            raise BdptError(f"display: out must be a contiguous uint8 cuda tensor of {H * W * ch} bytes")
+        st = self._torch_stream(c.device)
+        self.display_device(c.data_ptr(), out.data_ptr(), 0 if mw is None else mw.data_ptr(), W, H, st, norm, s)
+        self._torch_done(st)
+        return out
+
+    def display_device(self, rgb_ptr: int, out_ptr: int, meter_ptr: int = 0, width: int | None = None,
+                       height: int | None = None, stream_ptr: int = 0, norm: float = 1.0,
+                       settings: "DisplaySettings | None" = None) -> None:
+        """bdpt_display: asynchronous, on device buffers; meter_ptr 0 = settings.exposure and settings.white."""
+        d = (settings or DisplaySettings()).c(norm)
+        W, H = self.config.width if width is None else width, self.config.height if height is None else height
+        _check(lib().bdpt_display(self._h, W, H, ctypes.c_void_p(rgb_ptr), ctypes.c_void_p(meter_ptr or None),
+                                  ctypes.byref(d), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream_ptr)))
 
     def denoise_var(self, rgb=None, var=None, aov=None, samples_done: int | None = None, return_variance: bool = False,
                     **params):

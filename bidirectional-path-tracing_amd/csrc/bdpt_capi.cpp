@@ -102,6 +102,12 @@ hipError_t launch_denoise_var_blur(int W, int H, const void* src, void* dst, flo
 hipError_t launch_denoise_var_iter(int W, int H, int step, float sc2, float inv_n, float sigma_z, int demodulate,
                                    const void* guide, const void* src, void* dst, float* out, float* out_var, bool last,
                                    hipStream_t st);
+// display_kernels.hip: display output (bdpt_meter, bdpt_display)
+hipError_t launch_display(const float* color, const float* thresholds, const uint32_t* meter, float norm, float exposure,
+                          float white, int tone, int channels, size_t N, unsigned char* out, hipStream_t st);
+hipError_t launch_meter(const float* color, const float* aov, const uint32_t* prev, float norm, float key, int key_permille,
+                        int white_permille, float rate, float fallback_exposure, float fallback_white, size_t N,
+                        uint32_t* hist, uint32_t* out, hipStream_t st);
 // aov_kernels.hip: a masked sum of path-length layers (planes of n floats)
 hipError_t launch_layers_compose(const float* layers, size_t n, uint64_t mask, float* out, hipStream_t st);
 // aov_kernels.hip: light-group planes (n floats each) recombined with per-group RGB gains (host, n_groups x 3)
@@ -368,6 +374,12 @@ struct bdpt_ctx : CtxStream {
     // filter for many planes (bdpt_denoise_planes): packed guides, the guide's images B_0 .. B_7
     // (SHARED mode) and the ping-pong pair of the planes in flight; each grows on its own
     DevBuf<void> dnp_guide, dnp_traj, dnp_img[2];
+    // display output (bdpt_meter, bdpt_display): the meter's global histogram (zeroed per call), the three
+    // encodes' threshold tables (256 floats each, uploaded at the first display call), the host forms' staging
+    DevBuf<uint32_t> meter_hist;
+    DevBuf<float> display_tables;
+    bool display_tables_ready = false;
+    DevBuf<void> display_stage;
     // stats of the last render
     bool pending_timing = false;
     bdpt_stats stats{};
@@ -2889,6 +2901,185 @@ int bdpt_reproject_host(bdpt_ctx* c, const bdpt_frame_params* p, const float* co
     if ((rc = bdpt_reproject(c, p, dc, da, hist_in ? dhi : nullptr, dout, dho, r, c->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(out, dout, px * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(hist_out, dho, px * 8 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+// ---------------------------------------------------------------- display output
+// The encode's curve in double, on y >= 0.
+static double encode_curve(int32_t encode, double y) {
+    if (encode == BDPT_ENCODE_SRGB) return y <= 0.0031308 ? 12.92 * y : 1.055 * std::pow(y, 1.0 / 2.4) - 0.055;
+    if (encode == BDPT_ENCODE_GAMMA22) return std::pow(y, 1.0 / 2.2);
+    return y;
+}
+
+int bdpt_display_thresholds(int32_t encode, float out[255]) {
+    if (encode != BDPT_ENCODE_SRGB && encode != BDPT_ENCODE_GAMMA22 && encode != BDPT_ENCODE_LINEAR)
+        return fail(BDPT_ERR_INVALID, "bdpt_display_thresholds: encode must be BDPT_ENCODE_SRGB, _GAMMA22 or _LINEAR");
+    if (!out) return fail(BDPT_ERR_INVALID, "bdpt_display_thresholds: out must not be NULL");
+    for (int k = 1; k <= 255; k++) {
+        const double target = (k - 0.5) / 255.0;
+        // a start near the step from the inverse curve, then float by float to the smallest t that reaches it
+        double y = target;
+        if (encode == BDPT_ENCODE_SRGB) y = target <= 12.92 * 0.0031308 ? target / 12.92 : std::pow((target + 0.055) / 1.055, 2.4);
+        else if (encode == BDPT_ENCODE_GAMMA22) y = std::pow(target, 2.2);
+        float t = static_cast<float>(y);
+        while (encode_curve(encode, t) < target) t = std::nextafterf(t, 2.f);
+        for (float below = std::nextafterf(t, 0.f); t > 0.f && encode_curve(encode, below) >= target; below = std::nextafterf(t, 0.f)) t = below;
+        out[k - 1] = t;
+    }
+    return BDPT_OK;
+}
+
+struct ByteSpan {
+    const char* name;
+    const void* p;
+    size_t bytes;
+};
+static bool byte_spans_overlap(const ByteSpan& a, const ByteSpan& b) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
+    return a.p && b.p && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+static int check_image_size(const std::string& entry, int32_t width, int32_t height) {
+    if (width <= 0 || height <= 0) return fail(BDPT_ERR_INVALID, entry + "width/height must be > 0");
+    if (static_cast<uint64_t>(width) * static_cast<uint64_t>(height) >= (1ull << 28))
+        return fail(BDPT_ERR_INVALID, entry + "width * height must be below 2^28");
+    return BDPT_OK;
+}
+static bool positive_finite(float v) { return v > 0.f && std::isfinite(v); }
+
+static int check_meter(int32_t width, int32_t height, const float* color, const float* aov, const uint32_t* prev,
+                       const bdpt_meter_params* m, const uint32_t* out) {
+    const std::string entry = "bdpt_meter: ";
+    if (!m) return fail(BDPT_ERR_INVALID, entry + "null meter params");
+    if (int rc = check_image_size(entry, width, height)) return rc;
+    if (!positive_finite(m->norm)) return fail(BDPT_ERR_INVALID, entry + "norm must be > 0");
+    if (!positive_finite(m->key)) return fail(BDPT_ERR_INVALID, entry + "key must be > 0");
+    if (m->key_permille < 1 || m->key_permille > 1000) return fail(BDPT_ERR_INVALID, entry + "key_permille must be in [1, 1000]");
+    if (m->white_permille < 1 || m->white_permille > 1000) return fail(BDPT_ERR_INVALID, entry + "white_permille must be in [1, 1000]");
+    if (!(m->rate > 0.f && m->rate <= 1.f)) return fail(BDPT_ERR_INVALID, entry + "rate must be in (0, 1]");
+    if (!positive_finite(m->fallback_exposure)) return fail(BDPT_ERR_INVALID, entry + "fallback_exposure must be > 0");
+    if (!positive_finite(m->fallback_white)) return fail(BDPT_ERR_INVALID, entry + "fallback_white must be > 0");
+    if (!color) return fail(BDPT_ERR_INVALID, entry + "color must not be NULL");
+    if (!out) return fail(BDPT_ERR_INVALID, entry + "out_words must not be NULL");
+    const size_t px = static_cast<size_t>(width) * height;
+    const ByteSpan o = {"out_words", out, 16};
+    const ByteSpan in[] = {{"color", color, px * 12}, {"aov", aov, px * 32}, {"prev", prev, 16}};
+    for (const ByteSpan& i : in)
+        if (byte_spans_overlap(o, i)) return fail(BDPT_ERR_INVALID, entry + o.name + " overlaps " + i.name);
+    return BDPT_OK;
+}
+
+int bdpt_meter(bdpt_ctx* c, int32_t width, int32_t height, const float* color, const float* aov, const uint32_t* prev,
+               const bdpt_meter_params* m, uint32_t* out, void* hip_stream) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_meter(width, height, color, aov, prev, m, out);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    HIP_TRY(c->meter_hist.reserve(sizeof(uint32_t) * BDPT_METER_BINS));
+    if ((rc = begin_use(c, st))) return rc;
+    if ((rc = begin_timed(c, st))) return rc;
+    HIP_TRY(launch_meter(color, aov, prev, m->norm, m->key, m->key_permille, m->white_permille, m->rate, m->fallback_exposure,
+                         m->fallback_white, static_cast<size_t>(width) * height, c->meter_hist, out, st));
+    return end_timed(c, st, 0, 2);
+}
+
+// The host forms' staging: [16-byte aligned parts] color, aov, 4 words in, 4 words out, display bytes.
+static size_t up16(size_t n) { return (n + 15) & ~static_cast<size_t>(15); }
+
+int bdpt_meter_host(bdpt_ctx* c, int32_t width, int32_t height, const float* color, const float* aov, const uint32_t* prev,
+                    const bdpt_meter_params* m, uint32_t out[4]) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_meter(width, height, color, aov, prev, m, out);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t px = static_cast<size_t>(width) * height, nc = up16(px * 12), na = up16(px * 32);
+    HIP_TRY(c->display_stage.reserve(nc + na + 32));
+    char* const base = static_cast<char*>(c->display_stage.get());
+    float* const dc = reinterpret_cast<float*>(base);
+    float* const da = reinterpret_cast<float*>(base + nc);
+    uint32_t* const dprev = reinterpret_cast<uint32_t*>(base + nc + na);
+    uint32_t* const dout = dprev + 4;
+    HIP_TRY(hipMemcpyAsync(dc, color, px * 12, hipMemcpyHostToDevice, c->stream));
+    if (aov) HIP_TRY(hipMemcpyAsync(da, aov, px * 32, hipMemcpyHostToDevice, c->stream));
+    if (prev) HIP_TRY(hipMemcpyAsync(dprev, prev, 16, hipMemcpyHostToDevice, c->stream));
+    if ((rc = bdpt_meter(c, width, height, dc, aov ? da : nullptr, prev ? dprev : nullptr, m, dout, c->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+int bdpt_debug_meter_histogram(bdpt_ctx* c, uint32_t out[BDPT_METER_BINS]) {
+    if (!c || !out) return fail(BDPT_ERR_INVALID, "null argument");
+    if (!c->meter_hist.get()) return fail(BDPT_ERR_INVALID, "bdpt_debug_meter_histogram: no bdpt_meter call on this context yet");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, c->meter_hist, sizeof(uint32_t) * BDPT_METER_BINS, hipMemcpyDeviceToHost));
+    return BDPT_OK;
+}
+
+static int check_display(int32_t width, int32_t height, const float* color, const uint32_t* meter,
+                         const bdpt_display_params* d, const unsigned char* out) {
+    const std::string entry = "bdpt_display: ";
+    if (!d) return fail(BDPT_ERR_INVALID, entry + "null display params");
+    if (int rc = check_image_size(entry, width, height)) return rc;
+    if (!positive_finite(d->norm)) return fail(BDPT_ERR_INVALID, entry + "norm must be > 0");
+    if (!positive_finite(d->exposure)) return fail(BDPT_ERR_INVALID, entry + "exposure must be > 0");
+    if (!positive_finite(d->white)) return fail(BDPT_ERR_INVALID, entry + "white must be > 0");
+    if (d->tone != BDPT_TONE_CLAMP && d->tone != BDPT_TONE_REINHARD && d->tone != BDPT_TONE_FILMIC)
+        return fail(BDPT_ERR_INVALID, entry + "tone must be BDPT_TONE_CLAMP, _REINHARD or _FILMIC");
+    if (d->encode != BDPT_ENCODE_SRGB && d->encode != BDPT_ENCODE_GAMMA22 && d->encode != BDPT_ENCODE_LINEAR)
+        return fail(BDPT_ERR_INVALID, entry + "encode must be BDPT_ENCODE_SRGB, _GAMMA22 or _LINEAR");
+    if (d->channels != 3 && d->channels != 4) return fail(BDPT_ERR_INVALID, entry + "channels must be 3 or 4");
+    if (!color) return fail(BDPT_ERR_INVALID, entry + "color must not be NULL");
+    if (!out) return fail(BDPT_ERR_INVALID, entry + "out must not be NULL");
+    const size_t px = static_cast<size_t>(width) * height;
+    const ByteSpan o = {"out", out, px * static_cast<size_t>(d->channels)};
+    const ByteSpan in[] = {{"color", color, px * 12}, {"meter", meter, 16}};
+    for (const ByteSpan& i : in)
+        if (byte_spans_overlap(o, i)) return fail(BDPT_ERR_INVALID, entry + o.name + " overlaps " + i.name);
+    return BDPT_OK;
+}
+
+int bdpt_display(bdpt_ctx* c, int32_t width, int32_t height, const float* color, const uint32_t* meter,
+                 const bdpt_display_params* d, unsigned char* out, void* hip_stream) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_display(width, height, color, meter, d, out);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if (!c->display_tables_ready) {  // once per context: the three tables, 256 floats apart
+        float host[3 * 256] = {};
+        for (int32_t enc = 0; enc < 3; enc++)
+            if ((rc = bdpt_display_thresholds(enc, host + 256 * enc))) return rc;
+        HIP_TRY(c->display_tables.reserve(sizeof(host)));
+        HIP_TRY(hipMemcpy(c->display_tables, host, sizeof(host), hipMemcpyHostToDevice));
+        c->display_tables_ready = true;
+    }
+    if ((rc = begin_use(c, st))) return rc;
+    if ((rc = begin_timed(c, st))) return rc;
+    HIP_TRY(launch_display(color, c->display_tables.get() + 256 * d->encode, meter, d->norm, d->exposure, d->white, d->tone,
+                           d->channels, static_cast<size_t>(width) * height, out, st));
+    return end_timed(c, st, 0, 1);
+}
+
+int bdpt_display_host(bdpt_ctx* c, int32_t width, int32_t height, const float* color, const uint32_t* meter,
+                      const bdpt_display_params* d, unsigned char* out) {
+    if (!c) return fail(BDPT_ERR_INVALID, "null ctx");
+    int rc = check_display(width, height, color, meter, d, out);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t px = static_cast<size_t>(width) * height, nc = up16(px * 12), nb = px * static_cast<size_t>(d->channels);
+    HIP_TRY(c->display_stage.reserve(nc + 16 + nb));
+    char* const base = static_cast<char*>(c->display_stage.get());
+    float* const dc = reinterpret_cast<float*>(base);
+    uint32_t* const dmeter = reinterpret_cast<uint32_t*>(base + nc);
+    unsigned char* const dout = reinterpret_cast<unsigned char*>(base + nc + 16);
+    HIP_TRY(hipMemcpyAsync(dc, color, px * 12, hipMemcpyHostToDevice, c->stream));
+    if (meter) HIP_TRY(hipMemcpyAsync(dmeter, meter, 16, hipMemcpyHostToDevice, c->stream));
+    if ((rc = bdpt_display(c, width, height, dc, meter ? dmeter : nullptr, d, dout, c->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout, nb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BDPT_OK;
 }

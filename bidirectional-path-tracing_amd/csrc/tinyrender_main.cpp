@@ -76,8 +76,19 @@
 // used: one flag without the other, an unreadable or malformed FILE, a path / direct scene, and --gpus /
 // --devices, --layers, --light-groups, --strategies, --cross, --denoise-planes, --batches, --denoise-var,
 // --adaptive, --sample-window and --aov.
+// --display[=png|ppm] (default png) also writes an 8-bit image beside the EXRs, the same name with the extension
+// .png / .ppm: <out stem>.png from the last colour the command made (the plain frame, or <out>_denoised.exr's with
+// --denoise / --denoise-var; --adaptive's frame), through bdpt_meter_host and bdpt_display_host. --exposure
+// auto[:KEY[:RATE]] (the default; the header's BDPT_METER_* otherwise) meters the frame, under the feature buffers
+// when the command rendered them; --exposure EV shows it at 2^EV. --tone clamp|reinhard|filmic (default reinhard),
+// --encode srgb|gamma22|linear (default srgb). With --cameras --temporal every frame gets <out stem>.f<nn>.png, its
+// exposure adapted from the frame before at RATE. The planes of --layers, --light-groups, --strategies and --cross
+// get one file each, all shown with the sum frame's meter words, so that they stay comparable. The EXRs are the
+// same bytes with or without it; with several devices the first one displays. A bad value of any of the four
+// flags, or one of the last three without --display, is refused, the flag named, before any device is used.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -169,7 +180,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Syntax: %s <scene.toml> [nogui] [--width W --height H --spp N --rr D --device K "
                              "--out FILE.exr --seed S --gpus N --devices a,b,... --shard samples|rows "
-                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted] --cross --denoise-planes[=own|shared] --batches K --denoise-var[=ITER] --adaptive THR[:K[:STEP[:PASSES]]] --cameras FILE --temporal[=MAXHIST]]\n", argv[0]);
+                             "--sample-window F:S:C --aov --denoise[=ITER] --layers N --light-groups --strategies[=unweighted] --cross --denoise-planes[=own|shared] --batches K --denoise-var[=ITER] --adaptive THR[:K[:STEP[:PASSES]]] --cameras FILE --temporal[=MAXHIST] --display[=png|ppm] --exposure auto[:KEY[:RATE]]|EV --tone clamp|reinhard|filmic --encode srgb|gamma22|linear]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string toml = argv[1];
@@ -196,6 +207,10 @@ int main(int argc, char** argv) {
     float temporal_max_history = BDPT_REPROJECT_MAX_HISTORY;
     std::string cameras_file;       // --cameras FILE
     std::vector<bdpt_camera> cameras;
+    enum { DISPLAY_NONE, DISPLAY_PNG, DISPLAY_PPM } display = DISPLAY_NONE;  // --display[=png|ppm]
+    bool exposure_auto = true, exposure_given = false, tone_given = false, encode_given = false;
+    bdpt_meter_params meter = {1.f, BDPT_METER_KEY, BDPT_METER_KEY_PERMILLE, BDPT_METER_WHITE_PERMILLE, BDPT_METER_RATE, 1.f, 1.f};
+    bdpt_display_params shown = {1.f, 1.f, 1.f, BDPT_TONE_REINHARD, BDPT_ENCODE_SRGB, 3};
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -306,6 +321,55 @@ int main(int argc, char** argv) {
         } else if (a.rfind("--temporal", 0) == 0) {
             std::fprintf(stderr, "%s: --temporal takes no value or =MAXHIST\n", a.c_str());
             return EXIT_FAILURE;
+        } else if (a == "--display" || a == "--display=png") {
+            display = DISPLAY_PNG;
+        } else if (a == "--display=ppm") {
+            display = DISPLAY_PPM;
+        } else if (a.rfind("--display", 0) == 0) {
+            std::fprintf(stderr, "%s: --display takes no value, =png or =ppm\n", a.c_str());
+            return EXIT_FAILURE;
+        } else if (a == "--exposure") {
+            const std::string v = next("--exposure");
+            bool ok = true;
+            if (v.compare(0, 4, "auto") == 0) {  // auto[:KEY[:RATE]]
+                exposure_auto = true;
+                const char* q = v.c_str() + 4;
+                float* const field[2] = {&meter.key, &meter.rate};
+                for (int k = 0; ok && k < 2 && *q == ':'; k++) {
+                    char* end = nullptr;
+                    *field[k] = std::strtof(q + 1, &end);
+                    ok = end != q + 1;
+                    q = end;
+                }
+                ok = ok && *q == '\0' && meter.key > 0.f && meter.key < 1e30f && meter.rate > 0.f && meter.rate <= 1.f;
+            } else {  // EV, in stops
+                char* end = nullptr;
+                const double ev = std::strtod(v.c_str(), &end);
+                ok = end != v.c_str() && *end == '\0' && ev >= -64. && ev <= 64.;
+                if (ok) exposure_auto = false, shown.exposure = static_cast<float>(std::exp2(ev));
+            }
+            if (!ok) {
+                std::fprintf(stderr, "--exposure %s: auto[:KEY[:RATE]] with KEY > 0 and RATE in (0, 1], or EV, a number of stops in [-64, 64]\n",
+                             v.c_str());
+                return EXIT_FAILURE;
+            }
+            exposure_given = true;
+        } else if (a == "--tone") {
+            const std::string v = next("--tone");
+            if (v != "clamp" && v != "reinhard" && v != "filmic") {
+                std::fprintf(stderr, "--tone must be clamp, reinhard or filmic, not %s\n", v.c_str());
+                return EXIT_FAILURE;
+            }
+            shown.tone = v == "clamp" ? BDPT_TONE_CLAMP : v == "reinhard" ? BDPT_TONE_REINHARD : BDPT_TONE_FILMIC;
+            tone_given = true;
+        } else if (a == "--encode") {
+            const std::string v = next("--encode");
+            if (v != "srgb" && v != "gamma22" && v != "linear") {
+                std::fprintf(stderr, "--encode must be srgb, gamma22 or linear, not %s\n", v.c_str());
+                return EXIT_FAILURE;
+            }
+            shown.encode = v == "srgb" ? BDPT_ENCODE_SRGB : v == "gamma22" ? BDPT_ENCODE_GAMMA22 : BDPT_ENCODE_LINEAR;
+            encode_given = true;
         } else if (a == "--denoise-planes" || a == "--denoise-planes=shared") {
             denoise_planes = BDPT_DENOISE_PLANES_SHARED;
         } else if (a == "--denoise-planes=own") {
@@ -352,6 +416,10 @@ int main(int argc, char** argv) {
     }
     if (windowed && !devices.empty()) {
         std::fprintf(stderr, "--sample-window renders on one device (--gpus / --devices split the frame themselves)\n");
+        return EXIT_FAILURE;
+    }
+    if (display != DISPLAY_NONE && windowed && window.count == 0) {
+        std::fprintf(stderr, "--display of an empty --sample-window (count 0): there is no sample to normalise by\n");
         return EXIT_FAILURE;
     }
     if (want_denoise && windowed && window.count == 0) {
@@ -411,6 +479,11 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--cameras %s: %s\n", cameras_file.c_str(), error.c_str());
             return EXIT_FAILURE;
         }
+    }
+    if (display == DISPLAY_NONE && (exposure_given || tone_given || encode_given)) {
+        std::fprintf(stderr, "%s sets how --display[=png|ppm] shows the frame: give that flag\n",
+                     exposure_given ? "--exposure" : tone_given ? "--tone" : "--encode");
+        return EXIT_FAILURE;
     }
     if (shard_given && devices.empty()) {
         std::fprintf(stderr, "--shard applies to a multi-device render (--gpus N / --devices a,b,...)\n");
@@ -527,7 +600,32 @@ int main(int argc, char** argv) {
     p.row_stride = 1;
     std::vector<float> rgb(static_cast<size_t>(cfg.width) * cfg.height * 3, 0.f);  // Integrator::init: rgb->clear()
 
+    // --display: the 8-bit image of `color` beside the EXR `exr_name`, its extension .png / .ppm. With --exposure
+    // auto the exposure and white point come from meter words: measure = true meters color (under aov, NULL:
+    // every pixel; adapted from prev, NULL: none) into words first, measure = false shows it with the words given.
+    auto write_display = [&](bdpt_ctx* dctx, const float* color, const float* aov, const uint32_t* prev, uint32_t* words,
+                             bool measure, float norm, const std::string& exr_name) -> int {
+        if (exposure_auto && measure) {
+            bdpt_meter_params m = meter;
+            m.norm = norm;
+            if (bdpt_meter_host(dctx, cfg.width, cfg.height, color, aov, prev, &m, words) != BDPT_OK) return die("bdpt_meter_host");
+        }
+        bdpt_display_params d = shown;
+        d.norm = norm;
+        std::vector<unsigned char> bytes(static_cast<size_t>(cfg.width) * cfg.height * 3);
+        if (bdpt_display_host(dctx, cfg.width, cfg.height, color, exposure_auto ? words : nullptr, &d, bytes.data()) != BDPT_OK)
+            return die("bdpt_display_host");
+        const std::string stem = side_path(exr_name, "");
+        const std::string file = stem.substr(0, stem.size() - 4) + (display == DISPLAY_PNG ? ".png" : ".ppm");
+        const int rc = display == DISPLAY_PNG ? bdpt_save_png(bytes.data(), cfg.width, cfg.height, 3, file.c_str())
+                                              : bdpt_save_ppm(bytes.data(), cfg.width, cfg.height, file.c_str());
+        if (rc != BDPT_OK) return die(display == DISPLAY_PNG ? "bdpt_save_png" : "bdpt_save_ppm");
+        std::printf("Saved %s image to %s\n", display == DISPLAY_PNG ? "PNG" : "PPM", file.c_str());
+        return EXIT_SUCCESS;
+    };
+
     if (temporal) {  // the camera sequence: render, feature buffers, reproject, per frame
+        uint32_t words[2][4] = {};  // --display: the meter words of this frame and of the one before
         const std::string exr = out.empty() ? exr_path_of(toml) : out;
         const size_t px = static_cast<size_t>(cfg.width) * cfg.height;
         std::vector<float> aov(px * 8), acc(px * 3), den(px * 3), hist[2] = {std::vector<float>(px * 8), std::vector<float>(px * 8)};
@@ -559,6 +657,11 @@ int main(int argc, char** argv) {
                 const std::string side = side_path(exr, (std::string(suffix) + "_denoised").c_str());
                 if (bdpt_save_exr(den.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
                 std::printf("Saved EXR image to %s\n", side.c_str());
+            }
+            if (display != DISPLAY_NONE) {  // the frame's last colour, its exposure adapted from the frame before
+                if (const int rc = write_display(ctx, want_denoise ? den.data() : acc.data(), aov.data(), f ? words[(f - 1) & 1] : nullptr,
+                                                 words[f & 1], true, 1.f, frame))
+                    return rc;
             }
         }
         const auto t1 = std::chrono::high_resolution_clock::now();
@@ -637,6 +740,9 @@ int main(int argc, char** argv) {
         if (bdpt_save_exr(variance.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
         std::printf("Saved EXR image to %s\n", side.c_str());
     }
+    // --display shows the last colour the command made (the filtered frame if there is one) and meters it under
+    // the feature buffers when the command rendered them
+    std::vector<float> shown_color, shown_aov;
     if (want_aov || want_denoise || want_denoise_var) {
         bdpt_ctx* fctx = ctx;  // several devices: the first renders the feature buffers and filters
         if (!fctx && bdpt_ctx_create(scene, devices[0], &fctx) != BDPT_OK) return die("bdpt_ctx_create (feature buffers)");
@@ -664,6 +770,7 @@ int main(int argc, char** argv) {
             const std::string side = side_path(exr, "_denoised");
             if (bdpt_save_exr(den.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
             std::printf("Saved EXR image to %s\n", side.c_str());
+            if (display != DISPLAY_NONE) shown_color.swap(den);
         }
         if (want_denoise_var) {
             bdpt_denoise_params d = {denoise_var_iterations, BDPT_DENOISE_VAR_SIGMA_COLOR, BDPT_DENOISE_SIGMA_NORMAL,
@@ -676,8 +783,21 @@ int main(int argc, char** argv) {
             const std::string side = side_path(exr, "_denoised");
             if (bdpt_save_exr(den.data(), cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
             std::printf("Saved EXR image to %s\n", side.c_str());
+            if (display != DISPLAY_NONE) shown_color.swap(den);
         }
+        if (display != DISPLAY_NONE) shown_aov.swap(aov);
         if (fctx != ctx) bdpt_ctx_destroy(fctx);
+    }
+    uint32_t frame_words[4] = {};  // --exposure auto: the frame's meter words, with which its planes are shown too
+    const float window_norm = windowed ? static_cast<float>(cfg.spp) / static_cast<float>(window.count) : 1.f;
+    if (display != DISPLAY_NONE) {
+        bdpt_ctx* dctx = ctx;  // several devices: the first displays
+        if (!dctx && bdpt_ctx_create(scene, devices[0], &dctx) != BDPT_OK) return die("bdpt_ctx_create (display)");
+        const bool filtered = !shown_color.empty();  // (a filtered frame is normalised already)
+        if (const int rc = write_display(dctx, filtered ? shown_color.data() : rgb.data(), shown_aov.empty() ? nullptr : shown_aov.data(),
+                                         nullptr, frame_words, true, filtered ? 1.f : window_norm, exr))
+            return rc;
+        if (dctx != ctx) bdpt_ctx_destroy(dctx);
     }
     // --layers, --light-groups, --strategies: the frame again as n planes (on several devices the
     // first renders them), one EXR per plane under suffix(plane index), optionally only the planes
@@ -697,6 +817,9 @@ int main(int argc, char** argv) {
             const std::string side = side_path(exr, suffix(static_cast<int>(k)).c_str());
             if (bdpt_save_exr(px, cfg.width, cfg.height, side.c_str()) != BDPT_OK) return die("saveEXR");
             std::printf("Saved EXR image to %s\n", side.c_str());
+            // every plane under the sum frame's exposure and white point, so that the planes stay comparable
+            if (display != DISPLAY_NONE)
+                if (const int rc = write_display(pctx, px, nullptr, nullptr, frame_words, false, window_norm, side)) return rc;
         }
         if (denoise_planes >= 0) {
             bdpt_denoise_params d = {denoise_iterations, BDPT_DENOISE_SIGMA_COLOR, BDPT_DENOISE_SIGMA_NORMAL,

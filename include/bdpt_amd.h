@@ -49,6 +49,9 @@
  *   bdpt_render_pixels       (no counterpart) a sample window of the BDPT frame for a list of pixels
  *   bdpt_render_adaptive     (no counterpart) further samples only where the batch variance asks
  *   bdpt_reproject           (no counterpart) a preview's history reprojected into the next camera's frame
+ *   bdpt_meter               (no counterpart) exposure and white point from a luminance histogram of the frame
+ *   bdpt_display             srgb.fs (renderpass.cpp:397) exposure, tone curve and 8-bit encode on the device
+ *   bdpt_save_png / _ppm     (no counterpart) the 8-bit frame as a PNG or PPM file
  *
  * Conventions: plain C types only; status 0 = OK, < 0 = error (message from
  * bdpt_last_error(), thread-local). A context is bound to one HIP device and is
@@ -969,6 +972,118 @@ int bdpt_reproject_host(bdpt_ctx* ctx, const bdpt_frame_params* cur, const float
                         const float* hist_in_host, float* out_color_host, float* hist_out_host,
                         const bdpt_reproject_params* params);
 
+/* ---- display output: metered exposure, tone curve, 8-bit encode ---- */
+/* (new) The last stage of a preview: a linear float32 frame turned into 8-bit codes on the device. The
+ * reference ends its viewer's frame with a linear -> sRGB pass (src/core/renderpass.cpp:397,
+ * src/shaders/srgb.fs); exposure metering and the tone curves have no counterpart. Pinned to the formulas
+ * below and to their numpy restatements (bdpt_amd.py meter_numpy, display_numpy), bit for bit. Float32,
+ * every operation rounded on its own (no fma); only + - * /, comparisons and integer work on the device:
+ * no exp, log or pow in any kernel. The counts of the meter are integers added with integer atomics, so
+ * any order of the additions gives the same words: two runs give the same bits.
+ *
+ * Thresholds in place of the transfer curve. Quantising an encoded value to 8 bits, code = round(255 *
+ * curve(y)) clamped to 0..255, is a monotone step function of the linear value y, so it is stated by the
+ * 255 places where it steps: T_k, k = 1..255, the smallest float32 t with curve(t) >= (k - 0.5) / 255, curve
+ * evaluated in double on the host. Then code(y) = #{k : T_k <= y} (numpy: searchsorted(T, y, side="right")),
+ * exact for every float32 y, where a float32 pow on the device could differ from the host's by a code at a
+ * step. bdpt_display_thresholds needs no device. The curves, on y >= 0:
+ *   BDPT_ENCODE_SRGB     IEC 61966-2-1: y <= 0.0031308 ? 12.92 y : 1.055 y^(1/2.4) - 0.055
+ *   BDPT_ENCODE_GAMMA22  y^(1/2.2), the inverse of what the texture reader applies to a map (scene.cpp)
+ *   BDPT_ENCODE_LINEAR   y
+ * Every table is strictly increasing and below 1. BDPT_ERR_INVALID: an unknown encode, a NULL out. */
+#define BDPT_ENCODE_SRGB 0
+#define BDPT_ENCODE_GAMMA22 1
+#define BDPT_ENCODE_LINEAR 2
+int bdpt_display_thresholds(int32_t encode, float out[255]);
+
+/* (new) Exposure from a luminance histogram of the frame. color: width * height * 3 floats; aov (NULL: every
+ * pixel is a candidate): the frame's feature buffers (bdpt_render_aov, width * height * 8 floats); prev (NULL:
+ * none): the 4 output words of an earlier call, for exposure that adapts over a sequence.
+ * Per pixel: c = color * norm; Y = (0.212671 r + 0.715160 g) + 0.072169 b (getLuminance's constants,
+ * bdpt_path.hpp; two products and a sum, then a product and a sum). The pixel is counted iff it is covered -
+ * with aov, cov = aov[7] * norm > 0, as bdpt_denoise forms it - and Y is a positive normal finite float: 16 <=
+ * bits(Y) >> 19 < 4080 (a negative Y has the sign bit and lands above). Its bin is bits(Y) >> 19: the 8
+ * exponent bits and the top 4 mantissa bits, so 4096 uint32 bins form a piecewise-linear log2 scale of 16
+ * steps per stop.
+ * Over the frame, T the number of counted pixels: rank_key = (T * key_permille + 999) / 1000 in 64-bit
+ * integers; b_key the lowest bin at which the running count (bins ascending, inclusive) reaches rank_key;
+ * Y_key the float with bits (b_key << 19) | (1 << 18), the bin's centre; b_white, Y_white likewise from
+ * white_permille. e_m = key / Y_key; e = prev[0] + (e_m - prev[0]) * rate when prev is given, prev[0] > 0 and
+ * rate < 1, else e_m (at rate 1 the rounded blend would not be e_m itself); w = max(e * Y_white, 1).
+ * Output: four 32-bit words on the device, [float e, float w, uint32 T, uint32 b_key | b_white << 16]. With
+ * T == 0: [fallback_exposure, fallback_white, 0, 0].
+ * Metering sees first-hit coverage only: what a pixel shows through a mirror or glass counts as that
+ * pixel's luminance, and an environment seen on a miss is left out when aov is given.
+ * BDPT_ERR_INVALID, the field named in the message: a NULL color or out; width * height >= 2^28; norm, key,
+ * fallback_exposure or fallback_white not > 0; a permille outside 1..1000; rate outside (0, 1]; out
+ * overlapping color, aov or prev. The context owns the 4096-bin histogram (16 KiB, zeroed on the stream each
+ * call). bdpt_get_stats afterwards: kernel_ms and launches (2) of this call. Asynchronous on `hip_stream`;
+ * the host form stages the buffers, takes prev as 4 host words and returns the words. */
+typedef struct {
+    float norm;               /* multiplies color and aov on load, as bdpt_denoise_params.norm; > 0 */
+    float key;                /* the luminance the key percentile is exposed to; > 0 */
+    int32_t key_permille;     /* 1..1000: the percentile (in thousandths) of the counted pixels that is the key */
+    int32_t white_permille;   /* 1..1000: the percentile that becomes Reinhard's white point */
+    float rate;               /* (0, 1]: the step from prev's exposure towards this frame's; 1 ignores prev */
+    float fallback_exposure;  /* e when no pixel is counted; > 0 */
+    float fallback_white;     /* w when no pixel is counted; > 0 */
+} bdpt_meter_params;
+/* Defaults: recorded choices, not acceptance numbers. KEY 0.18 is photographic middle grey; the median as
+ * the key and the 99th percentile as white were looked at on the 4-spp HardLight 40 x 28 frame of
+ * tests/test_gpu_display.py and the Caustic frame of tools/display_cost.py and on nothing else; RATE 0.25
+ * on the three-frame camera move of the same test. */
+#define BDPT_METER_KEY 0.18f
+#define BDPT_METER_KEY_PERMILLE 500
+#define BDPT_METER_WHITE_PERMILLE 990
+#define BDPT_METER_RATE 0.25f
+#define BDPT_METER_BINS 4096
+int bdpt_meter(bdpt_ctx* ctx, int32_t width, int32_t height, const float* color_device, const float* aov_device,
+               const uint32_t* prev_device, const bdpt_meter_params* params, uint32_t* out_words_device,
+               void* hip_stream);
+int bdpt_meter_host(bdpt_ctx* ctx, int32_t width, int32_t height, const float* color_host, const float* aov_host,
+                    const uint32_t* prev_host, const bdpt_meter_params* params, uint32_t out_words[4]);
+/* The 4096 bin counts of the context's last bdpt_meter / bdpt_meter_host call (waits for it). */
+int bdpt_debug_meter_histogram(bdpt_ctx* ctx, uint32_t out[BDPT_METER_BINS]);
+
+/* (new) Float RGB -> 8-bit. color: width * height * 3 floats; meter (NULL: none): bdpt_meter's 4 words on
+ * the device, e = word 0 and w = word 1, so metering and display chain with no host round trip; without it
+ * e = params.exposure and w = params.white. out: width * height * channels bytes, rows in the framebuffer's
+ * order (row 0 = top, as bdpt_save_exr writes them); channels 3, or 4 with alpha = 255.
+ * Per channel value v of a pixel:
+ *   1. x = (v * norm) * e
+ *   2. x = x > 0 ? x : 0            (NaN and -0 become 0)
+ *   3. x = x < 65536 ? x : 65536    (+inf becomes 65536)
+ *   4. BDPT_TONE_CLAMP:    y = x
+ *      BDPT_TONE_REINHARD: y = (x * (1 + x * iw2)) / (1 + x), iw2 = 1 / (w * w) formed on the device
+ *      BDPT_TONE_FILMIC:   y = (x * (2.51 x + 0.03)) / (x * (2.43 x + 0.59) + 0.14), in this order: a = 2.51 *
+ *                          x; a = a + 0.03; n = x * a; b = 2.43 * x; b = b + 0.59; d = x * b; d = d + 0.14; y = n / d
+ *                          (Narkowicz's rational fit of the ACES curve; the constants rounded to float32)
+ *   5. code = #{k : T_k <= y}, T the table of params.encode
+ * The tone curve is applied per channel, which shifts the hue of saturated colours towards white as they
+ * brighten; a luminance-preserving curve is not built. 8 bits with no dither band smooth gradients.
+ * BDPT_ERR_INVALID, the field named in the message: a NULL color or out; width * height >= 2^28; norm,
+ * exposure or white not > 0 (exposure and white are checked with or without meter); an unknown tone, encode
+ * or channels; out overlapping color or meter. bdpt_get_stats afterwards: kernel_ms and launches (1) of this
+ * call. Asynchronous on `hip_stream`; the host form stages the buffers (meter: 4 host words) and is
+ * synchronous. A lane takes 4 pixels with three 16-byte loads and three dword stores when channels is 3,
+ * color is 16-byte and out 4-byte aligned; otherwise pixel by pixel, same bytes. */
+#define BDPT_TONE_CLAMP 0
+#define BDPT_TONE_REINHARD 1
+#define BDPT_TONE_FILMIC 2
+typedef struct {
+    float norm;        /* multiplies color on load; > 0 */
+    float exposure;    /* e without meter words; > 0 */
+    float white;       /* w without meter words (Reinhard's white point, in exposed units); > 0 */
+    int32_t tone;      /* BDPT_TONE_* */
+    int32_t encode;    /* BDPT_ENCODE_* */
+    int32_t channels;  /* 3 (RGB) or 4 (RGBA, alpha 255) */
+} bdpt_display_params;
+int bdpt_display(bdpt_ctx* ctx, int32_t width, int32_t height, const float* color_device,
+                 const uint32_t* meter_device, const bdpt_display_params* params, unsigned char* out_device,
+                 void* hip_stream);
+int bdpt_display_host(bdpt_ctx* ctx, int32_t width, int32_t height, const float* color_host,
+                      const uint32_t* meter_host, const bdpt_display_params* params, unsigned char* out_host);
+
 /* ---- several HIP devices in one process ---- */
 /* The reference fans the offline loop out over host threads (parallel_for,
  * src/core/parallelfor.h:25-65, renderer.cpp:157); here every device gets one
@@ -1204,6 +1319,17 @@ int bdpt_config_load_toml(const char* toml_path, bdpt_config* out);
 int bdpt_encode_exr(const float* rgb, int32_t width, int32_t height, unsigned char* out, int64_t capacity,
                     int64_t* size);
 int bdpt_save_exr(const float* rgb, int32_t width, int32_t height, const char* path);
+/* (new) 8-bit image files of bdpt_display's bytes (pixel-major, row 0 = top), host only, no dependency.
+ * PNG: channels 3 (colour type 2) or 4 (colour type 6), bit depth 8, every scanline with filter type 0, the
+ * data as zlib stored blocks (no compression) of at most 65535 bytes, with the unit's own CRC-32 and
+ * Adler-32. bdpt_encode_png as bdpt_encode_exr: out = NULL only reports *size. PPM: "P6\n<width>
+ * <height>\n255\n" and the RGB bytes, the header the texture reader of scene.cpp accepts (no comments); 3
+ * channels only. BDPT_ERR_INVALID: a NULL argument, width or height < 1, other channels, a capacity below
+ * *size; BDPT_ERR_IO: the file cannot be written. */
+int bdpt_encode_png(const unsigned char* pixels, int32_t width, int32_t height, int32_t channels, unsigned char* out,
+                    int64_t capacity, int64_t* size);
+int bdpt_save_png(const unsigned char* pixels, int32_t width, int32_t height, int32_t channels, const char* path);
+int bdpt_save_ppm(const unsigned char* rgb, int32_t width, int32_t height, const char* path);
 
 #ifdef __cplusplus
 }
